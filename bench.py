@@ -5,9 +5,13 @@ over 10,000 instances per GPU, heterogeneous LinkShape (latency/jitter/loss/dup/
 bandwidth), Poisson(0.5) packets per instance per 1 µs tick.  One step = one pass of the hot path
 over one window of `--window` ticks of offered traffic that is already resident in HBM (generated
 on the device before the timed region): filter -> netem -> HTB (k_sim), routing by destination
-shard, RCCL all-to-all (N > 1), per-destination delivery sort.  The same line carries an
-`at_1M_peers` object: the C4 gossip flood over 1,000,000 peers in total (split over the N GPUs),
-so both halves of BASELINE.json's metric ("at 10k & 1M peers") are measured in one run.
+shard, RCCL all-to-all (N > 1), per-destination delivery sort.  A plain run sets up, warms up,
+times the `--steps` steps and prints the line; `--dump-outputs DIR` also writes the last timed
+step's results as .npy files.  With `--full` the same line carries an `at_1M_peers` object: the C4
+gossip flood over 1,000,000 peers in total (split over the N GPUs), so both halves of
+BASELINE.json's metric ("at 10k & 1M peers") are measured in one run; `--full` also adds the
+`at_subcapacity` and `at_epochs` runs, the CPU oracle baseline beside every run and (N > 1)
+`weak_per_gpu`.
 
 `--workload gossip` (C4, BASELINE.json configs[3]): flood of 64 messages over --peers instances per
 GPU, degree 8, 1 KiB, L~U[5,50] ms, loss 1 %.  A step is one 5 ms window: forwards of the previous
@@ -20,8 +24,8 @@ Launch: N = 1 runs directly.  `--gpus N` with N > 1 and no WORLD_SIZE in the env
 ranks itself (torch.distributed.run, one process per GPU) from this parent, which never touches
 the GPU; under an external launcher WORLD_SIZE must equal --gpus.  The storm headline is
 BASELINE.json configs[2] at every N: 10,000 instances in total, split over the ranks (strong
-scaling); at N > 1 the line also carries `weak_per_gpu`, the same storm with 10,000 instances per
-rank.  The 1M-peer gossip is 1,000,000 peers in total at every N.  Cross-shard deliveries are
+scaling); at N > 1 a `--full` line also carries `weak_per_gpu`, the same storm with 10,000 instances
+per rank.  The 1M-peer gossip is 1,000,000 peers in total at every N.  Cross-shard deliveries are
 exchanged by the engine's RCCL all-to-all.
 """
 import argparse
@@ -91,7 +95,16 @@ def parse(argv=None):
                    help="total peers of the at_1M_peers run (split over the ranks)")
     p.add_argument("--launch-check", action="store_true",
                    help="launcher self-test: every rank reports RANK/WORLD_SIZE and exits before any GPU call")
+    p.add_argument("--full", action="store_true",
+                   help="besides the headline run: the CPU oracle baselines, the at_1M_peers gossip run, the "
+                        "at_subcapacity and at_epochs runs and (N > 1) weak_per_gpu; --no-cpu, --no-1m and "
+                        "--no-variants take single ones out again.  Without --full only the headline is measured")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the timed path handed its caller in the last step "
+                        "as DIR/<name>.npy (float32/float64, see dump_outputs)")
     a = p.parse_args(argv)
+    if not a.full:  # a plain run measures the headline figure and nothing else
+        a.no_cpu = a.no_1m = a.no_variants = True
     if not a.peers:
         a.peers = {"storm": 10_000, "gossip": 125_000, "epochs": 100_000, "bridge": 1000}[a.workload]
     if a.workload in ("epochs", "bridge"):
@@ -293,13 +306,13 @@ def run_bridge(a, world, rank, local, dist, want_cpu):
     src, dst, data, off = workloads.bridge_traffic(n)
     msgs = np.empty(4 * len(src), dtype=br.MSG_DTYPE)
     buf = np.empty(4 * len(data) + (1 << 20), dtype=np.uint8)
-    got = [0, 0]
+    got = [0, 0, 0]  # datagrams, payload bytes, datagrams of the last recv_into call
 
     def one():
         b.send_many(src, dst, data, off)
         b.step()
         while True:
-            k = b.recv_into(msgs, buf)
+            k = got[2] = b.recv_into(msgs, buf)
             got[0] += k
             got[1] += int(msgs["len"][:k].sum()) if k else 0
             if k < len(msgs):
@@ -311,7 +324,7 @@ def run_bridge(a, world, rank, local, dist, want_cpu):
     if dist:
         dist.barrier()
         torch.cuda.synchronize()
-    got[:] = [0, 0]
+    got[:] = [0, 0, 0]
     t0 = time.perf_counter()
     for _ in range(a.steps):
         one()
@@ -320,6 +333,18 @@ def run_bridge(a, world, rank, local, dist, want_cpu):
         dist.barrier()
     el = time.perf_counter() - t0
     s = eng.stats()
+    if a.dump_outputs:
+        # the datagrams the last step's final recv_into handed back (a step's receipts fit one call
+        # at the default sizes): a row per datagram, its payload as a byte sum
+        m = msgs[:got[2]]
+        lo = m["off"].astype(np.int64)
+        hi = lo + m["len"].astype(np.int64)
+        cs = np.concatenate(([0], np.cumsum(buf[:int(hi.max()) if len(m) else 0], dtype=np.int64)))
+        rows = np.stack([m[k].astype(np.float64) for k in ("t_ns", "src", "dst", "seq", "flags", "len")]
+                        + [(cs[hi] - cs[lo]).astype(np.float64)], axis=1)
+        d = Path(a.dump_outputs)
+        d.mkdir(parents=True, exist_ok=True)
+        np.save(d / (f"received_rank{rank}.npy" if world > 1 else "received.npy"), rows)
     b.close()
     eng.close()
     if dist:
@@ -431,7 +456,7 @@ def headline_plan(a, world):
     total, bounds = shard_bounds(a.peers, world, a.workload == "storm")
     plan = {"workload": a.workload, "peers_total": total, "bounds": bounds,
             "scaling": "strong" if a.workload == "storm" and world > 1 else "weak"}
-    if a.workload == "storm" and world > 1:
+    if a.workload == "storm" and world > 1 and a.full:
         plan["weak_per_gpu_peers_total"] = shard_bounds(a.peers, world, False)[0]
     if a.workload == "storm" and not a.no_1m:
         plan["at_1M_peers_total"] = shard_bounds(a.gossip_1m_peers, world, True)[0]
@@ -442,12 +467,53 @@ def headline_plan(a, world):
     return plan
 
 
+# Pre-generated windows resident in HBM at a time (a C3 window is ~160 MB of offered packets, a C5
+# epoch ~320 MB).  A run of more timed steps generates the next windows between timed stretches of
+# this many steps, outside the timing, so --steps sets the number of timed steps at any size.
+RESIDENT_WINDOWS = 256
+
+DUMP_MAX_ELEMS = 12_000_000  # float32 elements of the per-packet array (48 MB; the whole dump stays under 64 MB)
+STAT_NAMES = ("offered", "scheduled", "cloned", "corrupted", "bytes_scheduled", "now_tick", "flushed", "lost_in_flight")
+
+
+def dump_outputs(dirname, rank, world, eng, workload):
+    """--dump-outputs: what the timed path hands its caller after the last timed step, as .npy files
+    (with `_rank<r>` before the suffix at N > 1).  The bench's engine sorts its deliveries and discards
+    them (TGSIM_OPT_DISCARD_DELIVERIES), so the caller's results are
+      verdicts  float32, the last window's per-packet verdict bytes in generation order; a window of
+                more than DUMP_MAX_ELEMS / N packets is sampled at fixed (seeded, ascending) positions;
+      stats     float64, tgsim_stats after the last step: STAT_NAMES, then by_verdict in
+                abi.VERDICT_NAMES order (the counts of scheduled, cloned and corrupted records are
+                what the discarded deliveries leave behind);
+      reached   float64, gossip only: peers of this shard each flood has reached."""
+    import numpy as np
+
+    from testground_amd import abi
+
+    d = Path(dirname)
+    d.mkdir(parents=True, exist_ok=True)
+    v = eng.verdicts()
+    cap = max(1, DUMP_MAX_ELEMS // world)
+    if len(v) > cap:
+        v = v[np.sort(np.random.default_rng(0x7E576A0D).integers(0, len(v), cap))]
+    s = eng.stats()
+    out = {"verdicts": v.astype(np.float32),
+           "stats": np.array([s[k] for k in STAT_NAMES] + [s["by_verdict"][k] for k in abi.VERDICT_NAMES],
+                             dtype=np.float64)}
+    if workload == "gossip":
+        out["reached"] = eng.gossip_reached().astype(np.float64)
+    tag = f"_rank{rank}" if world > 1 else ""
+    for name, arr in out.items():
+        np.save(d / f"{name}{tag}.npy", arr)
+
+
 def run_workload(a, workload, peers, steps, warmup, window, lam, world, rank, local, dist, want_cpu,
-                 split=False, shapes=None):
+                 split=False, shapes=None, dump=None):
     """Builds one engine shard on this rank, brings the workload to its timed state, times `steps`
     steps (barrier + synchronize on both sides, max over ranks) and returns the rank-0 result object
     (None on the other ranks).  `peers` instances per rank (weak scaling), or with split=True
-    `peers` instances in total, split evenly over the ranks (strong scaling)."""
+    `peers` instances in total, split evenly over the ranks (strong scaling).  `dump`: the directory
+    of --dump-outputs."""
     import numpy as np
     import torch
 
@@ -539,7 +605,7 @@ def run_workload(a, workload, peers, steps, warmup, window, lam, world, rank, lo
         for _ in range(settle):  # untimed: bring every netem queue to its sustained state
             eng.gen_storm(lam, window)
             one_step()
-        for _ in range(warmup + steps):
+        for _ in range(warmup + min(steps, RESIDENT_WINDOWS)):
             eng.gen_storm(lam, window)  # inputs resident in HBM before the timed region
 
     def run_steps(n):
@@ -576,13 +642,27 @@ def run_workload(a, workload, peers, steps, warmup, window, lam, world, rank, lo
     if dist:
         dist.barrier()
         torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    run_steps(steps)
-    torch.cuda.synchronize()
-    if dist:
-        dist.barrier()
-    el = time.perf_counter() - t0
+    el, left = 0.0, steps
+    while True:
+        n = left if workload == "gossip" else min(left, RESIDENT_WINDOWS)
+        t0 = time.perf_counter()
+        run_steps(n)
+        torch.cuda.synchronize()
+        if dist:
+            dist.barrier()
+        el += time.perf_counter() - t0
+        left -= n
+        if not left:
+            break
+        for _ in range(min(left, RESIDENT_WINDOWS)):  # untimed: the next stretch's windows
+            eng.gen_storm(lam, window)
+        torch.cuda.synchronize()
+        if dist:
+            dist.barrier()
+            torch.cuda.synchronize()
     s1 = eng.stats()
+    if dump:
+        dump_outputs(dump, rank, world, eng, workload)
     offered = s1["offered"] - s0["offered"]
     scheduled = s1["scheduled"] - s0["scheduled"]
     verd = np.array([s1["by_verdict"][k] - s0["by_verdict"][k] for k in abi.VERDICT_NAMES], dtype=np.float64)
@@ -748,10 +828,10 @@ def main(argv=None):
         res = run_bridge(a, world, rank, local, dist, want_cpu=not a.no_cpu)
     else:
         # storm (configs[2]: "10k instances, 1/2/4/8 GPUs"): the headline is --peers instances in
-        # total, split over the ranks; the weak-scaling run (--peers per GPU) rides along at N > 1
+        # total, split over the ranks; with --full the weak-scaling run (--peers per GPU) rides along at N > 1
         res = run_workload(a, a.workload, a.peers, a.steps, a.warmup, a.window, a.lam, world, rank, local, dist,
-                           want_cpu=not a.no_cpu, split=a.workload == "storm")
-        if a.workload == "storm" and world > 1:
+                           want_cpu=not a.no_cpu, split=a.workload == "storm", dump=a.dump_outputs)
+        if a.workload == "storm" and world > 1 and a.full:
             w = run_workload(a, "storm", a.peers, a.steps, a.warmup, a.window, a.lam, world, rank, local, dist,
                              want_cpu=False)
             if res is not None:

@@ -10,6 +10,7 @@ ok() { # rc 0 = pass, 1 = test failures (keep going), anything else = stop
   if [ "$rc" -ne 0 ] && [ "$rc" -ne 1 ]; then echo "stopping after $what"; exit "$rc"; fi
 }
 STEPS="${STEPS:-all}"
+BENCH_ARGS="${BENCH_ARGS---full}"  # the bench step: the whole default line unless the caller names its arguments
 if [[ "$STEPS" == *test* || "$STEPS" == all ]]; then
   timeout -k 10 900 python -u -m pytest tests -m gpu -x -v --timeout 300 --timeout-method thread ${PYTEST_ARGS} > gpurun_out/pytest_gpu.log 2>&1
   ok $? pytest; tail -30 gpurun_out/pytest_gpu.log

@@ -15,7 +15,7 @@ if [ "${TESTS:-0}" = 1 ]; then
   tail -1 $O/smoke.log
 fi
 B="--shapes $SHAPES --no-1m"
-timeout -k 10 600 python bench.py $B ${BENCH_ARGS} > $O/bench.json 2> $O/bench.err || { tail $O/bench.err; exit 1; }
+timeout -k 10 600 python bench.py --full $B ${BENCH_ARGS} > $O/bench.json 2> $O/bench.err || { tail $O/bench.err; exit 1; }
 tail -c 400 $O/bench.json; echo
 rm -rf $O/trace
 timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o run -- python3 bench.py $B --no-cpu > $O/trace.log 2>&1 || { tail $O/trace.log; exit 1; }

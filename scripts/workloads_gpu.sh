@@ -14,7 +14,7 @@ if [ -z "$SKIP_TESTS" ]; then
   ok $? pytest; tail -15 gpurun_out/pytest_gpu.log
 fi
 # BENCHES: ';'-separated bench.py argument lists
-IFS=';' read -r -a runs <<< "${BENCHES:---workload gossip --no-cpu;--workload epochs --no-cpu;--workload gossip --peers 1000000}"
+IFS=';' read -r -a runs <<< "${BENCHES:---workload gossip --no-cpu;--workload epochs --no-cpu;--workload gossip --peers 1000000 --full}"
 for args in "${runs[@]}"; do
   tag=$(echo "$args" | tr -c 'a-zA-Z0-9' '_')
   timeout -k 10 900 python bench.py $args > "gpurun_out/bench_${tag}.log" 2>&1

@@ -27,9 +27,27 @@ def test_launch_command():
     assert cmd[-3:] == ["--gpus", "4", "--steps", "5"][-3:]
 
 
+def test_plain_run_measures_only_the_headline():
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert (a.steps, a.warmup, a.dump_outputs) == (7, 2, None)
+    assert a.no_cpu and a.no_1m and a.no_variants
+    for world in (1, 2):
+        plan = bench.headline_plan(a, world)
+        assert plan["peers_total"] == 10_000 and plan["cpu_baseline_ranks"] == []
+        assert not {"weak_per_gpu_peers_total", "at_1M_peers_total", "at_subcapacity_total", "at_epochs_total"} & set(plan)
+    # --full brings every rider back; the --no-* options still take single ones out
+    f = bench.parse(["--full"])
+    assert not (f.no_cpu or f.no_1m or f.no_variants)
+    plan = bench.headline_plan(f, 1)
+    assert plan["at_1M_peers_total"] == 1_000_000 and plan["at_epochs_total"] == 100_000
+    assert plan["at_subcapacity_total"] == 10_000 and plan["cpu_baseline_ranks"] == [0]
+    g = bench.parse(["--full", "--no-1m", "--dump-outputs", "out"])
+    assert g.no_1m and not g.no_cpu and not g.no_variants and g.dump_outputs == "out"
+
+
 def test_two_ranks_spawned_on_cpu():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
-    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--launch-check"],
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--full", "--launch-check"],
                        capture_output=True, text=True, timeout=300, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [json.loads(x) for x in r.stdout.splitlines() if x.startswith("{")]
