@@ -43,7 +43,7 @@ if a.fused:
 n = e._lib.tgsim_debug_stamps(e._h, None, 0)
 st = np.zeros(n, dtype=np.uint64)
 e._lib.tgsim_debug_stamps(e._h, st.ctypes.data, n)
-st = st.reshape(-1, 32).astype(np.int64)
+st = st.reshape(-1, 40).astype(np.int64)
 live = st[:, 4] > 0
 st = st[live]
 us = lambda x: x * 10 / 1000  # noqa: E731  (s_memrealtime: 100 MHz)

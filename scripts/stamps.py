@@ -48,7 +48,7 @@ for _ in range(a.steps):
 n = e._lib.tgsim_debug_stamps(e._h, None, 0)
 st = np.zeros(n, dtype=np.uint64)
 e._lib.tgsim_debug_stamps(e._h, st.ctypes.data, n)
-st = st.reshape(-1, 32).astype(np.int64)
+st = st.reshape(-1, 40).astype(np.int64)
 t0 = st[:, 0].min()
 ph = np.diff(st[:, :5], axis=1) * 10 / 1000  # us (100 MHz)
 tot = (st[:, 4] - st[:, 0]) * 10 / 1000
@@ -65,16 +65,20 @@ start = (st[:, 0] - t0) * 10 / 1000
 end = (st[:, 4] - t0) * 10 / 1000
 ts = np.linspace(0, end.max(), 20)
 print("  concurrency over time:", [int(((start <= t) & (end > t)).sum()) for t in ts])
-pf = st[:, 8:32]  # profile build counters (see k_sim PROF_* slots)
+pf = st[:, 8:40]  # profile build counters (see k_sim PROF_* slots)
 nb = np.maximum(nbat, 1)
 names = {0: "parallel", 1: "windows", 7: "S+htb", 8: "departures", 9: "decide", 10: "window-end",
          11: "commit", 4: "insert", 14: "ins-search", 15: "ins-shift", 12: "serve-mid", 13: "serve-end",
-         16: "refill", 20: "rf-count", 21: "rf-take", 22: "rf-insert"}
+         16: "refill", 20: "rf-count", 21: "rf-take", 22: "rf-insert", 24: "loop-tail"}
 print("  cycles per batch (mean over wgs): " + ", ".join(f"{v} {np.mean(pf[:, k] / nb):.0f}" for k, v in names.items()))
 print(f"  per batch: {np.mean(pf[:, 3] / nb):.2f} windows, {np.mean(pf[:, 2] / nb):.2f} full-queue runs, "
       f"{np.mean(pf[:, 5] / nb):.2f} inserted items, {np.mean(pf[:, 6] / nb):.2f} shift chunks, "
       f"{np.mean(pf[:, 17] / nb):.2f} refill rounds, {np.mean(pf[:, 18] / nb):.2f} refilled items, "
       f"{np.mean(pf[:, 19] / nb):.2f} pool appends, {np.mean(pf[:, 23] / nb):.2f} windows ended by an admission")
+# delay draws (Philox counter 1 + tabledist) evaluated, per admitted original that needs one
+draws = lambda m: pf[m, 25].sum() / max(pf[m, 26].sum(), 1)  # noqa: E731
+print(f"  per batch: {np.mean(pf[:, 25] / nb):.1f} delay draws for {np.mean(pf[:, 26] / nb):.1f} admitted originals "
+      f"with a drawn delay: {draws(slice(None)):.2f} draws per admitted packet")
 # the heavy-source chain's limit.  A sub-window ends early when an item admitted in
 # it becomes eligible before a later packet of it (reorder, or a delay <= 0 with J > L); absorbing
 # those into the sub-window's departure scan would leave windows - admission-ended sub-windows.
@@ -90,7 +94,7 @@ print("  slowest workgroups (= sources):")
 for i in np.argsort(-tot)[:a.top]:
     line = (f"    src {src_of[i]:7d} start {start[i]:7.1f} us {tot[i]:8.1f} us  batches {nbat[i]:3d}  "
             f"q {st[i, 7] >> 32}/{st[i, 7] & 0xffffffff}  win x{pf[i, 3]} items {pf[i, 5]} chunks {pf[i, 6]} "
-            f"refills {pf[i, 17]}/{pf[i, 18]} pool+ {pf[i, 19]}  "
+            f"refills {pf[i, 17]}/{pf[i, 18]} pool+ {pf[i, 19]} draws {pf[i, 25]}/{pf[i, 26]}  "
             + " ".join(f"{v} {pf[i, k] // nb[i]}" for k, v in names.items()))
     if shapes:
         s = shapes[src_of[i]]
@@ -114,7 +118,8 @@ if shapes:  # per bandwidth class: phase times and profile cycles per batch
         line = (f"  bw {c:6.0f} Mbit/s: {m.sum():5d} srcs, total {tot[m].mean():6.1f} us (load {ph[m, 0].mean():5.2f}, "
                 f"batches {ph[m, 1].mean():6.2f}, end {ph[m, 2].mean():5.2f}, wb {ph[m, 3].mean():5.2f}); per batch: "
                 + ", ".join(f"{v} {np.mean(pf[m, k] / nb[m]):.0f}" for k, v in names.items()) +
-                f"; windows {np.mean(pf[m, 3] / nb[m]):.2f}, fullq {np.mean(pf[m, 2] / nb[m]):.2f}")
+                f"; windows {np.mean(pf[m, 3] / nb[m]):.2f}, fullq {np.mean(pf[m, 2] / nb[m]):.2f}, "
+                f"draws per admitted {draws(m):.2f}")
         print(line)
 if shapes:
     lat = np.array([shapes[i].Latency for i in src_of]) / 1e6

@@ -36,7 +36,7 @@ for _ in range(a.groups):
 n = e._lib.tgsim_debug_stamps(e._h, None, 0)
 st = np.zeros(n, dtype=np.uint64)
 e._lib.tgsim_debug_stamps(e._h, st.ctypes.data, n)
-st = st.reshape(-1, 32).astype(np.int64)
+st = st.reshape(-1, 40).astype(np.int64)
 g = len(st) // a.peers
 t0 = st[:, 0].min()
 start, end = (st[:, 0] - t0) / 100, (st[:, 4] - t0) / 100  # us

@@ -14,7 +14,7 @@ ROOT = PKG.parent
 CSRC = PKG / "csrc"
 LIB = PKG / "libtgsim.so"
 SOURCES = [CSRC / "tgsim_kernels.hip", CSRC / "tgsim_engine.cpp", CSRC / "tgsim_bridge.cpp", CSRC / "tgsim_comm.cpp"]
-HEADERS = [CSRC / "tgsim_internal.h", CSRC / "tgsim_launch.h", ROOT / "include" / "tgsim.h"]
+HEADERS = [CSRC / "tgsim_internal.h", CSRC / "tgsim_launch.h", CSRC / "tgsim_fastmod.h", ROOT / "include" / "tgsim.h"]
 ORACLE_DIR = ROOT / "oracle"
 ORACLE_LIB = ORACLE_DIR / "build" / "libtgoracle.so"
 

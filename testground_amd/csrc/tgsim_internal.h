@@ -180,7 +180,8 @@ struct SimArgs {
   // (at exactly 256 B, kernarg windows k * 256, the scheduler had spilled 9 more SGPRs in k_sim_fused)
 };
 static_assert(sizeof(SimArgs) == 280, "SimArgs layout");
-constexpr uint32_t kStampSlots = 32;  // 8 phase stamps + 24 profile counters (TGSIM_PROFILE)
+constexpr uint32_t kProfSlots = 32;
+constexpr uint32_t kStampSlots = 8 + kProfSlots;  // 8 phase stamps + the profile counters (TGSIM_PROFILE)
 
 // Fused launch of up to kFuseMax consecutive windows (k_sim_fused).  Window-major:
 // ticket t -> window t / S of the (t % S)-th source in dispatch order, started once the source's

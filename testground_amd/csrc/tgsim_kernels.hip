@@ -14,6 +14,7 @@
 //                  by (t, src, seq, clone-first).
 #include <errno.h>
 #include <stdlib.h>
+#include "tgsim_fastmod.h"
 #include "tgsim_launch.h"
 
 namespace tgsim {
@@ -236,6 +237,14 @@ __device__ __forceinline__ uint64_t delayed(const SrcParams& p, uint64_t T, uint
   return delay > 0 ? T + (uint64_t)delay : T;
 }
 
+// The same with the division done once per source: rcp = fastmod_rcp(2 sigma), exact for every raw
+// (tgsim_fastmod.h).
+__device__ __forceinline__ uint64_t delayed(const SrcParams& p, uint64_t T, uint32_t raw, uint32_t rcp) {
+  if (p.sigma == 0) return T + p.lat_ns;
+  const int64_t delay = (int64_t)fastmod_u32(raw, 2u * (uint32_t)p.sigma, rcp) + (int64_t)p.lat_ns - (int64_t)p.sigma;
+  return delay > 0 ? T + (uint64_t)delay : T;
+}
+
 // Gossip receipt of one emitted record (single shard; what k_gossip_recv does at delivery): the
 // earliest receipt tick of flood seq / degree at the destination, which becomes pending unless it
 // has forwarded the flood already (fw: the destination's forwarded mask).  Receipts are order-free
@@ -360,10 +369,18 @@ __device__ __forceinline__ void stamp(const SimArgs& a, uint32_t wg, uint32_t la
 #define PROF_T0(n) const uint64_t _pt##n = __builtin_amdgcn_s_memtime()
 #define PROF_ADD(k, n) (pf[k] += __builtin_amdgcn_s_memtime() - _pt##n)
 #define PROF_CNT(k, v) (pf[k] += (v))
+// the loop tail: from the end of a batch's windows to the next batch's first counter, the back
+// edge and whatever it waits for included
+#define PROF_TAIL_VAR() uint64_t _pt_tail = 0
+#define PROF_TAIL_T0() (_pt_tail = __builtin_amdgcn_s_memtime())
+#define PROF_TAIL_ADD(k) (pf[k] += _pt_tail ? __builtin_amdgcn_s_memtime() - _pt_tail : 0)
 #else
 #define PROF_T0(n) do {} while (0)
 #define PROF_ADD(k, n) do {} while (0)
 #define PROF_CNT(k, v) do {} while (0)
+#define PROF_TAIL_VAR() do {} while (0)
+#define PROF_TAIL_T0() do {} while (0)
+#define PROF_TAIL_ADD(k) do {} while (0)
 #endif
 
 // Wave-uniform queue state of the source plus the helpers that operate on it.  Every member is
@@ -433,7 +450,7 @@ struct SimQueue {
   uint32_t sched, corrupted, lost;
   uint64_t bytes;
 #ifdef TGSIM_PROFILE
-  uint64_t pf[24];
+  uint64_t pf[kProfSlots];
 #endif
 
   __device__ __forceinline__ uint4& slot(uint32_t k) { return lds.slot[(rh + k) & kSlotMask]; }
@@ -1073,7 +1090,7 @@ __device__ __forceinline__ uint32_t sim_source(const SimArgs& a, const uint32_t 
   Q.sched = Q.corrupted = Q.lost = 0;
   Q.bytes = 0;
 #ifdef TGSIM_PROFILE
-  for (int k = 0; k < 24; ++k) Q.pf[k] = 0;
+  for (int k = 0; k < (int)kProfSlots; ++k) Q.pf[k] = 0;
   uint64_t* pf = Q.pf;
 #endif
   // ---- load the head of the departure ring and the eligibility queue into LDS
@@ -1087,7 +1104,7 @@ __device__ __forceinline__ uint32_t sim_source(const SimArgs& a, const uint32_t 
   uint32_t rl = 0;  // ring entries loaded (a prefix)
   uint64_t idx = sbeg + lane;  // the lane's next offered record
   const uint64_t last_in = send > sbeg ? send - 1 : sbeg;
-  InRec rec = {}, rec2 = {};   // records of batches b and b + 1
+  InRec rec = {}, rec2 = {};   // records of batches b and b + 1 (see the batch loop for what stays in flight)
   uint32_t wbase = 0, wctl = 0, wdue = 0, nd = 0;  // wheel: base id, control word, lane j: bucket j's due count
   uint64_t wlast = 0;                              // the last bucket id due before H
   // due item c + lane: its bucket (from the base) is the first whose running sum exceeds it (the
@@ -1131,7 +1148,7 @@ __device__ __forceinline__ uint32_t sim_source(const SimArgs& a, const uint32_t 
         qv[u] = gh[(qh + (k < qn ? k : ql)) & (kHeapCap - 1)];
       }
     }
-    // the records of the first two batches (two batches in flight from here on); branch-free loads, a
+    // the records of the first two batches; branch-free loads, a
     // lane past the end re-reads the last record (never used): a conditional load left a wait inside
     // its branch
     if (send > sbeg) {
@@ -1230,6 +1247,7 @@ __device__ __forceinline__ uint32_t sim_source(const SimArgs& a, const uint32_t 
   const bool plain = src_on && !a.any_disabled && pp.rule_n == 0;
   const uint32_t ext_v = (pp.shift_ext >> 8 & 1u) ? TGSIM_V_EXTERNAL : TGSIM_V_NO_ROUTE;
   const bool corr = (pp.rho_dup | pp.rho_cor | pp.rho_reo) != 0;
+  const uint32_t sig_rcp = fastmod_rcp(2u * (uint32_t)pp.sigma);  // the delay draws' modulus, divided once
   const uint32_t lim = a.queue_limit;
   uint32_t last_dup = st.last_dup, last_cor = st.last_cor, last_reo = st.last_reo;
   // per-lane verdict counts, reduced over the wave once at the end (no wave-uniform counters held
@@ -1269,19 +1287,25 @@ __device__ __forceinline__ uint32_t sim_source(const SimArgs& a, const uint32_t 
   // below the netem limit (sparse sources: gossip, ping-pong, splitbrain)
   const bool open_q = kOpen || (!corr && (uint64_t)Q.rn + Q.qn + Q.pn + Q.fn + Q.pk + 2 * (send - sbeg) < lim);
   uint64_t T_enq = 0;  // open queue: offer time of the last packet that reached the netem enqueue
-  // the verdict bytes of batch b are stored during batch b + 1: stored last in their own batch,
-  // their write latency sat in front of the loop's back edge (vmcnt counts stores)
+  // the verdict bytes of batch b are stored during batch b + 1.  (As built, the copy rec = rec2
+  // below stands on the loop's back edge behind a vmcnt(0): every batch ends by waiting for its own
+  // stores and atomics and for the record load issued at its top, so the records are less than one
+  // batch ahead.  The profile build's loop-tail counter puts that tail at 800 of a batch's 8,500
+  // cycles; a form with the one wait behind the parallel phase was bit-exact and slower,
+  // profiles/LOG.md round 7.)
   uint64_t v_idx = 0;
   uint32_t v_out = 0;
   bool v_pend = false;
+  PROF_TAIL_VAR();
   for (uint32_t b = 0; b < n_batches; ++b) {
+    PROF_TAIL_ADD(24);
     PROF_T0(b);
     const uint64_t my_idx = idx;
     const bool staged = my_idx < send;
     const InRec r = rec;
     idx += kWave;
     rec = rec2;
-    // in flight two batches ahead (three: no gain, A/B round 2)
+    // issued two batches ahead (three: no gain, A/B round 2)
     rec2 = a.in[idx + kWave < send ? idx + kWave : last_in];
     if (v_pend) a.verdict[v_idx] = (uint8_t)v_out;
     const uint64_t T = a.t0_ns + (uint64_t)r.tick * a.tick_ns;
@@ -1312,7 +1336,7 @@ __device__ __forceinline__ uint32_t sim_source(const SimArgs& a, const uint32_t 
             } else {
               cst = 2;
               if (pp.thr_cor && pp.thr_cor >= r2[1]) flc |= TGSIM_FLAG_CORRUPT;
-              ec = (pp.thr_reo && pp.thr_reo >= r2[2]) ? T : delayed(pp, T, r2[3]);
+              ec = (pp.thr_reo && pp.thr_reo >= r2[2]) ? T : delayed(pp, T, r2[3], sig_rcp);
               if (ec > kEMask) { perr = 1; ec = kEMask; }
             }
           }
@@ -1347,6 +1371,11 @@ __device__ __forceinline__ uint32_t sim_source(const SimArgs& a, const uint32_t 
       }
       // ---------- windows
       uint64_t pend = (kOpen || open_q) ? 0ull : __ballot(cand);
+      // the original's drawn delay, once per packet: a packet admitted in a sub-window that ends in
+      // front of it is decided again in the next one, and the draw depends on the packet alone
+      // (kNoDraw: not drawn yet; an eligibility time is below 2^63)
+      constexpr uint64_t kNoDraw = ~0ull;
+      uint64_t eo_drawn = kNoDraw;
       if constexpr (!kOpen) while (pend) {
         PROF_CNT(3, 1);
         if (Q.rn + Q.qn + Q.pn + Q.fn + Q.pk >= lim) {
@@ -1451,13 +1480,16 @@ __device__ __forceinline__ uint32_t sim_source(const SimArgs& a, const uint32_t 
         // delay draw only for admitted originals
         uint64_t eo = reo_o ? T : T + pp.lat_ns;
         const bool need1 = orig_adm && !reo_o && pp.sigma != 0;
-        if (__ballot(need1)) {
-          if (need1) {
+        const bool draw1 = need1 && eo_drawn == kNoDraw;
+        if (__ballot(draw1)) {
+          PROF_CNT(25, (uint32_t)__popcll(__ballot(draw1)));
+          if (draw1) {
             uint32_t r1[4];
             philox(Q.src, r.dst, r.seq, 1, a.key0, a.key1, r1);
-            eo = delayed(pp, T, r1[0]);
+            eo_drawn = delayed(pp, T, r1[0], sig_rcp);
           }
         }
+        if (need1) eo = eo_drawn;
         if (orig_adm && eo > kEMask) { perr = 1; eo = kEMask; }
         PROF_ADD(9, s3);
         PROF_T0(s4);
@@ -1489,6 +1521,7 @@ __device__ __forceinline__ uint32_t sim_source(const SimArgs& a, const uint32_t 
         }
         const bool inwin = inw && lane < wend;
         const uint64_t mwin = __ballot(inwin);
+        PROF_CNT(26, (uint32_t)__popcll(__ballot(inwin && need1)));  // admitted originals with a drawn delay
         uint64_t T_w, e_new = ~0ull;  // e_new: earliest new item (>= T_w unless madm)
         uint32_t Dw = 0, lw = 0;
         if (mwin) {
@@ -1594,6 +1627,7 @@ __device__ __forceinline__ uint32_t sim_source(const SimArgs& a, const uint32_t 
         if (lane == j) vout = vj;
       }
     }
+    PROF_TAIL_T0();
     v_pend = staged;
     v_idx = my_idx;
     v_out = vout;
@@ -1753,7 +1787,7 @@ __device__ __forceinline__ uint32_t sim_source(const SimArgs& a, const uint32_t 
   stamp(a, wg, lane, 6, __builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (31 << 11)));  // HW_ID
   stamp(a, wg, lane, 7, ((uint64_t)(Q.qn + Q.pn + Q.fn) << 32) | Q.rn);
 #ifdef TGSIM_PROFILE
-  for (int k = 0; k < 24; ++k) stamp(a, wg, lane, 8 + k, Q.pf[k]);
+  for (int k = 0; k < (int)kProfSlots; ++k) stamp(a, wg, lane, 8 + k, Q.pf[k]);
 #endif
   const uint32_t sched = readlane32((uint32_t)scan_sum_i32((int32_t)Q.sched), kWave - 1);
   const uint32_t corrupted = readlane32((uint32_t)scan_sum_i32((int32_t)Q.corrupted), kWave - 1);
