@@ -405,7 +405,7 @@ struct tgsim_engine_s {
   uint64_t sim_launches = 0;
   bool stamps_on = false;
   DevBuf<uint32_t> d_order;  // dispatch order of the next k_sim, computed behind this one
-  DevBuf<uint32_t> d_work;   // sparse steps: k_sim_sparse's deferred sources, [0] = count, then ids
+  DevBuf<uint32_t> d_work;   // sparse steps: the work buffer (SparseWork)
   int sparse_mode = -1;      // TGSIM_SPARSE: -1 auto, 0 never, 1 always
   bool rotated = false;      // a sparse step may have left queues in place (head slot != 0)
   bool sparse_seen = false;  // h_work holds a measured worklist size
@@ -1203,15 +1203,13 @@ int run_sim(Eng* E, uint32_t n_ticks, bool local_hist = false) {
     a.g_floods = E->gossip.n_floods;
     a.g_degree = E->gossip.degree;
   }
-  a.worklist = nullptr;
+  a.work.w = nullptr;
   if (sparse) {
-    // [0] the worklist's count, [1] k_sim_multi's, [2] emit-pool records claimed, [3] unused, the
-    // worklist's sources, 8 words of TGSIM_DEFER_STATS, then k_sim_multi's sources
-    if (E->d_work.cap < 2 * static_cast<size_t>(E->S) + 4 + 8) {
-      HIPCHK(E->d_work.ensure(2 * static_cast<size_t>(E->S) + 4 + 8));
+    if (E->d_work.cap < SparseWork::words(E->S)) {
+      HIPCHK(E->d_work.ensure(SparseWork::words(E->S)));
       HIPCHK(hipMemsetAsync(E->d_work.p, 0, sizeof(uint32_t) * E->d_work.cap, E->st));
     }
-    a.worklist = E->d_work.p + 4;
+    a.work.w = E->d_work.p;
     a.order = nullptr;  // (stamps, when on, are indexed by source: n_wg = S)
   }
   // the simulate kernels' span (bench: roofline): timing events cost the windows they bracket (a

@@ -125,6 +125,20 @@ constexpr uint32_t kStatCopies = TGSIM_STAT_COPIES;  // 64 had ~16k adds per add
                                                      // each), ~0.2 ms per window
 constexpr uint32_t kErrTimeOverflow = 1u;
 
+// The work buffer of a sparse window (SimArgs::work; allocated by run_sim, words(S) for S sources):
+// three counters, zeroed before k_sim_sparse and again by k_work_done behind the window's last
+// kernel, then the two lists of sources the counters count.
+struct SparseWork {
+  uint32_t* w;
+  static constexpr uint32_t kHeader = 4;  // the counters, padded to 16 B
+  static constexpr size_t words(size_t S) { return kHeader + 2 * S; }
+  __host__ __device__ uint32_t* list_n() const { return w; }       // sources left for k_sim_list
+  __host__ __device__ uint32_t* multi_n() const { return w + 1; }  // sources k_sim_sparse left for k_sim_multi
+  __host__ __device__ uint32_t* pool_n() const { return w + 2; }   // emit-pool records claimed (emit_claim)
+  __host__ __device__ uint32_t* list() const { return w + kHeader; }
+  __host__ __device__ uint32_t* multi(uint32_t S) const { return w + kHeader + S; }
+};
+
 struct SimArgs {
   const SrcParams* params;
   SrcState* state;
@@ -147,12 +161,10 @@ struct SimArgs {
   uint64_t* stamps;         // diagnostics: kStampSlots s_memrealtime stamps per workgroup, or null
   unsigned long long* dst_cnt;  // single shard: per-destination histogram of the emitted records, or null
   uint64_t* err_host;       // pinned host word: the sticky error bits, or null
-  // sparse steps: the sources k_sim_sparse left for k_sim_list; worklist[-4] their count,
-  // worklist[-3] k_sim_multi's, worklist[-2] the emit-pool records claimed (zeroed before k_sim_sparse)
-  uint32_t* worklist;
+  SparseWork work;          // sparse steps (null otherwise)
   // The rest of the emit layout (EmitRead): source s's first 2 n_s + emit_r records at its region; a
   // source with more (it served more than emit_r old queue items in the window) claims the rest from
-  // emit_pool (worklist[-2] counts the records claimed, emit_pool_cap bounds them) and stores where
+  // emit_pool (work.pool_n() counts the records claimed, emit_pool_cap bounds them) and stores where
   // they start in emit_pool_idx[s].  emit_r = kHeapCap: the classic layout, which the netem limit
   // keeps every source inside (no pool; dense steps and fused windows always use it).
   tgsim_delivery* emit_pool;

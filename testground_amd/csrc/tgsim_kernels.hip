@@ -298,20 +298,25 @@ __device__ __forceinline__ EmitOut emit_out(const SimArgs& a, uint32_t s, uint64
   o.cap = (uint32_t)(2 * (send - sbeg)) + a.emit_r;
   return o;
 }
+// Raises sticky error bits (one lane): the statistics' error word, and the host's pinned copy, which
+// the host reads at its sync points.
+__device__ __forceinline__ void raise_error(const SimArgs& a, uint32_t bits) {
+  atomicOr(&a.stats[kStErr], (unsigned long long)bits);
+  if (a.err_host) __hip_atomic_store(a.err_host, (uint64_t)bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
 // For up to `total` records: what exceeds the region comes from the pool, one atomic (lane 0; the
 // caller is wave-uniform).  The classic layout (emit_r = kHeapCap) never needs it.
 __device__ __forceinline__ void emit_claim(const SimArgs& a, uint32_t s, EmitOut& o, uint32_t total, uint32_t lane) {
   if (total <= o.cap) return;
   const uint32_t need = total - o.cap;
   uint32_t at = 0;
-  if (lane == 0) at = atomicAdd(a.worklist - 2, need);
+  if (lane == 0) at = atomicAdd(a.work.pool_n(), need);
   at = (uint32_t)__builtin_amdgcn_readfirstlane((int)at);
   if ((uint64_t)at + need <= a.emit_pool_cap) {
     o.over = a.emit_pool + at;
     if (lane == 0) a.emit_pool_idx[s] = at;
   } else if (lane == 0) {
-    atomicOr(&a.stats[kStErr], (unsigned long long)kErrEmitPool);
-    if (a.err_host) __hip_atomic_store(a.err_host, (uint64_t)kErrEmitPool, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    raise_error(a, kErrEmitPool);
   }
 }
 
@@ -1809,11 +1814,7 @@ __device__ __forceinline__ uint32_t sim_source(const SimArgs& a, const uint32_t 
     // what the model charged and the window did not move (wraps below zero when it moved more: the
     // readers sum modulo 2^64)
     if (qbytes != moved_end) atomicAdd(&sc[kStCarrySkip], (unsigned long long)(qbytes - moved_end));
-    if (err) {
-      atomicOr(&a.stats[kStErr], (unsigned long long)kErrTimeOverflow);
-      if (a.err_host)  // the host's pinned copy (sticky; read at its sync points)
-        __hip_atomic_store(a.err_host, (uint64_t)kErrTimeOverflow, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
+    if (err) raise_error(a, kErrTimeOverflow);
   }
   return (uint32_t)__builtin_amdgcn_readfirstlane((int)next_ticket);
 }
@@ -1937,17 +1938,244 @@ __device__ __forceinline__ bool emit_record(const SimArgs& a, const EmitOut& eo,
 }
 
 // ---------------------------------------------------------------------------------------------
+// The register-only family of the sparse windows: k_sim_sparse (sparse_source) takes every source,
+// k_sim_multi (multi_source) the FIFO sources it hands on, k_sim_list (sim_source, the LDS path) the
+// rest.  The first two share the steps below, each written once: the per-packet netem decisions
+// (netem_decide), the FIFO test of a round of candidates (fifo_round), the release of the old
+// departure ring (release_old_ring), one served round of 64 lanes (serve_round), the verdict counts
+// (tally_verdicts) and the state store and statistics (finish_source).  What a caller keeps is where
+// its queue and candidates live: registers (sparse_source), or HBM behind the queue's tail
+// (multi_source).  DESIGN.md §5.4.
+
+// Source s goes on to k_sim_list.
+__device__ __forceinline__ void defer_to_list(const SimArgs& a, uint32_t s, uint32_t lane) {
+  if (lane == 0) a.work.list()[atomicAdd(a.work.list_n(), 1u)] = s;
+}
+
+// One offered packet's filter and netem decisions (queue-independent; every candidate is admitted):
+// Philox draw 0 decides loss, duplication, corruption and reordering, draw 2 the clone, draw 1 the
+// jittered delay.  A `plain` source skips the filter's gathers.  perr is set when a time left the
+// item format (kErrTimeOverflow).
+struct Offer {
+  uint32_t vout;  // the verdict byte: the clone's verdict << 4 | the packet's
+  bool cand;      // the packet is queued as io
+  uint32_t cst;   // its clone: 0 none, 1 lost before the queue, 2 queued (as ic, with kClone)
+  uint4 io, ic;
+};
+// kClone = false (multi_source: a queued clone only makes the source defer) leaves ic unset.
+template <bool kClone>
+__device__ __forceinline__ Offer netem_decide(const SimArgs& a, const SrcParams& pp, uint32_t src, bool src_on, bool plain,
+                                              uint32_t ext_v, bool staged, const InRec& r, uint64_t T, uint32_t& perr) {
+  const uint32_t len = r.len & 0xFFFFu;
+  uint32_t fv = 0u;
+  if (staged) fv = plain ? (r.dst == TGSIM_EXTERNAL ? ext_v : kFvPass) : filter(a, pp, src_on, r.dst);
+  Offer o = {0xF0u | fv, false, 0u, make_uint4(0, 0, 0, 0), make_uint4(0, 0, 0, 0)};
+  if (staged && fv == kFvPass) {
+    uint32_t r0[4];
+    philox(src, r.dst, r.seq, 0, a.key0, a.key1, r0);
+    const int count = 1 + (pp.thr_dup && pp.thr_dup >= r0[0]) - (pp.thr_loss && pp.thr_loss >= r0[1]);
+    if (count == 0) {
+      o.vout = 0xF0u | TGSIM_V_LOSS;
+    } else {
+      o.cand = true;
+      if (count == 2) {
+        uint32_t r2[4];
+        philox(src, r.dst, r.seq, 2, a.key0, a.key1, r2);
+        if (pp.thr_loss && pp.thr_loss >= r2[0]) {
+          o.cst = 1;
+        } else {
+          o.cst = 2;
+          if constexpr (kClone) {
+            uint32_t flc = TGSIM_FLAG_DUP;
+            if (pp.thr_cor && pp.thr_cor >= r2[1]) flc |= TGSIM_FLAG_CORRUPT;
+            uint64_t ec = (pp.thr_reo && pp.thr_reo >= r2[2]) ? T : delayed(pp, T, r2[3]);
+            if (ec > kEMask) { perr = 1; ec = kEMask; }
+            o.ic = make_item(ec, len, flc, r.seq, r.dst);
+          }
+        }
+      }
+      const uint32_t flo = (pp.thr_cor && pp.thr_cor >= r0[2]) ? TGSIM_FLAG_CORRUPT : 0u;
+      const bool reo_o = pp.thr_reo && pp.thr_reo >= r0[3];
+      uint64_t eo = reo_o ? T : T + pp.lat_ns;
+      if (!reo_o && pp.sigma != 0) {
+        uint32_t r1[4];
+        philox(src, r.dst, r.seq, 1, a.key0, a.key1, r1);
+        eo = delayed(pp, T, r1[0]);
+      }
+      if (eo > kEMask) { perr = 1; eo = kEMask; }
+      o.io = make_item(eo, len, flo, r.seq, r.dst);
+      const uint32_t cv = o.cst == 0 ? TGSIM_V_NONE : o.cst == 1 ? TGSIM_V_LOSS : TGSIM_V_SCHEDULED;
+      o.vout = (cv << 4) | TGSIM_V_SCHEDULED;
+    }
+  }
+  return o;
+}
+
+// FIFO test of one round of candidates (io where cand, mc their ballot): none precedes its
+// predecessor -- the candidate before it in the round, else `last`, the last item so far (if any).
+__device__ __forceinline__ bool fifo_round(bool cand, const uint4& io, uint64_t mc, const uint4& last, bool has_last,
+                                           uint32_t lane, uint64_t below) {
+  const uint64_t bc = mc & below;
+  const uint32_t pl = bc ? 63u - (uint32_t)__builtin_clzll(bc) : lane;
+  TG_FULL_EXEC("ds_permute");
+  uint4 prev = make_uint4((uint32_t)__builtin_amdgcn_ds_bpermute((int)(pl << 2), (int)io.x),
+                          (uint32_t)__builtin_amdgcn_ds_bpermute((int)(pl << 2), (int)io.y),
+                          (uint32_t)__builtin_amdgcn_ds_bpermute((int)(pl << 2), (int)io.z), 0u);
+  if (!bc) prev = last;
+  return __ballot(cand && (bc || has_last) && item_lt(io, prev)) == 0;
+}
+
+// The departure ring is (old ring ++ served).  The last enqueue (at T_enq, after serving the items
+// eligible before it; 0: none) released the prefix departing before T_enq.  The old ring's part of
+// it is known before HTB runs: the kept old entries stay where they are in HBM, only the head moves.
+struct OldRing {
+  bool stop;      // the release stopped inside the old ring (or nothing was released)
+  uint32_t kept;  // old entries still in the ring
+  uint32_t head;  // the ring's head slot after the release
+};
+__device__ __forceinline__ OldRing release_old_ring(const uint64_t (&rg)[kSparseQ], uint32_t rn, uint32_t rh0,
+                                                    uint64_t T_enq, uint32_t lane) {
+  bool stop = T_enq == 0;
+  uint32_t k0 = 0;
+  if (T_enq) {
+#pragma unroll
+    for (uint32_t u = 0; u < kSparseQ; ++u) {
+      if (!stop && u * kWave < rn) {
+        const uint64_t m = __ballot(u * kWave + lane < rn && rg[u] >= T_enq);
+        const uint32_t cnt = rn - u * kWave < kWave ? rn - u * kWave : kWave;
+        if (m) {
+          k0 += (uint32_t)__builtin_ctzll(m);
+          stop = true;
+        } else {
+          k0 += cnt;
+        }
+      }
+    }
+  }
+  return {stop, rn - k0, (rh0 + k0) & (kHeapCap - 1)};
+}
+
+// A source's served items so far, over its rounds of 64 lanes.
+struct Served {
+  uint64_t tat;        // HTB's TAT after them
+  uint64_t bytes;      // per lane: bytes of the lane's records
+  uint32_t emitted;    // records in the source's emit region and pool (the others: destination buckets)
+  uint32_t sched, cor, lost;  // records written, the corrupted among them, items to dead destinations
+  uint32_t sk0;        // the served entries released with the old ring (a prefix)
+  bool releasing;      // ... which may still grow: every one so far departed before the last enqueue
+};
+__device__ __forceinline__ Served serve_begin(const SrcState& st, const OldRing& ring, uint64_t T_enq) {
+  return {st.tat, 0, 0, 0, 0, 0, 0, T_enq && !ring.stop};
+}
+// One round: lanes [0, ns) hold the served items base .. base + ns - 1 in key order (x).  HTB as one
+// max-plus scan (d = max(e, TAT before), TAT' = max(TAT, e - burst) + cost), then the records (dead
+// destinations leave the sender and are lost) with the receipts folded in, then the departures
+// appended to the ring behind the old entries kept, less the prefix released with the old ring.
+// kStamp: sparse_source's phase stamp behind the scan.
+template <bool kStamp>
+__device__ __forceinline__ void serve_round(const SimArgs& a, const SrcParams& pp, const EmitOut& eo, uint32_t s,
+                                            uint32_t src, uint64_t* wr, const OldRing& ring, uint64_t T_enq,
+                                            const uint4& x, uint32_t ns, uint32_t base, uint32_t lane, uint64_t below,
+                                            Served& sv) {
+  const bool hs = lane < ns;
+  // the destinations' forwarded masks, for the receipts (in flight during the scan; the 32-bit half
+  // that holds the record's flood bit: one register across the scan)
+  const uint32_t fw_f = a.g_first ? x.z / a.g_degree : 0u;
+  const uint32_t fw = a.g_first && hs && x.w - a.shard_begin < a.n_src && fw_f < 64u
+                          ? reinterpret_cast<const uint32_t*>(a.g_fwd)[2ull * (x.w - a.shard_begin) + (fw_f >> 5)]
+                          : 0u;
+  const uint64_t e = w0_of(x) & kEMask;
+  const uint32_t xlen = x.y >> 14 & 0xFFFFu;
+  const uint64_t c = ((uint64_t)xlen * pp.mult) >> (pp.shift_ext & 0xFFu);
+  uint64_t A = hs ? c : 0, Bm = hs ? (e > pp.burst_ns ? e - pp.burst_ns : 0) + c : 0;
+  scan_maxplus(A, Bm);
+  const uint64_t ta = sv.tat + A;
+  const uint64_t tat_after = ta > Bm ? ta : Bm;
+  const uint64_t before = shr1_u64(tat_after, sv.tat);
+  const uint64_t d = e > before ? e : before;
+  if (ns) sv.tat = readlane64(tat_after, ns - 1);
+  if constexpr (kStamp) stamp(a, s, lane, 3, __builtin_amdgcn_s_memrealtime());
+  bool live = hs && x.w != kDeadDst;
+  const bool dead = hs && !live;
+  live = emit_record(a, eo, live, x, d, xlen, src, fw, fw_f, sv.emitted, below);
+  if (live) sv.bytes += xlen;
+  sv.sched += ballot_count(live);
+  sv.cor += ballot_count(live && (x.y >> 31));
+  sv.lost += ballot_count(dead);
+  if (sv.releasing) {
+    const uint32_t n1 = ballot_count(hs && e < T_enq);
+    const uint64_t m = __ballot(lane < n1 && d >= T_enq);
+    if (m) {
+      sv.sk0 = base + (uint32_t)__builtin_ctzll(m);
+      sv.releasing = false;
+    } else {
+      sv.sk0 = base + n1;
+      sv.releasing = n1 == kWave;
+    }
+  }
+  if (hs && base + lane >= sv.sk0) wr[(ring.head + ring.kept + base + lane - sv.sk0) & (kHeapCap - 1)] = d;
+}
+
+// Adds a round's verdict bytes to the counts: lane v < 8 of vcnt holds the packets and clones with
+// verdict v.
+__device__ __forceinline__ void tally_verdicts(bool staged, uint32_t vout, uint32_t lane, uint32_t& vcnt,
+                                               uint32_t& t_clone) {
+  const uint32_t vo = vout & 15u, vc = vout >> 4;
+#pragma unroll
+  for (uint32_t v = 0; v < 8; ++v) {
+    const uint32_t t = ballot_count(staged && vo == v) + ballot_count(staged && vc == v);
+    if (lane == v) vcnt += t;
+  }
+  t_clone += ballot_count(staged && vc != TGSIM_V_NONE);
+}
+
+// The end of a served source: the state (wpos items left queued, near_n as SrcState packs it, ns_all
+// items served) and the statistics.  The per-window queue model counts the whole queue and ring
+// loaded and stored; q_kept is what of that the source left where it was.
+__device__ __forceinline__ void finish_source(const SimArgs& a, uint32_t s, const SrcState& st, const Served& sv,
+                                              const OldRing& ring, uint32_t ns_all, uint32_t wpos, uint32_t near_n,
+                                              uint64_t q_kept, uint32_t n, uint32_t vcnt, uint32_t t_clone,
+                                              uint32_t perr, unsigned long long* sc, uint32_t lane) {
+  const uint32_t rn_new = ring.kept + ns_all - sv.sk0;
+  if (lane == 0) {
+    SrcState ns_;
+    ns_.tat = sv.tat;
+    ns_.heap_n = q_pack(wpos, 0);
+    ns_.near_n = near_n;
+    ns_.ring_n = r_pack(rn_new, ring.head);
+    ns_.last_dup = st.last_dup;
+    ns_.last_cor = st.last_cor;
+    ns_.last_reo = st.last_reo;
+    a.state[s] = ns_;
+    a.emit_n[s] = sv.emitted;
+  }
+  const uint64_t t_bytes = wave_sum(sv.bytes);
+  const bool err = __ballot(perr != 0) != 0;
+  if (lane < 8 && vcnt) atomicAdd(&sc[kStVerdict0 + lane], (unsigned long long)vcnt);
+  if (lane == 0) {
+    const uint64_t qb = 16ull * q_len(st) + 8ull * r_len(st) + 16ull * wpos + 8ull * rn_new;
+    if (q_kept) atomicAdd(&sc[kStCarrySkip], (unsigned long long)q_kept);
+    if (n) atomicAdd(&sc[kStOffered], (unsigned long long)n);
+    if (sv.sched) atomicAdd(&sc[kStScheduled], (unsigned long long)sv.sched);
+    if (a.dst_bkt && sv.sched > sv.emitted) atomicAdd(&sc[kStBktRecs], (unsigned long long)(sv.sched - sv.emitted));
+    if (t_clone) atomicAdd(&sc[kStCloned], (unsigned long long)t_clone);
+    if (sv.cor) atomicAdd(&sc[kStCorrupted], (unsigned long long)sv.cor);
+    if (sv.lost) atomicAdd(&sc[kStLost], (unsigned long long)sv.lost);
+    if (t_bytes) atomicAdd(&sc[kStBytes], (unsigned long long)t_bytes);
+    if (qb) atomicAdd(&sc[kStQueue], (unsigned long long)qb);
+    if (err) raise_error(a, kErrTimeOverflow);
+  }
+}
+
 // k_sim_multi: the FIFO sources k_sim_sparse cannot take in one round of lanes -- more than 64
-// offered packets, or more than kFifoRounds x 64 items to serve (the gossip flood's peak).  The same
-// FIFO path as sparse_source (the stored queue is one sorted region, the new items extend it in
-// order, so HTB serves the prefix below the horizon in that order and the rest stays in place), with
-// the candidates written straight behind the queue's tail in offer order: any number of rounds of 64
-// offered packets and of served items run in one wave, at a register-only cost per round, and no
-// LDS (the wave count per SIMD is set by the registers).  The served prefix (the queue's due items,
-// then the due candidates) leaves by moving the head slot.  A source that turns out not to be FIFO
-// (a clone that is queued, a new item before its predecessor) goes on to the general worklist
-// (k_sim_list), which reads only the stored queue: the slots behind its tail are free space.  One wave
-// per source, a grid-stride loop over the list k_sim_sparse wrote.
+// offered packets, or more than kFifoRounds x 64 items to serve (the gossip flood's peak).
+// sparse_source's FIFO path with the candidates written straight behind the queue's tail in offer
+// order: any number of rounds of 64 offered packets and of served items run in one wave, at a
+// register-only cost per round, and no LDS (the wave count per SIMD is set by the registers).  The
+// served prefix (the queue's due items, then the due candidates) leaves by moving the head slot.  A
+// source that turns out not to be FIFO (a clone that is queued, a new item before its predecessor)
+// goes on to k_sim_list, which reads only the stored queue: the slots behind its tail are free
+// space.  One wave per source, a grid-stride loop over the list k_sim_sparse wrote.
 __device__ __forceinline__ void multi_source(const SimArgs& a, const uint32_t s) {
   const uint32_t lane = threadIdx.x;
   const uint64_t below = (1ull << lane) - 1;
@@ -1958,14 +2186,11 @@ __device__ __forceinline__ void multi_source(const SimArgs& a, const uint32_t s)
   const uint64_t sbeg = a.off[s], send = a.off[s + 1];
   const uint32_t n = (uint32_t)(send - sbeg);
   const uint32_t rn = r_len(st), qn = q_len(st), rh0 = r_head(st);
-  auto defer = [&]() {
-    if (lane == 0) a.worklist[atomicAdd(a.worklist - 4, 1u)] = s;
-  };
   // (k_sim_sparse checked the rest: no correlated draws, below the netem limit even if every offered
   // packet and a clone were queued -- so the candidates fit behind the tail, qn + n < kHeapCap --, at
   // most 256 ring entries, one sorted queue region)
   if (qn + n >= kHeapCap) {
-    defer();
+    defer_to_list(a, s, lane);
     return;
   }
   uint4* const wq = a.heap + (size_t)s * kHeapCap;
@@ -1994,53 +2219,13 @@ __device__ __forceinline__ void multi_source(const SimArgs& a, const uint32_t s)
     InRec r = {};
     if (staged) r = a.in[sbeg + base + lane];
     const uint64_t T = a.t0_ns + (uint64_t)r.tick * a.tick_ns;
-    const uint32_t len = r.len & 0xFFFFu;
-    uint32_t fv = 0u;
-    if (staged) fv = plain ? (r.dst == TGSIM_EXTERNAL ? ext_v : kFvPass) : filter(a, pp, src_on, r.dst);
-    uint32_t vout = 0xF0u | fv;
-    bool cand = false, queued_clone = false;
-    uint4 io = make_uint4(0, 0, 0, 0);
-    if (staged && fv == kFvPass) {
-      uint32_t r0[4];
-      philox(src, r.dst, r.seq, 0, a.key0, a.key1, r0);
-      const int count = 1 + (pp.thr_dup && pp.thr_dup >= r0[0]) - (pp.thr_loss && pp.thr_loss >= r0[1]);
-      if (count == 0) {
-        vout = 0xF0u | TGSIM_V_LOSS;
-      } else {
-        cand = true;
-        uint32_t cv = TGSIM_V_NONE;
-        if (count == 2) {  // the clone: lost before the queue keeps the source FIFO, queued does not
-          uint32_t r2[4];
-          philox(src, r.dst, r.seq, 2, a.key0, a.key1, r2);
-          if (pp.thr_loss && pp.thr_loss >= r2[0]) cv = TGSIM_V_LOSS;
-          else queued_clone = true;
-        }
-        const uint32_t flo = (pp.thr_cor && pp.thr_cor >= r0[2]) ? TGSIM_FLAG_CORRUPT : 0u;
-        const bool reo_o = pp.thr_reo && pp.thr_reo >= r0[3];
-        uint64_t eo = reo_o ? T : T + pp.lat_ns;
-        if (!reo_o && pp.sigma != 0) {
-          uint32_t r1[4];
-          philox(src, r.dst, r.seq, 1, a.key0, a.key1, r1);
-          eo = delayed(pp, T, r1[0]);
-        }
-        if (eo > kEMask) { perr = 1; eo = kEMask; }
-        io = make_item(eo, len, flo, r.seq, r.dst);
-        vout = (cv << 4) | TGSIM_V_SCHEDULED;
-      }
-    }
-    if (__ballot(queued_clone)) fifo = false;
+    const auto [vout, cand, cst, io, ic] = netem_decide<false>(a, pp, src, src_on, plain, ext_v, staged, r, T, perr);
+    // a clone lost before the queue keeps the source FIFO, a queued one does not
+    if (__ballot(cst == 2)) fifo = false;
     const uint64_t mc = __ballot(cand);
-    // FIFO: no candidate before its predecessor (the candidate before it, or the last item so far)
-    const uint64_t bc = mc & below;
-    const uint32_t pl = bc ? 63u - (uint32_t)__builtin_clzll(bc) : lane;
-    TG_FULL_EXEC("ds_permute");
-    uint4 prev = make_uint4((uint32_t)__builtin_amdgcn_ds_bpermute((int)(pl << 2), (int)io.x),
-                            (uint32_t)__builtin_amdgcn_ds_bpermute((int)(pl << 2), (int)io.y),
-                            (uint32_t)__builtin_amdgcn_ds_bpermute((int)(pl << 2), (int)io.z), 0u);
-    if (!bc) prev = last;
-    if (__ballot(cand && (bc || has_last) && item_lt(io, prev))) fifo = false;
-    if (cand) wq[(qh + qn + nc + (uint32_t)__popcll(bc)) & (kHeapCap - 1)] = io;
-    n_due += (uint32_t)__popcll(__ballot(cand && (w0_of(io) & kEMask) < h));
+    if (!fifo_round(cand, io, mc, last, has_last, lane, below)) fifo = false;
+    if (cand) wq[(qh + qn + nc + (uint32_t)__popcll(mc & below)) & (kHeapCap - 1)] = io;
+    n_due += ballot_count(cand && (w0_of(io) & kEMask) < h);
     if (mc) {
       const uint32_t ll = 63u - (uint32_t)__builtin_clzll(mc);
       last = make_uint4(readlane32(io.x, ll), readlane32(io.y, ll), readlane32(io.z, ll), 0u);
@@ -2049,16 +2234,10 @@ __device__ __forceinline__ void multi_source(const SimArgs& a, const uint32_t s)
     }
     nc += (uint32_t)__popcll(mc);
     if (staged) a.verdict[sbeg + base + lane] = (uint8_t)vout;  // rewritten by k_sim_list if deferred
-    const uint32_t vo = vout & 15u, vc = vout >> 4;
-#pragma unroll
-    for (uint32_t v = 0; v < 8; ++v) {
-      const uint32_t t = ballot_count(staged && vo == v) + ballot_count(staged && vc == v);
-      if (lane == v) vcnt += t;
-    }
-    t_clone += ballot_count(staged && vc != TGSIM_V_NONE);
+    tally_verdicts(staged, vout, lane, vcnt, t_clone);
   }
   if (!fifo) {
-    defer();
+    defer_to_list(a, s, lane);
     return;
   }
   // the candidates' stores complete before the serving rounds read the due ones back (other lanes'
@@ -2071,131 +2250,36 @@ __device__ __forceinline__ void multi_source(const SimArgs& a, const uint32_t s)
     for (uint32_t c = 0; c * kWave < qn; ++c) {
       const uint32_t k = c * kWave + lane;
       const uint4 v = k < qn ? gh[(qh + k) & (kHeapCap - 1)] : make_uint4(0, 0, 0, 0);
-      const uint32_t d = (uint32_t)__popcll(__ballot(k < qn && (w0_of(v) & kEMask) < h));
+      const uint32_t d = ballot_count(k < qn && (w0_of(v) & kEMask) < h);
       nq += d;
       if (d < kWave) break;
     }
   }
-  // ---- the old ring: the prefix departing before the last enqueue is released (as in sparse_source)
   uint64_t* wr = a.ring + (size_t)s * kHeapCap;
-  bool ring_stop = T_enq == 0;
-  uint32_t k0 = 0;
-  if (T_enq) {
-#pragma unroll
-    for (uint32_t u = 0; u < kSparseQ; ++u) {
-      if (!ring_stop && u * kWave < rn) {
-        const uint64_t m = __ballot(u * kWave + lane < rn && rg[u] >= T_enq);
-        const uint32_t cnt = rn - u * kWave < kWave ? rn - u * kWave : kWave;
-        if (m) {
-          k0 += (uint32_t)__builtin_ctzll(m);
-          ring_stop = true;
-        } else {
-          k0 += cnt;
-        }
-      }
-    }
-  }
-  // the kept old entries stay where they are in HBM: the head moves past the released ones
-  const uint32_t old_kept = rn - k0, rh1 = (rh0 + k0) & (kHeapCap - 1);
-  // ---- in place: the served prefix (a due candidate means the whole queue is due) leaves by moving
-  // the head slot; the candidates not served are already behind the tail
+  const OldRing ring = release_old_ring(rg, rn, rh0, T_enq, lane);
+  // ---- in place: the served prefix leaves by moving the head slot; the candidates not served are
+  // already behind the tail
   const uint32_t new_head = (qh + nq + n_due) & (kHeapCap - 1);
   const uint32_t wpos = qn - nq + nc - n_due;
   const uint32_t ns_all = nq + n_due;
-  // ---- HTB, records, receipts and the ring, for the served items in rounds of 64 lanes: the
-  // queue's due items, then the due candidates, contiguous from the head slot
-  uint64_t tat_c = st.tat;
-  uint32_t emitted = 0, sched_n = 0, sk0 = 0, t_cor = 0, t_lost = 0;
-  uint64_t bytes = 0;
-  bool releasing = T_enq && !ring_stop;
+  // ---- the served items, contiguous from the head slot: the queue's due items, then the due candidates
+  Served sv = serve_begin(st, ring, T_enq);
   EmitOut eo = emit_out(a, s, sbeg, send);
   emit_claim(a, s, eo, ns_all, lane);
   for (uint32_t base = 0; base < ns_all; base += kWave) {
-    const uint32_t k = base + lane;
     const uint32_t ns = ns_all - base < kWave ? ns_all - base : kWave;
-    const bool hs = lane < ns;
-    const uint4 x = hs ? gh[(qh + k) & (kHeapCap - 1)] : make_uint4(0, 0, 0, 0);
-    const uint32_t fw_f = a.g_first ? x.z / a.g_degree : 0u;
-    const uint32_t fw = a.g_first && hs && x.w - a.shard_begin < a.n_src && fw_f < 64u
-                            ? reinterpret_cast<const uint32_t*>(a.g_fwd)[2ull * (x.w - a.shard_begin) + (fw_f >> 5)]
-                            : 0u;
-    const uint64_t e = w0_of(x) & kEMask;
-    const uint32_t xlen = x.y >> 14 & 0xFFFFu;
-    const uint64_t c = ((uint64_t)xlen * pp.mult) >> (pp.shift_ext & 0xFFu);
-    uint64_t A = hs ? c : 0, Bm = hs ? (e > pp.burst_ns ? e - pp.burst_ns : 0) + c : 0;
-    scan_maxplus(A, Bm);
-    const uint64_t ta = tat_c + A;
-    const uint64_t tat_after = ta > Bm ? ta : Bm;
-    const uint64_t before = shr1_u64(tat_after, tat_c);
-    const uint64_t d = e > before ? e : before;
-    tat_c = readlane64(tat_after, ns - 1);
-    bool live = hs && x.w != kDeadDst;
-    const bool dead = hs && !live;
-    live = emit_record(a, eo, live, x, d, xlen, src, fw, fw_f, emitted, below);
-    if (live) bytes += xlen;
-    sched_n += (uint32_t)__popcll(__ballot(live));
-    t_cor += (uint32_t)__popcll(__ballot(live && (x.y >> 31)));
-    t_lost += (uint32_t)__popcll(__ballot(dead));
-    if (releasing) {  // a prefix of the served entries departed before the last enqueue
-      const uint32_t n1 = (uint32_t)__popcll(__ballot(hs && e < T_enq));
-      const uint64_t m = __ballot(lane < n1 && d >= T_enq);
-      if (m) {
-        sk0 = base + (uint32_t)__builtin_ctzll(m);
-        releasing = false;
-      } else {
-        sk0 = base + n1;
-        releasing = n1 == kWave;
-      }
-    }
-    if (hs && k >= sk0) wr[(rh1 + old_kept + k - sk0) & (kHeapCap - 1)] = d;
+    const uint4 x = lane < ns ? gh[(qh + base + lane) & (kHeapCap - 1)] : make_uint4(0, 0, 0, 0);
+    serve_round<false>(a, pp, eo, s, src, wr, ring, T_enq, x, ns, base, lane, below, sv);
   }
-  const uint32_t rn_new = old_kept + ns_all - sk0;
-  if (lane == 0) {
-    SrcState ns_;
-    ns_.tat = tat_c;
-    ns_.heap_n = q_pack(wpos, 0);
-    ns_.near_n = wpos | new_head << 16;  // sorted in place
-    ns_.ring_n = r_pack(rn_new, rh1);
-    ns_.last_dup = st.last_dup;
-    ns_.last_cor = st.last_cor;
-    ns_.last_reo = st.last_reo;
-    a.state[s] = ns_;
-    a.emit_n[s] = emitted;
-  }
-  // ---- statistics
-  const uint64_t t_bytes = wave_sum(bytes);
-  const bool err = __ballot(perr != 0) != 0;
-  if (lane < 8 && vcnt) atomicAdd(&sc[kStVerdict0 + lane], (unsigned long long)vcnt);
-  if (lane == 0) {
-    const uint64_t qb = 16ull * qn + 8ull * rn + 16ull * wpos + 8ull * rn_new;
-    // HBM items of the queue this step touched: the due prefix read, the tail item, the appended ones
-    const uint32_t q_moved = nq + (qn ? 1u : 0u) + nc - n_due;
-    const uint64_t q_kept = (qn + wpos > q_moved ? 16ull * (qn + wpos - q_moved) : 0ull) + 8ull * old_kept;
-    if (q_kept) atomicAdd(&sc[kStCarrySkip], (unsigned long long)q_kept);
-    if (n) atomicAdd(&sc[kStOffered], (unsigned long long)n);
-    if (sched_n) atomicAdd(&sc[kStScheduled], (unsigned long long)sched_n);
-    if (a.dst_bkt && sched_n > emitted) atomicAdd(&sc[kStBktRecs], (unsigned long long)(sched_n - emitted));
-    if (t_clone) atomicAdd(&sc[kStCloned], (unsigned long long)t_clone);
-    if (t_cor) atomicAdd(&sc[kStCorrupted], (unsigned long long)t_cor);
-    if (t_lost) atomicAdd(&sc[kStLost], (unsigned long long)t_lost);
-    if (t_bytes) atomicAdd(&sc[kStBytes], (unsigned long long)t_bytes);
-    if (qb) atomicAdd(&sc[kStQueue], (unsigned long long)qb);
-    if (err) {
-      atomicOr(&a.stats[kStErr], (unsigned long long)kErrTimeOverflow);
-      if (a.err_host)
-        __hip_atomic_store(a.err_host, (uint64_t)kErrTimeOverflow, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-  }
+  // HBM items of the queue this step touched: the due prefix read, the tail item, the appended ones
+  const uint32_t q_moved = nq + (qn ? 1u : 0u) + nc - n_due;
+  const uint64_t q_kept = (qn + wpos > q_moved ? 16ull * (qn + wpos - q_moved) : 0ull) + 8ull * ring.kept;
+  finish_source(a, s, st, sv, ring, ns_all, wpos, wpos | new_head << 16, q_kept, n, vcnt, t_clone, perr, sc, lane);
 }
 
-// The multi-round list k_sim_sparse writes: its count is the word after the worklist's count (one
-// memset clears both), its sources follow the worklist's statistics words.
-__device__ __forceinline__ uint32_t* multi_count(const SimArgs& a) { return a.worklist - 3; }
-__device__ __forceinline__ uint32_t* multi_list(const SimArgs& a) { return a.worklist + a.n_src + 8; }
-
 __global__ __launch_bounds__(kWave) void k_sim_multi(SimArgs a) {
-  const uint32_t* const list = multi_list(a);
-  const uint32_t n = *multi_count(a);
+  const uint32_t* const list = a.work.multi(a.n_src);
+  const uint32_t n = *a.work.multi_n();
   for (uint32_t i = blockIdx.x; i < n; i += gridDim.x) multi_source(a, list[i]);
 }
 
@@ -2210,7 +2294,7 @@ __global__ __launch_bounds__(kWave) void k_sim_multi(SimArgs a) {
 // queued items, 256 ring entries or 64 items to serve) writes nothing and goes to the worklist.
 // (FIFO sources with more than one round of lanes go to k_sim_multi above instead.)
 __device__ __forceinline__ void sparse_source(const SimArgs& a, const uint32_t s) {
-  const uint32_t lane = threadIdx.x & (kWave - 1);
+  const uint32_t lane = threadIdx.x;
   const uint64_t below = (1ull << lane) - 1;
   stamp(a, s, lane, 0, __builtin_amdgcn_s_memrealtime());
   // the queue starts at its head slot; the ring (needed only after the netem decisions) is read with
@@ -2221,21 +2305,15 @@ __device__ __forceinline__ void sparse_source(const SimArgs& a, const uint32_t s
   const uint64_t sbeg = a.off[s], send = a.off[s + 1];
   const uint32_t n = (uint32_t)(send - sbeg);
   const uint32_t rn = r_len(st), qn = q_len(st), rh0 = r_head(st);
-  auto defer = [&](uint32_t why) {
-    if (lane == 0) a.worklist[atomicAdd(a.worklist - 4, 1u)] = s;
-    (void)why;
-  };
   if (q_parked(st)) {  // far items parked in the timing wheel: the general path reads them
-    defer(5u);
+    defer_to_list(a, s, lane);
     return;
   }
   const bool sorted_st = q_near(st) == qn;  // the whole queue is one sorted region
   // FIFO candidates beyond one round of lanes go to k_sim_multi (multi-round, candidates written behind
   // the queue tail in HBM)
   auto defer_multi = [&]() {
-    if (lane == 0) {
-      multi_list(a)[atomicAdd(multi_count(a), 1u)] = s;
-    }
+    if (lane == 0) a.work.multi(a.n_src)[atomicAdd(a.work.multi_n(), 1u)] = s;
   };
   unsigned long long* const sc = a.stats + (size_t)(s % kStatCopies) * kStSlots;
   const uint4 qh0 = sorted_st && qn && !n ? gh[q_head(st)] : make_uint4(0, 0, 0, 0);
@@ -2257,10 +2335,11 @@ __device__ __forceinline__ void sparse_source(const SimArgs& a, const uint32_t s
   const SrcParams pp = a.params[s];
   if ((pp.rho_dup | pp.rho_cor | pp.rho_reo) != 0 || (uint64_t)rn + qn + 2ull * n >= a.queue_limit || n > kWave ||
       (!sorted_st && qn > kSparseQ * kWave) || rn > kSparseQ * kWave) {
-    const uint32_t why = (pp.rho_dup | pp.rho_cor | pp.rho_reo) != 0 ? 0u : (uint64_t)rn + qn + 2ull * n >= a.queue_limit ? 1u
-                         : n > kWave ? 2u : rn > kSparseQ * kWave ? 4u : 3u;
-    if (why == 2u && sorted_st && rn <= kSparseQ * kWave) defer_multi();
-    else defer(why);
+    // more offered packets than one round of lanes and nothing else in the way: k_sim_multi's
+    const bool general = (pp.rho_dup | pp.rho_cor | pp.rho_reo) != 0 || (uint64_t)rn + qn + 2ull * n >= a.queue_limit ||
+                         rn > kSparseQ * kWave;
+    if (!general && n > kWave && sorted_st) defer_multi();
+    else defer_to_list(a, s, lane);
     return;
   }
   const uint32_t src = a.shard_begin + s;
@@ -2296,53 +2375,11 @@ __device__ __forceinline__ void sparse_source(const SimArgs& a, const uint32_t s
   const bool staged = lane < n;
   if (staged) r = a.in[sbeg + lane];
   const uint64_t T = a.t0_ns + (uint64_t)r.tick * a.tick_ns;
-  const uint32_t len = r.len & 0xFFFFu;
-  // ---- filter and netem decisions (queue-independent; every candidate is admitted)
   const bool src_on = a.enabled[src] != 0;
   const bool plain = src_on && !a.any_disabled && pp.rule_n == 0;
   const uint32_t ext_v = (pp.shift_ext >> 8 & 1u) ? TGSIM_V_EXTERNAL : TGSIM_V_NO_ROUTE;
-  uint32_t fv = 0u;
-  if (staged) fv = plain ? (r.dst == TGSIM_EXTERNAL ? ext_v : kFvPass) : filter(a, pp, src_on, r.dst);
-  uint32_t vout = 0xF0u | fv;
-  bool cand = false;
-  uint32_t cst = 0, perr = 0;
-  uint4 io = make_uint4(0, 0, 0, 0), ic = make_uint4(0, 0, 0, 0);
-  if (staged && fv == kFvPass) {
-    uint32_t r0[4];
-    philox(src, r.dst, r.seq, 0, a.key0, a.key1, r0);
-    const int count = 1 + (pp.thr_dup && pp.thr_dup >= r0[0]) - (pp.thr_loss && pp.thr_loss >= r0[1]);
-    if (count == 0) {
-      vout = 0xF0u | TGSIM_V_LOSS;
-    } else {
-      cand = true;
-      if (count == 2) {
-        uint32_t r2[4];
-        philox(src, r.dst, r.seq, 2, a.key0, a.key1, r2);
-        if (pp.thr_loss && pp.thr_loss >= r2[0]) {
-          cst = 1;
-        } else {
-          cst = 2;
-          uint32_t flc = TGSIM_FLAG_DUP;
-          if (pp.thr_cor && pp.thr_cor >= r2[1]) flc |= TGSIM_FLAG_CORRUPT;
-          uint64_t ec = (pp.thr_reo && pp.thr_reo >= r2[2]) ? T : delayed(pp, T, r2[3]);
-          if (ec > kEMask) { perr = 1; ec = kEMask; }
-          ic = make_item(ec, len, flc, r.seq, r.dst);
-        }
-      }
-      const uint32_t flo = (pp.thr_cor && pp.thr_cor >= r0[2]) ? TGSIM_FLAG_CORRUPT : 0u;
-      const bool reo_o = pp.thr_reo && pp.thr_reo >= r0[3];
-      uint64_t eo = reo_o ? T : T + pp.lat_ns;
-      if (!reo_o && pp.sigma != 0) {
-        uint32_t r1[4];
-        philox(src, r.dst, r.seq, 1, a.key0, a.key1, r1);
-        eo = delayed(pp, T, r1[0]);
-      }
-      if (eo > kEMask) { perr = 1; eo = kEMask; }
-      io = make_item(eo, len, flo, r.seq, r.dst);
-      const uint32_t cv = cst == 0 ? TGSIM_V_NONE : cst == 1 ? TGSIM_V_LOSS : TGSIM_V_SCHEDULED;
-      vout = (cv << 4) | TGSIM_V_SCHEDULED;
-    }
-  }
+  uint32_t perr = 0;
+  const auto [vout, cand, cst, io, ic] = netem_decide<true>(a, pp, src, src_on, plain, ext_v, staged, r, T, perr);
   const uint64_t mc = __ballot(cand);
   const uint64_t T_enq = mc ? readlane64(T, 63u - (uint32_t)__builtin_clzll(mc)) : 0ull;
   stamp(a, s, lane, 2, __builtin_amdgcn_s_memrealtime());
@@ -2369,58 +2406,21 @@ __device__ __forceinline__ void sparse_source(const SimArgs& a, const uint32_t s
     ns += k;
   };
   uint4* wq = a.heap + (size_t)s * kHeapCap;
-  uint32_t wpos = 0;
-  // The departure ring: old ring ++ served.  The last enqueue (at T_enq, after serving the items
-  // eligible before it) released the prefix departing before T_enq; the old ring's part of it is
-  // known before HTB runs, so the kept old entries are written back (and their registers freed) as
-  // soon as the source is known not to defer.
   uint64_t* wr = a.ring + (size_t)s * kHeapCap;
-  uint32_t old_kept = rn;     // old entries still in the ring
-  uint32_t rh1 = rh0;         // the ring's head slot after the release
-  bool ring_stop = T_enq == 0;  // the release stopped inside the old ring (or nothing was released)
-  auto write_old_ring = [&]() {  // (the kept old entries stay in place in HBM: only the head moves)
-    uint32_t k0 = 0;
-    if (T_enq) {
-#pragma unroll
-      for (uint32_t u = 0; u < kSparseQ; ++u) {
-        if (!ring_stop && u * kWave < rn) {
-          const uint64_t m = __ballot(u * kWave + lane < rn && rg[u] >= T_enq);
-          const uint32_t cnt = rn - u * kWave < kWave ? rn - u * kWave : kWave;
-          if (m) {
-            k0 += (uint32_t)__builtin_ctzll(m);
-            ring_stop = true;
-          } else {
-            k0 += cnt;
-          }
-        }
-      }
-    }
-    old_kept = rn - k0;
-    rh1 = (rh0 + k0) & (kHeapCap - 1);
-  };
+  uint32_t wpos = 0;
+  // the old ring's release runs (and frees its registers) as soon as the source is known not to defer
+  OldRing ring = {};
   // ---- FIFO sources (no jitter, no reordering, no duplicates: gossip): the stored queue is sorted
   // (a whole near region) and the new items, in offer order, are sorted and not before its last
   // item, so (queue ++ new) is sorted: HTB serves its prefix below the horizon, in that order, and
   // the rest goes back sorted, shifted down, with no gather of the queue, no rank and no compaction.
   bool fifo = sorted_st && __ballot(cand && cst == 2) == 0;
   if (fifo && mc) {
-    const uint64_t bc = mc & below;  // the candidate before each candidate, or the queue's last item
-    const uint32_t pl = bc ? 63u - (uint32_t)__builtin_clzll(bc) : lane;
-    TG_FULL_EXEC("ds_permute");
-    uint4 prev = make_uint4((uint32_t)__builtin_amdgcn_ds_bpermute((int)(pl << 2), (int)io.x),
-                            (uint32_t)__builtin_amdgcn_ds_bpermute((int)(pl << 2), (int)io.y),
-                            (uint32_t)__builtin_amdgcn_ds_bpermute((int)(pl << 2), (int)io.z), 0u);
-    bool first = cand && !bc;
-    if (qn) {
-      if (qn <= kWave) {
-        const uint32_t tl = qn - 1;
-        qt = make_uint4(readlane32(q[0].x, tl), readlane32(q[0].y, tl), readlane32(q[0].z, tl), 0u);
-      }
-      if (first) prev = qt;
-    } else {
-      first = false;  // nothing queued: the first candidate has no predecessor
+    if (qn && qn <= kWave) {
+      const uint32_t tl = qn - 1;
+      qt = make_uint4(readlane32(q[0].x, tl), readlane32(q[0].y, tl), readlane32(q[0].z, tl), 0u);
     }
-    fifo = __ballot(cand && (bc || first) && item_lt(io, prev)) == 0;
+    fifo = fifo_round(cand, io, mc, qt, qn != 0, lane, below);
   }
   uint32_t new_head = 0;
   uint32_t q_moved = 0;  // queue items read or written in HBM (FIFO path: not the whole queue)
@@ -2429,11 +2429,11 @@ __device__ __forceinline__ void sparse_source(const SimArgs& a, const uint32_t s
   if (fifo) {
     // the queue's prefix below the horizon: its first chunk, and while a chunk is due entirely the
     // next one (the served items run in rounds of 64 below, at most kFifoRounds)
-    uint32_t nq = (uint32_t)__popcll(__ballot(lane < qn && (w0_of(q[0]) & kEMask) < h));
+    uint32_t nq = ballot_count(lane < qn && (w0_of(q[0]) & kEMask) < h);
     for (uint32_t c = 1; c < kFifoRounds && nq == c * kWave && qn > nq; ++c) {
       const uint32_t k = c * kWave + lane;
       const uint4 v = k < qn ? gh[(qh + k) & (kHeapCap - 1)] : make_uint4(0, 0, 0, 0);
-      nq += (uint32_t)__popcll(__ballot(k < qn && (w0_of(v) & kEMask) < h));
+      nq += ballot_count(k < qn && (w0_of(v) & kEMask) < h);
     }
     const bool due_o = cand && (w0_of(io) & kEMask) < h;  // a prefix of the candidates
     const uint64_t dm = __ballot(due_o);
@@ -2442,7 +2442,7 @@ __device__ __forceinline__ void sparse_source(const SimArgs& a, const uint32_t s
       defer_multi();
       return;
     }
-    write_old_ring();
+    ring = release_old_ring(rg, rn, rh0, T_enq, lane);
     fifo_nq = nq;
     ns_all = nq + n_due;
     due_f = due_o;
@@ -2461,7 +2461,7 @@ __device__ __forceinline__ void sparse_source(const SimArgs& a, const uint32_t s
   } else {
     if (sorted_st) {  // sorted, but the new items do not extend it in order: the general path
       if (qn > kSparseQ * kWave) {
-        defer(6u);
+        defer_to_list(a, s, lane);
         return;
       }
       load_rest();
@@ -2477,12 +2477,12 @@ __device__ __forceinline__ void sparse_source(const SimArgs& a, const uint32_t s
     gather(due_o, io);
     gather(due_c, ic);
     // remaining items: everything not served, written back as the pool
-    uint32_t nrem = qn + (uint32_t)__popcll(mc) + (uint32_t)__popcll(__ballot(cand && cst == 2)) - ns;
+    uint32_t nrem = qn + (uint32_t)__popcll(mc) + ballot_count(cand && cst == 2) - ns;
     if (over || nrem > kSparseQ * kWave) {
-      defer(7u);
+      defer_to_list(a, s, lane);
       return;
     }
-    write_old_ring();
+    ring = release_old_ring(rg, rn, rh0, T_enq, lane);
     // ---- write back the items HTB does not serve this step as the pool (no order needed); the
     // registers holding the queue are free for the rest
     auto keep = [&](bool f, const uint4& v) {
@@ -2507,58 +2507,15 @@ __device__ __forceinline__ void sparse_source(const SimArgs& a, const uint32_t s
                    (uint32_t)__builtin_amdgcn_ds_permute((int)(to << 2), (int)x.y),
                    (uint32_t)__builtin_amdgcn_ds_permute((int)(to << 2), (int)x.z),
                    (uint32_t)__builtin_amdgcn_ds_permute((int)(to << 2), (int)x.w));
+    ns_all = ns;
   }
-  if (!fifo) ns_all = ns;
-  // ---- HTB, records, receipts and the ring, for the served items in rounds of 64 lanes (more than
-  // one only on the FIFO path: the queue's due prefix, then the due candidates, in order)
-  uint64_t tat_c = st.tat;
-  uint32_t emitted = 0, sched_n = 0, sk0 = 0, t_sched = 0, t_cor = 0, t_lost = 0;
-  uint64_t bytes = 0;
-  bool releasing = T_enq && !ring_stop;  // served entries departing before the last enqueue are released
+  // ---- the served items in rounds of 64 lanes (more than one only on the FIFO path: the queue's due
+  // prefix, then the due candidates, in order)
+  Served sv = serve_begin(st, ring, T_enq);
   EmitOut eo = emit_out(a, s, sbeg, send);
   emit_claim(a, s, eo, ns_all, lane);
   for (uint32_t base = 0;; base += kWave) {
-    const bool hs = lane < ns;
-    // the destinations' forwarded masks, for the receipts folded in below (in flight during the scan)
-    // (the 32-bit half of the mask that holds the record's flood bit: one register across the scan)
-    const uint32_t fw_f = a.g_first ? x.z / a.g_degree : 0u;
-    const uint32_t fw = a.g_first && hs && x.w - a.shard_begin < a.n_src && fw_f < 64u
-                            ? reinterpret_cast<const uint32_t*>(a.g_fwd)[2ull * (x.w - a.shard_begin) + (fw_f >> 5)]
-                            : 0u;
-    // HTB: d = max(e, TAT before), TAT' = max(TAT, e - burst) + cost, one max-plus scan
-    const uint64_t e = w0_of(x) & kEMask;
-    const uint32_t xlen = x.y >> 14 & 0xFFFFu;
-    const uint64_t c = ((uint64_t)xlen * pp.mult) >> (pp.shift_ext & 0xFFu);
-    uint64_t A = hs ? c : 0, Bm = hs ? (e > pp.burst_ns ? e - pp.burst_ns : 0) + c : 0;
-    scan_maxplus(A, Bm);
-    const uint64_t ta = tat_c + A;
-    const uint64_t tat_after = ta > Bm ? ta : Bm;
-    const uint64_t before = shr1_u64(tat_after, tat_c);
-    const uint64_t d = e > before ? e : before;
-    if (ns) tat_c = readlane64(tat_after, ns - 1);
-    stamp(a, s, lane, 3, __builtin_amdgcn_s_memrealtime());
-    // records of the served items (dead destinations leave the sender and are lost)
-    bool live = hs && x.w != kDeadDst;
-    const bool dead = hs && !live;
-    live = emit_record(a, eo, live, x, d, xlen, src, fw, fw_f, emitted, below);
-    if (live) bytes += xlen;
-    sched_n += (uint32_t)__popcll(__ballot(live));
-    t_cor += (uint32_t)__popcll(__ballot(live && (x.y >> 31)));
-    t_lost += (uint32_t)__popcll(__ballot(dead));
-    // the served entries join the ring, behind the old entries kept; a prefix of them departing
-    // before the last enqueue was released with the old ring (when that released all of it)
-    if (releasing) {
-      const uint32_t n1 = (uint32_t)__popcll(__ballot(hs && e < T_enq));
-      const uint64_t m = __ballot(lane < n1 && d >= T_enq);
-      if (m) {
-        sk0 = base + (uint32_t)__builtin_ctzll(m);
-        releasing = false;
-      } else {
-        sk0 = base + n1;
-        releasing = n1 == kWave;
-      }
-    }
-    if (hs && base + lane >= sk0) wr[(rh1 + old_kept + base + lane - sk0) & (kHeapCap - 1)] = d;
+    serve_round<true>(a, pp, eo, s, src, wr, ring, T_enq, x, ns, base, lane, below, sv);
     if (base + kWave >= ns_all) break;
     // the next round (FIFO): the queue's due items from HBM, then the due candidates
     const uint32_t nb = base + kWave, k = nb + lane;
@@ -2566,89 +2523,46 @@ __device__ __forceinline__ void sparse_source(const SimArgs& a, const uint32_t s
     ns = fifo_nq > nb ? (fifo_nq - nb < kWave ? fifo_nq - nb : kWave) : 0u;
     gather(due_f && cpos >= nb && cpos < nb + kWave, io);
   }
-  t_sched = sched_n;
-  const uint32_t rn_new = old_kept + ns_all - sk0;
-  if (lane == 0) {
-    SrcState ns_;
-    ns_.tat = tat_c;
-    ns_.heap_n = q_pack(wpos, 0);
-    ns_.near_n = fifo ? wpos | new_head << 16 : 0;  // sorted in place (FIFO), or all of it pool, compacted
-    ns_.ring_n = r_pack(rn_new, rh1);
-    ns_.last_dup = st.last_dup;
-    ns_.last_cor = st.last_cor;
-    ns_.last_reo = st.last_reo;
-    a.state[s] = ns_;
-    a.emit_n[s] = emitted;
-  }
   if (staged) a.verdict[sbeg + lane] = (uint8_t)vout;
   stamp(a, s, lane, 4, __builtin_amdgcn_s_memrealtime());
   stamp(a, s, lane, 5, ((uint64_t)s << 32) | n);
   stamp(a, s, lane, 7, ((uint64_t)qn << 32) | rn);
-  // ---- statistics (per-lane counts reduced over the wave)
-  const uint32_t vo = vout & 15u, vc = vout >> 4;
-  uint32_t vcnt = 0;  // lane v < 8: packets and clones with verdict v
-#pragma unroll
-  for (uint32_t v = 0; v < 8; ++v) {
-    const uint32_t t = ballot_count(staged && vo == v) + ballot_count(staged && vc == v);
-    if (lane == v) vcnt = t;
-  }
-  const uint32_t t_clone = ballot_count(staged && vc != TGSIM_V_NONE);
-  const uint64_t t_bytes = wave_sum(bytes);
-  const bool err = __ballot(perr != 0) != 0;
-  if (lane < 8 && vcnt) atomicAdd(&sc[kStVerdict0 + lane], (unsigned long long)vcnt);
-  if (lane == 0) {
-    const uint64_t qb = 16ull * qn + 8ull * rn + 16ull * wpos + 8ull * rn_new;
-    // the per-window model counts the whole queue loaded and stored; the FIFO path left most of it
-    const uint64_t q_kept = (fifo && qn + wpos > q_moved ? 16ull * (qn + wpos - q_moved) : 0ull) + 8ull * old_kept;
-    if (q_kept) atomicAdd(&sc[kStCarrySkip], (unsigned long long)q_kept);
-    if (n) atomicAdd(&sc[kStOffered], (unsigned long long)n);
-    if (t_sched) atomicAdd(&sc[kStScheduled], (unsigned long long)t_sched);
-    if (a.dst_bkt && t_sched > emitted) atomicAdd(&sc[kStBktRecs], (unsigned long long)(t_sched - emitted));
-    if (t_clone) atomicAdd(&sc[kStCloned], (unsigned long long)t_clone);
-    if (t_cor) atomicAdd(&sc[kStCorrupted], (unsigned long long)t_cor);
-    if (t_lost) atomicAdd(&sc[kStLost], (unsigned long long)t_lost);
-    if (t_bytes) atomicAdd(&sc[kStBytes], (unsigned long long)t_bytes);
-    if (qb) atomicAdd(&sc[kStQueue], (unsigned long long)qb);
-    if (err) {
-      atomicOr(&a.stats[kStErr], (unsigned long long)kErrTimeOverflow);
-      if (a.err_host)
-        __hip_atomic_store(a.err_host, (uint64_t)kErrTimeOverflow, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-  }
+  uint32_t vcnt = 0, t_clone = 0;
+  tally_verdicts(staged, vout, lane, vcnt, t_clone);
+  // the FIFO path left most of the queue where it was; the other wrote all of it back, compacted
+  const uint64_t q_kept = (fifo && qn + wpos > q_moved ? 16ull * (qn + wpos - q_moved) : 0ull) + 8ull * ring.kept;
+  finish_source(a, s, st, sv, ring, ns_all, wpos, fifo ? wpos | new_head << 16 : 0, q_kept, n, vcnt, t_clone, perr,
+                sc, lane);
 }
 
 // (A one-lane-per-source pass listing the active sources, so that idle peers cost no wave, was
 // measured and dropped: 4.17-4.21 against 4.40-4.41 G pkt/s at 1M peers -- an idle wave exits after
 // its first loads, cheaper than the pass over a million sources.)
-// Sources per workgroup (one wave each) and their placement.  Workgroups are dealt round-robin
-// over the 8 XCDs (MI355X_MICROARCH.md §Workgroup dispatch: blocks b and b + 8 share one), each with
-// its own L2, so source s = blockIdx.x put neighbouring sources -- whose 32-B states, 64-B
-// parameters, 8-B offsets, offered records and emit counts share 128-B lines -- on eight different
-// L2s, each fetching the whole line.  With kSparseXcd the blocks of one XCD take one contiguous
-// eighth of the sources, so a line is fetched by one L2.
-constexpr uint32_t kSparseWpg = 1;
-constexpr bool kSparseXcd = true;  // the 1M-peer window's simulate bytes -11 % at equal time
-__host__ __device__ inline uint32_t sparse_blocks(uint32_t n_src) {
-  const uint32_t nb = (n_src + kSparseWpg - 1) / kSparseWpg;
-  return kSparseXcd ? (nb + 7) / 8 * 8 : nb;
-}
-__global__ __launch_bounds__(kWave * kSparseWpg, 7) void k_sim_sparse(SimArgs a) {
-  // the source index must stay wave-uniform for the compiler (a VGPR index turns every per-source
-  // load into a vector load: 126 VGPR spills at 7 waves per SIMD), hence readfirstlane
+// One source per workgroup of one wave (several waves per workgroup were measured and not kept), and
+// the workgroups placed by XCD.  Workgroups are dealt round-robin over the 8 XCDs
+// (MI355X_MICROARCH.md §Workgroup dispatch: blocks b and b + 8 share one), each with its own L2, so
+// source s = blockIdx.x put neighbouring sources -- whose 32-B states, 64-B parameters, 8-B offsets,
+// offered records and emit counts share 128-B lines -- on eight different L2s, each fetching the
+// whole line.  Instead the blocks of one XCD take one contiguous eighth of the sources (the grid is
+// rounded up to a multiple of 8), so a line is fetched by one L2: the 1M-peer window's simulate
+// bytes -11 % at equal time.
+__host__ __device__ inline uint32_t sparse_blocks(uint32_t n_src) { return (n_src + 7) / 8 * 8; }
+__global__ __launch_bounds__(kWave, 7) void k_sim_sparse(SimArgs a) {
+  // (the source index is wave-uniform, from blockIdx alone: a VGPR index turns every per-source load
+  // into a vector load, 126 VGPR spills at 7 waves per SIMD)
   const uint32_t b = blockIdx.x;
-  const uint32_t w = kSparseWpg > 1 ? (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : 0u;
-  const uint32_t blk = kSparseXcd ? (b & 7u) * (gridDim.x >> 3) + (b >> 3) : b;
-  const uint32_t s = blk * kSparseWpg + w;
+  const uint32_t s = (b & 7u) * (gridDim.x >> 3) + (b >> 3);
   if (s < a.n_src) sparse_source(a, s);
 }
 
-// The general path for the worklist k_sim_sparse left: a grid-stride loop over the list (its
-// length is read on the device, so the launch needs no host round trip).
+// The general path for the sources the two kernels above left: a grid-stride loop over the list
+// (its length is read on the device, so the launch needs no host round trip).
 __global__ __launch_bounds__(kWave) void k_sim_list(SimArgs a) {
   __shared__ SimLdsT<kHeapCap> lds;
-  const uint32_t n = a.worklist[-4];
+  const uint32_t* const list = a.work.list();
+  const uint32_t n = *a.work.list_n();
   for (uint32_t i = blockIdx.x; i < n; i += gridDim.x) {
-    const uint32_t s = a.worklist[i];
+    const uint32_t s = list[i];
     if (a.g_first) sim_source<false, kHeapCap, kModePlain, true, true>(a, s, s, lds);
     else sim_source<false, kHeapCap, kModePlain, false, true>(a, s, s, lds);
     wave_lds_sync();  // the write-back's LDS reads are done before the next source's loads land
@@ -3960,16 +3874,17 @@ uint32_t sim_fused_resident() {
 
 // Behind the last sparse kernel: the deferral counts to pinned host memory (the next step's sparse/dense
 // choice reads them without waiting) and every counter zeroed for the next sparse step.
-__global__ void k_work_done(uint32_t* work, uint32_t* host) {
+__global__ void k_work_done(SparseWork work, uint32_t* host) {
   const uint32_t i = threadIdx.x;
-  if (i < 2) __hip_atomic_store(&host[i], work[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  if (i < 2)
+    __hip_atomic_store(&host[i], *(i ? work.multi_n() : work.list_n()), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
   __syncthreads();
-  if (i < 4) work[i] = 0u;
+  if (i < SparseWork::kHeader) work.w[i] = 0u;
 }
 
 void launch_sim_sparse(const SimArgs& a, hipStream_t st, uint32_t* work_host, uint32_t list_hint) {
   if (!a.n_src) return;
-  hipLaunchKernelGGL(k_sim_sparse, dim3(sparse_blocks(a.n_src)), dim3(kWave * kSparseWpg), 0, st, a);
+  hipLaunchKernelGGL(k_sim_sparse, dim3(sparse_blocks(a.n_src)), dim3(kWave), 0, st, a);
   // (grids of 5,120 and 10,240 waves: the same 1M-peer window, within noise)
   hipLaunchKernelGGL(k_sim_multi, dim3(a.n_src < 2048 ? a.n_src : 2048), dim3(kWave), 0, st, a);
   // k_sim_list's grid from the last sparse step's deferrals (its length is read on the device; a
@@ -3979,7 +3894,7 @@ void launch_sim_sparse(const SimArgs& a, hipStream_t st, uint32_t* work_host, ui
   const uint32_t want = std::max<uint32_t>(64u, 2u * list_hint);
   const uint32_t lg = std::min<uint32_t>(std::min<uint32_t>(a.n_src, 16384u), want);
   hipLaunchKernelGGL(k_sim_list, dim3(lg), dim3(kWave), 0, st, a);
-  hipLaunchKernelGGL(k_work_done, dim3(1), dim3(64), 0, st, a.worklist - 4, work_host);
+  hipLaunchKernelGGL(k_work_done, dim3(1), dim3(64), 0, st, a.work, work_host);
 }
 
 void launch_order(const uint32_t* weight, uint32_t n, uint32_t* order, hipStream_t st) {
