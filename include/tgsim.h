@@ -367,6 +367,34 @@ int tgsim_gen_gossip(void* engine, uint32_t n_ticks);
  * out[0..n_floods).  Returns n_floods. */
 int64_t tgsim_gossip_reached(void* engine, uint64_t* out, size_t cap);
 
+/* Propagation of flood f over this shard's peers.  hold(s, f) = the tick at which peer s offers its
+ * forwards of flood f, minus the flood's start tick (start_tick + f * start_gap_ticks): 0 for the
+ * origin, floor(d / tick) + 1 - start for a peer whose earliest uncorrupted receipt was delivered at
+ * d.  Only peers that have forwarded the flood count (the same set tgsim_gossip_reached counts): a
+ * receipt still pending for a later window is not in the report. */
+typedef struct {
+    uint64_t reached;    /* peers of this shard that have forwarded the flood          */
+    uint64_t sum_ticks;  /* sum of hold over them                                      */
+    uint32_t min_ticks;  /* 0xFFFFFFFF when reached == 0                               */
+    uint32_t max_ticks;  /* 0 when reached == 0                                        */
+} tgsim_gossip_flood;    /* 24 B */
+
+/* Reduced on the device; no per-peer table crosses to the host.  floods[0 .. min(cap, n_floods)) and,
+ * when n_bins > 0, hist[f * n_bins + b] = peers with min(hold / bin_ticks, n_bins - 1) == b (the last
+ * bin collects everything beyond).  n_bins 0 (hist may be NULL) .. 256; bin_ticks >= 1 when
+ * n_bins > 0.  Returns n_floods.  Synchronizes like tgsim_gossip_reached.  Per-shard results merge
+ * by sum / sum / min / max / sum.  -EINVAL (with a tgsim_last_error text) when the gossip driver is
+ * not armed, n_bins > 256, bin_ticks == 0 or hist == NULL with n_bins > 0, floods == NULL with
+ * cap > 0.  A late receipt (tgsim_gen_gossip) does not block the report. */
+int64_t tgsim_gossip_spread(void* engine, uint32_t bin_ticks, uint32_t n_bins,
+                            tgsim_gossip_flood* floods, uint64_t* hist, size_t cap);
+
+/* The forward ticks themselves (absolute) for peers [peer, peer + n) of this shard, row-major
+ * [n][n_floods], 0xFFFFFFFF where the peer has not forwarded the flood; compacted and masked on the
+ * device.  Returns the words written, -EINVAL for a range outside the shard, -ENOSPC when
+ * cap < n * n_floods. */
+int64_t tgsim_gossip_times(void* engine, uint32_t peer, uint32_t n, uint32_t* out, size_t cap);
+
 /* ---- sync counters (sync-service SignalEntry / Barrier) ------------------------------------ */
 /* K7: TGSIM_SYNC_STATES u64 counters in device memory, incremented by a kernel on the engine's sync
  * stream (never behind a queued simulation) that also writes the new value into a pinned host

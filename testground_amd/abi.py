@@ -104,6 +104,15 @@ class Gossip(C.Structure):
     ]
 
 
+class GossipFlood(C.Structure):
+    _fields_ = [("reached", C.c_uint64), ("sum_ticks", C.c_uint64), ("min_ticks", C.c_uint32),
+                ("max_ticks", C.c_uint32)]
+
+
+GOSSIP_FLOOD_DTYPE = np.dtype([("reached", "<u8"), ("sum_ticks", "<u8"), ("min_ticks", "<u4"), ("max_ticks", "<u4")])
+GOSSIP_MAX_BINS = 256
+
+
 class CommInfo(C.Structure):
     _fields_ = [("rank", C.c_int32), ("nranks", C.c_int32), ("exchanged_records", C.c_uint64),
                 ("max_rank_count", C.c_uint64), ("slot_cap", C.c_uint64), ("bounds", C.c_uint32 * 9),
@@ -124,6 +133,7 @@ CONFIG_DTYPE = np.dtype([("network", "<u8"), ("enable", "u1"), ("routing_policy"
                          ("n_rules", "<u4"), ("_pad2", "<u4"), ("ipv6", "u1", (16,))])
 assert SHAPE_DTYPE.itemsize == 56 and CONFIG_DTYPE.itemsize == 104
 assert PKT_DTYPE.itemsize == 16 and DELIVERY_DTYPE.itemsize == 24
+assert C.sizeof(GossipFlood) == 24 and GOSSIP_FLOOD_DTYPE.itemsize == 24
 assert C.sizeof(CommInfo) == 72 and C.sizeof(Gossip) == 24 and C.sizeof(Opts) == 56 and C.sizeof(Shape) == 56 and C.sizeof(Config) == 104
 
 # Every symbol include/tgsim.h declares (checked by tests/test_abi.py).
@@ -137,7 +147,8 @@ EXPORTS = [
     "tgsim_sim_capacity", "tgsim_drain", "tgsim_pending_deliveries", "tgsim_verdicts", "tgsim_stats",
     "tgsim_signal", "tgsim_signal_async", "tgsim_barrier_poll", "tgsim_sync_counters", "tgsim_sim_kernel_ms", "tgsim_delivery_kernel_ms", "tgsim_stream", "tgsim_debug_stamps",
     "tgsim_debug_fused_windows", "tgsim_debug_sparse_windows", "tgsim_debug_carry_bytes", "tgsim_debug_bucket_records", "tgsim_debug_exec_faults", "tgsim_step_n",
-    "tgsim_gossip_init", "tgsim_gen_gossip", "tgsim_gossip_reached", "tgsim_metrics",
+    "tgsim_gossip_init", "tgsim_gen_gossip", "tgsim_gossip_reached", "tgsim_gossip_spread",
+    "tgsim_gossip_times", "tgsim_metrics",
     "tgsim_comm_id", "tgsim_comm_init", "tgsim_comm_step", "tgsim_comm_launch", "tgsim_comm_finish", "tgsim_comm_run", "tgsim_comm_barrier", "tgsim_comm_info",
     "tgsim_bridge_create", "tgsim_bridge_destroy", "tgsim_bridge_send", "tgsim_bridge_step",
     "tgsim_bridge_recv", "tgsim_bridge_pending", "tgsim_bridge_in_flight", "tgsim_bridge_now_tick",
@@ -206,6 +217,8 @@ def declare(lib: C.CDLL, prefix: str) -> None:
     f("gossip_init", C.c_int, vp, C.POINTER(Gossip))
     f("gen_gossip", C.c_int, vp, C.c_uint32)
     f("gossip_reached", C.c_int64, vp, C.c_void_p, C.c_size_t)
+    f("gossip_spread", C.c_int64, vp, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t)
+    f("gossip_times", C.c_int64, vp, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t)
     f("offered", C.c_int64, vp, C.c_void_p, C.c_size_t)
     f("metrics", C.c_int64, vp, C.c_uint32, C.c_void_p, C.c_size_t)
     f("comm_id", C.c_int, vp)

@@ -446,6 +446,8 @@ struct tgsim_engine_s {
   tgsim_gossip gossip{};
   DevBuf<uint32_t> d_gfirst, d_gerr, d_gnbr;
   DevBuf<uint64_t> d_gfwd, d_gpend;
+  DevBuf<uint64_t> d_gspread;  // tgsim_gossip_spread's result tables, kSpreadReplicas x 64 x (n_bins + 3) words
+  DevBuf<uint32_t> d_gtimes;   // tgsim_gossip_times' rows
 
   int fail(int code, const char* fmt, ...) {
     char buf[512];
@@ -2127,7 +2129,7 @@ void tgsim_destroy(void* e) {
   E->d_in.release(); E->d_verdict.release(); E->d_emit.release(); E->d_emit_n.release(); E->d_emit_alt.release(); E->d_emit_n_alt.release(); E->d_lcnt.release(); E->d_lcnt_alt.release(); E->d_dbkt.release(); E->d_dbkt_alt.release(); E->d_sdoff.release(); E->d_sdpos.release(); E->d_sdblk.release(); E->d_sdtot.release(); E->d_sdoff_alt.release(); E->d_sdpos_alt.release(); E->d_sdblk_alt.release(); E->d_sdtot_alt.release(); E->d_sdoff_alt2.release(); E->d_sdpos_alt2.release(); E->d_sdblk_alt2.release(); E->d_sdtot_alt2.release(); E->d_emit_alt2.release(); E->d_emit_n_alt2.release(); E->d_lcnt_alt2.release(); E->d_dbkt_alt2.release(); E->d_pidx.release(); E->d_pidx_alt.release(); E->d_pidx_alt2.release(); E->d_rcnt.release(); E->d_rpos.release(); E->d_rblk.release(); E->d_rtot.release();
   E->d_bucket.release(); E->d_scatter.release(); E->d_sorted.release(); E->d_dcnt.release();
   E->d_doff.release(); E->d_dpos.release(); E->d_dblk.release(); E->d_dtot.release();
-  E->d_drain.release(); E->d_gfirst.release(); E->d_gfwd.release(); E->d_gpend.release(); E->d_gnbr.release(); E->d_gerr.release(); E->d_stats.release(); E->d_stamps.release(); E->d_order.release();
+  E->d_drain.release(); E->d_gfirst.release(); E->d_gfwd.release(); E->d_gpend.release(); E->d_gnbr.release(); E->d_gerr.release(); E->d_gspread.release(); E->d_gtimes.release(); E->d_stats.release(); E->d_stamps.release(); E->d_order.release();
   E->d_msrc.release(); E->d_mdst.release(); E->d_mhist.release(); E->d_work.release(); E->d_rsend.release();
   for (auto* q : {&E->gen_q, &E->gen_free})
     for (auto& w : *q) {
@@ -2408,6 +2410,69 @@ int64_t tgsim_gossip_reached(void* e, uint64_t* out, size_t cap) {
     out[f] = c;
   }
   return E->gossip.n_floods;
+}
+
+int64_t tgsim_gossip_spread(void* e, uint32_t bin_ticks, uint32_t n_bins, tgsim_gossip_flood* floods, uint64_t* hist,
+                            size_t cap) {
+  Eng* E = as_eng(e);
+  if (!E) return -EINVAL;
+  if (!E->gossip_on) return E->fail(-EINVAL, "gossip_spread: the gossip driver is not armed (tgsim_gossip_init)");
+  if (n_bins > kSpreadMaxBins) return E->fail(-EINVAL, "gossip_spread: n_bins %u above %u", n_bins, kSpreadMaxBins);
+  if (n_bins && bin_ticks == 0) return E->fail(-EINVAL, "gossip_spread: bin_ticks 0 with %u bins", n_bins);
+  if (n_bins && !hist) return E->fail(-EINVAL, "gossip_spread: no histogram buffer for %u bins", n_bins);
+  if (!floods && cap) return E->fail(-EINVAL, "gossip_spread: no flood buffer for %zu entries", cap);
+  HIPCHK(hipSetDevice(E->dev));
+  int rc = sync_stream(E);  // the receipts of the last delivery are folded on the delivery stream
+  if (rc) return rc;
+  const uint32_t nf = E->gossip.n_floods;
+  const size_t words = static_cast<size_t>(64) * (n_bins + 3);
+  HIPCHK(E->d_gspread.ensure(words * kSpreadReplicas));
+  GossipSpreadArgs a{};
+  a.first = E->d_gfirst.p;
+  a.fwd = E->d_gfwd.p;
+  a.res = reinterpret_cast<unsigned long long*>(E->d_gspread.p);
+  a.n_src = E->S;
+  a.n_floods = nf;
+  a.start = static_cast<uint32_t>(E->gossip.start_tick);
+  a.gap = E->gossip.start_gap_ticks;
+  a.bin_ticks = n_bins ? bin_ticks : 1u;
+  a.n_bins = n_bins;
+  launch_gossip_spread(a, E->st);
+  HIPCHK(hipGetLastError());
+  std::vector<uint64_t> res(words);
+  HIPCHK(hipMemcpyAsync(res.data(), E->d_gspread.p, sizeof(uint64_t) * words, hipMemcpyDeviceToHost, E->st));
+  HIPCHK(hipStreamSynchronize(E->st));
+  const uint32_t* mm = reinterpret_cast<const uint32_t*>(res.data() + 128);
+  for (uint32_t f = 0; f < nf && f < cap; ++f) {
+    floods[f].reached = res[f];
+    floods[f].sum_ticks = res[64 + f];
+    floods[f].min_ticks = mm[f];
+    floods[f].max_ticks = mm[64 + f];
+  }
+  if (n_bins) memcpy(hist, res.data() + 192, sizeof(uint64_t) * nf * n_bins);
+  return nf;
+}
+
+int64_t tgsim_gossip_times(void* e, uint32_t peer, uint32_t n, uint32_t* out, size_t cap) {
+  Eng* E = as_eng(e);
+  if (!E) return -EINVAL;
+  if (!E->gossip_on) return E->fail(-EINVAL, "gossip_times: the gossip driver is not armed (tgsim_gossip_init)");
+  if (peer < E->o.shard_begin || peer > E->o.shard_end || n > E->o.shard_end - peer)
+    return E->fail(-EINVAL, "gossip_times: peers [%u, %llu) outside the shard [%u, %u)", peer,
+                   static_cast<unsigned long long>(peer) + n, E->o.shard_begin, E->o.shard_end);
+  const size_t words = static_cast<size_t>(n) * E->gossip.n_floods;
+  if (cap < words) return E->fail(-ENOSPC, "gossip_times: %zu words for %zu", cap, words);
+  if (words && !out) return E->fail(-EINVAL, "gossip_times: no output buffer");
+  HIPCHK(hipSetDevice(E->dev));
+  int rc = sync_stream(E);
+  if (rc) return rc;
+  if (!words) return 0;
+  HIPCHK(E->d_gtimes.ensure(words));
+  launch_gossip_times(E->d_gfirst.p, E->d_gfwd.p, peer - E->o.shard_begin, n, E->gossip.n_floods, E->d_gtimes.p, E->st);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(out, E->d_gtimes.p, sizeof(uint32_t) * words, hipMemcpyDeviceToHost, E->st));
+  HIPCHK(hipStreamSynchronize(E->st));
+  return static_cast<int64_t>(words);
 }
 
 int64_t tgsim_sim_capacity(void* e) {

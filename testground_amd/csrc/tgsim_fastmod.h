@@ -27,4 +27,11 @@ TGSIM_HD inline uint32_t fastmod_u32(uint32_t raw, uint32_t m, uint32_t rcp) {
   return r >= m ? r - m : r;
 }
 
+// floor(raw / m) from the same reciprocal: q above is the quotient or one less (same bounds), and the
+// remainder tells which (the histogram bin of a hold time, k_gossip_spread).
+TGSIM_HD inline uint32_t fastdiv_u32(uint32_t raw, uint32_t m, uint32_t rcp) {
+  const uint32_t q = (uint32_t)(((uint64_t)raw * rcp) >> 32);
+  return q + (raw - q * m >= m ? 1u : 0u);
+}
+
 }  // namespace tgsim

@@ -303,6 +303,18 @@ struct GossipArgs {
   uint64_t tick_ns, win0;   // window start (absolute tick)
 };
 
+// k_gossip_spread (tgsim_gossip_spread): the reduction over the forwarded entries of first[].
+constexpr uint32_t kSpreadMaxBins = 256;
+constexpr uint32_t kSpreadReplicas = 8;  // result tables the workgroups' atomics are spread over
+struct GossipSpreadArgs {
+  const uint32_t* first;    // [s][64]
+  const uint64_t* fwd;      // [s]
+  unsigned long long* res;  // kSpreadReplicas x 64 x (n_bins + 3) words, initialised by the launcher; the report in the first
+  uint32_t n_src, n_floods;
+  uint32_t start, gap;      // flood f starts at tick start + f * gap (32 bits, like first[])
+  uint32_t bin_ticks, bin_rcp, n_bins;  // bin_rcp = fastmod_rcp(bin_ticks); n_bins 0: no histogram
+};
+
 // Engine hooks of the RCCL exchange layer (tgsim_comm.cpp), which drives the engine through the
 // public ABI and keeps its own state in the engine's comm slot (freed by tgsim_destroy).
 struct CommSlot {

@@ -2978,6 +2978,134 @@ __global__ __launch_bounds__(256) void k_gossip_write(GossipArgs g, const uint64
 }
 
 // ---------------------------------------------------------------------------------------------
+// Propagation report (tgsim_gossip_spread): one streaming pass over fwd[S] and first[S][64] in the
+// layout of the generation kernels (a wavefront per kGossipPeers peers, lane = flood).  A lane reads
+// a receipt tick only where the peer's fwd bit is set (the entries fold_receipt and gossip_recv_one
+// no longer touch), so a flood that has not spread leaves its rows unread.  Each lane keeps its
+// flood's count, sum, minimum and maximum in registers; the workgroup's histogram lives in LDS as
+// [bin][flood] (lane f on bank f mod 32 whatever its bin: the lanes of a wave never conflict, only
+// the waves of a workgroup contend for a word).  A persistent grid strides over the peer groups; a
+// workgroup ends with one set of global atomics per flood and one per non-zero bin.
+// res: [0, 64) reached, [64, 128) sum, then 64 u32 minima and 64 u32 maxima, then [flood][bin] u64;
+// kSpreadReplicas such tables, one per workgroup index mod kSpreadReplicas, folded into the first by
+// k_gossip_spread_fold.
+constexpr uint32_t kSpreadWaves = 16;
+__global__ __launch_bounds__(kSpreadWaves * kWave) void k_gossip_spread(GossipSpreadArgs a) {
+  __shared__ uint32_t hist[kSpreadMaxBins * kWave];
+  __shared__ unsigned long long r_sum[kWave];
+  __shared__ uint32_t r_cnt[kWave], r_min[kWave], r_max[kWave];
+  const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+  const uint32_t n_words = a.n_bins * kWave;
+  for (uint32_t i = threadIdx.x; i < n_words; i += kSpreadWaves * kWave) hist[i] = 0u;
+  if (threadIdx.x < kWave) {
+    r_sum[lane] = 0ull;
+    r_cnt[lane] = 0u;
+    r_min[lane] = 0xFFFFFFFFu;
+    r_max[lane] = 0u;
+  }
+  __syncthreads();
+  const uint32_t start = a.start + lane * a.gap;  // the flood's start tick (32 bits, as first[] holds ticks)
+  const uint32_t n_grp = (a.n_src + kGossipPeers - 1) / kGossipPeers, stride = gridDim.x * kSpreadWaves;
+  uint32_t cnt = 0, mn = 0xFFFFFFFFu, mx = 0;
+  uint64_t sum = 0;
+  uint32_t grp = blockIdx.x * kSpreadWaves + wv;
+  // lane i < 8: the mask of peer s0 + i (one 64-B load), the next group's while this one's rows arrive
+  uint64_t fwd_l = grp < n_grp && lane < kGossipPeers && grp * kGossipPeers + lane < a.n_src
+                       ? a.fwd[grp * kGossipPeers + lane] : 0ull;
+  while (grp < n_grp) {
+    const uint32_t s0 = grp * kGossipPeers, nxt = grp + stride;
+    const uint64_t fwd_n = nxt < n_grp && lane < kGossipPeers && nxt * kGossipPeers + lane < a.n_src
+                               ? a.fwd[nxt * kGossipPeers + lane] : 0ull;
+    uint32_t t[kGossipPeers];
+    bool have[kGossipPeers];
+#pragma unroll
+    for (uint32_t i = 0; i < kGossipPeers; ++i) {
+      have[i] = readlane64(fwd_l, i) >> lane & 1ull;
+      t[i] = have[i] ? a.first[(uint64_t)(s0 + i) * 64 + lane] : 0u;
+    }
+#pragma unroll
+    for (uint32_t i = 0; i < kGossipPeers; ++i) {
+      if (!have[i]) continue;
+      const uint32_t hold = t[i] - start;
+      ++cnt;
+      sum += hold;
+      mn = hold < mn ? hold : mn;
+      mx = hold > mx ? hold : mx;
+      if (a.n_bins) {
+        const uint32_t b = fastdiv_u32(hold, a.bin_ticks, a.bin_rcp);
+        atomicAdd(&hist[(b < a.n_bins ? b : a.n_bins - 1) * kWave + lane], 1u);
+      }
+    }
+    fwd_l = fwd_n;
+    grp = nxt;  // (n_grp <= 2^29 and the stride is a few thousand: no wrap)
+  }
+  if (cnt) {
+    atomicAdd(&r_cnt[lane], cnt);
+    atomicAdd(&r_sum[lane], (unsigned long long)sum);
+    atomicMin(&r_min[lane], mn);
+    atomicMax(&r_max[lane], mx);
+  }
+  __syncthreads();
+  // (replica blockIdx mod kSpreadReplicas: the chain of atomics on one word is that much shorter)
+  unsigned long long* res = a.res + (uint64_t)(blockIdx.x % kSpreadReplicas) * (kWave * (a.n_bins + 3));
+  if (threadIdx.x < kWave && r_cnt[lane]) {
+    uint32_t* mm = reinterpret_cast<uint32_t*>(res + 2 * kWave);
+    atomicAdd(&res[lane], (unsigned long long)r_cnt[lane]);
+    atomicAdd(&res[kWave + lane], r_sum[lane]);
+    atomicMin(&mm[lane], r_min[lane]);
+    atomicMax(&mm[kWave + lane], r_max[lane]);
+  }
+  for (uint32_t i = threadIdx.x; i < n_words; i += kSpreadWaves * kWave) {
+    const uint32_t v = hist[i], b = i >> 6, f = i & 63u;
+    if (v && f < a.n_floods) atomicAdd(&res[3 * kWave + (uint64_t)f * a.n_bins + b], (unsigned long long)v);
+  }
+}
+
+// The kSpreadReplicas result tables before the pass (minima all-ones, the rest zero) ...
+__global__ __launch_bounds__(256) void k_gossip_spread_init(unsigned long long* res, uint32_t words) {
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= words * kSpreadReplicas) return;
+  const uint32_t w = i % words;
+  res[i] = w >= 2 * kWave && w < 2 * kWave + kWave / 2 ? ~0ull : 0ull;  // 64 u32 minima = 32 words
+}
+
+// ... and folded into the first one behind it: sums, but for the minima and maxima (u32 pairs).
+__global__ __launch_bounds__(256) void k_gossip_spread_fold(unsigned long long* res, uint32_t words) {
+  const uint32_t w = blockIdx.x * 256 + threadIdx.x;
+  if (w >= words) return;
+  unsigned long long v = res[w];
+  for (uint32_t r = 1; r < kSpreadReplicas; ++r) {
+    const unsigned long long x = res[(uint64_t)r * words + w];
+    if (w >= 2 * kWave && w < 3 * kWave) {
+      uint32_t lo = (uint32_t)v, hi = (uint32_t)(v >> 32);
+      const uint32_t xl = (uint32_t)x, xh = (uint32_t)(x >> 32);
+      if (w < 2 * kWave + kWave / 2) {
+        lo = xl < lo ? xl : lo;
+        hi = xh < hi ? xh : hi;
+      } else {
+        lo = xl > lo ? xl : lo;
+        hi = xh > hi ? xh : hi;
+      }
+      v = ((unsigned long long)hi << 32) | lo;
+    } else {
+      v += x;
+    }
+  }
+  res[w] = v;
+}
+
+// tgsim_gossip_times: rows of n_floods forward ticks for n peers from local peer s0 on, masked by
+// the peers' fwd bits (a wavefront per peer, lane = flood).
+__global__ __launch_bounds__(256) void k_gossip_times(const uint32_t* __restrict__ first, const uint64_t* __restrict__ fwd,
+                                                      uint32_t s0, uint32_t n, uint32_t n_floods,
+                                                      uint32_t* __restrict__ out) {
+  const uint32_t r = blockIdx.x * 4 + (threadIdx.x >> 6), f = threadIdx.x & 63u;
+  if (r >= n || f >= n_floods) return;
+  const uint64_t s = (uint64_t)s0 + r;
+  out[(uint64_t)r * n_floods + f] = (fwd[s] >> f & 1ull) ? first[s * 64 + f] : 0xFFFFFFFFu;
+}
+
+// ---------------------------------------------------------------------------------------------
 // Exclusive scan (u64), three phases, 1024 elements per block.
 __device__ __forceinline__ uint64_t block_excl_scan(uint64_t v, uint64_t* sh, uint64_t& total) {
   const uint32_t t = threadIdx.x, lane = t & 63u, w = t >> 6;
@@ -3983,6 +4111,35 @@ void launch_gossip_recv_in(const GossipArgs& g, const tgsim_delivery* recs, uint
 
 void launch_gossip_recv_dev(const GossipArgs& g, const tgsim_delivery* recs, const uint64_t* n_dev, hipStream_t st) {
   hipLaunchKernelGGL(k_gossip_recv_dev, dim3(2048), dim3(256), 0, st, g, recs, n_dev);
+}
+
+void launch_gossip_spread(GossipSpreadArgs a, hipStream_t st) {
+  static uint32_t resident = 0;  // workgroups of k_gossip_spread the device holds at once
+  if (!resident) {
+    int dev = 0, per_cu = 0, cus = 0;
+    if (hipGetDevice(&dev) != hipSuccess ||
+        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+        hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_gossip_spread, kSpreadWaves * kWave, 0) != hipSuccess ||
+        per_cu <= 0 || cus <= 0)
+      resident = 512;
+    else
+      resident = (uint32_t)(per_cu * cus);
+  }
+  a.bin_rcp = fastmod_rcp(a.bin_ticks);
+  const uint32_t words = kWave * (a.n_bins + 3);
+  hipLaunchKernelGGL(k_gossip_spread_init, dim3((words * kSpreadReplicas + 255) / 256), dim3(256), 0, st, a.res, words);
+  // at least two peer groups per wavefront where there are that many (the mask of the next group is
+  // loaded while the rows of this one arrive), and no more workgroups than are resident at once
+  const uint32_t n_grp = (a.n_src + kGossipPeers - 1) / kGossipPeers;
+  uint32_t grid = (n_grp + 2 * kSpreadWaves - 1) / (2 * kSpreadWaves);
+  grid = grid > resident ? resident : grid;
+  if (grid) hipLaunchKernelGGL(k_gossip_spread, dim3(grid), dim3(kSpreadWaves * kWave), 0, st, a);
+  if (grid > 1) hipLaunchKernelGGL(k_gossip_spread_fold, dim3((words + 255) / 256), dim3(256), 0, st, a.res, words);
+}
+
+void launch_gossip_times(const uint32_t* first, const uint64_t* fwd, uint32_t s0, uint32_t n, uint32_t n_floods,
+                         uint32_t* out, hipStream_t st) {
+  if (n) hipLaunchKernelGGL(k_gossip_times, dim3(n / 4 + (n % 4 ? 1u : 0u)), dim3(256), 0, st, first, fwd, s0, n, n_floods, out);
 }
 
 void launch_gossip(const GossipArgs& g, const tgsim_delivery* recs, uint64_t n, uint64_t* counts,

@@ -62,6 +62,13 @@ void launch_gossip_nbr(const GossipArgs& g, uint32_t* nbr, hipStream_t st);
 void launch_gossip_recv_dev(const GossipArgs& g, const tgsim_delivery* recs, const uint64_t* n_dev, hipStream_t st);
 void launch_gossip_recv_in(const GossipArgs& g, const tgsim_delivery* recs, uint64_t n, uint64_t slot, bool skip_own,
                            hipStream_t st);
+// The propagation report: initialises a.res (minima all-ones, the rest zero) on st, then one pass of
+// a persistent grid sized from the CU count and the fold of the result replicas into the first.
+// bin_rcp is filled in here.
+void launch_gossip_spread(GossipSpreadArgs a, hipStream_t st);
+// Forward ticks of local peers [s0, s0 + n), rows of n_floods words (unforwarded: 0xFFFFFFFF).
+void launch_gossip_times(const uint32_t* first, const uint64_t* fwd, uint32_t s0, uint32_t n, uint32_t n_floods,
+                         uint32_t* out, hipStream_t st);
 // Exclusive scan of in[0..n) into out[0..n] (out[n] = total, also stored at *total when non-null);
 // pos (optional) receives a copy of out[0..n), the scatter cursors.
 // clear: the input counts, zeroed as they are read (the histogram free for its next window), or null

@@ -158,6 +158,35 @@ class CABIEngine:
         n = self._check(self._fn("gossip_reached")(self._h, out.ctypes.data, 64), "gossip_reached")
         return out[:n]
 
+    def _gossip_fn(self, name: str):
+        fn = getattr(self._lib, self._p + name, None)
+        if fn is None:  # an engine library without the propagation report (the oracle)
+            raise EngineError(-errno.ENOSYS, f"{self._p}{name} is not exported by this engine library")
+        return fn
+
+    def gossip_spread(self, bin_ticks: int = 0, n_bins: int = 0) -> dict:
+        """Propagation report of this shard, reduced on the device (tgsim_gossip_spread): per flood
+        `reached`, `sum_ticks`, `min_ticks`, `max_ticks` of the hold times (ticks from the flood's
+        start to a peer's forward) and `hist` [n_floods, n_bins], bin b = holds in
+        [b * bin_ticks, (b + 1) * bin_ticks), the last bin everything beyond."""
+        fn = self._gossip_fn("gossip_spread")
+        floods = np.zeros(64, dtype=abi.GOSSIP_FLOOD_DTYPE)
+        hist = np.zeros(64 * n_bins, dtype=np.uint64)
+        n = self._check(fn(self._h, bin_ticks, n_bins, floods.ctypes.data, hist.ctypes.data if n_bins else None, 64),
+                        "gossip_spread")
+        return {"reached": floods["reached"][:n].copy(), "sum_ticks": floods["sum_ticks"][:n].copy(),
+                "min_ticks": floods["min_ticks"][:n].copy(), "max_ticks": floods["max_ticks"][:n].copy(),
+                "hist": hist[:n * n_bins].reshape(n, n_bins)}
+
+    def gossip_times(self, peer: int, n: int) -> np.ndarray:
+        """[n, n_floods] absolute forward ticks of peers [peer, peer + n) of this shard (global
+        ids), 0xFFFFFFFF where the peer has not forwarded the flood (tgsim_gossip_times)."""
+        fn = self._gossip_fn("gossip_times")
+        n_floods = getattr(self, "n_floods", 64)  # set by gossip_init (unarmed: the call says so)
+        out = np.empty(n * n_floods, dtype=np.uint32)
+        self._check(fn(self._h, peer, n, out.ctypes.data, len(out)), "gossip_times")
+        return out.reshape(n, n_floods)
+
     def step(self, n_ticks: int) -> None:
         self._check(self._fn("step")(self._h, n_ticks), "step")
 

@@ -42,3 +42,24 @@ def lines(m: Dict[str, np.ndarray], plan: str, run: str, ts_ns: int, shard_begin
         meas = _escape(f"results.{plan}.{name}")
         out += [f"{meas},{tags},bin={b} value={int(c)}i {ts_ns}" for b, c in enumerate(m["hist"][h]) if c]
     return out
+
+
+GOSSIP_METRICS = [("gossip.reached", "reached"), ("gossip.hold_min", "min_ticks"), ("gossip.hold_max", "max_ticks"),
+                  ("gossip.hold_sum", "sum_ticks")]
+
+
+def gossip_lines(spread: Dict[str, np.ndarray], bin_ticks: int, plan: str, run: str, ts_ns: int) -> List[str]:
+    """The propagation report (Engine.gossip_spread(), or workloads.merge_spread of the shards') in
+    the shape of lines(): one line per flood and measure (tag `flood`; hold times in ticks after the
+    flood's start), and one per non-zero histogram bin (tags `flood` and `bin`, the bin's lower edge
+    b * bin_ticks in ticks; the last bin holds everything from its edge on)."""
+    tags = f"run={_escape(run)}"
+    out: List[str] = []
+    for name, key in GOSSIP_METRICS:
+        meas = _escape(f"results.{plan}.{name}")
+        out += [f"{meas},{tags},flood={f} value={int(v)}i {ts_ns}" for f, v in enumerate(spread[key])]
+    meas = _escape(f"results.{plan}.gossip.hold_hist")
+    for f, row in enumerate(spread["hist"]):
+        out += [f"{meas},{tags},flood={f},bin={b * int(bin_ticks)} value={int(c)}i {ts_ns}"
+                for b, c in enumerate(row) if c]
+    return out

@@ -223,6 +223,47 @@ def gossip_run(eng, n_windows: int, window: int, collect: bool = True):
     return out
 
 
+SPREAD_KEYS = ("reached", "sum_ticks", "min_ticks", "max_ticks", "hist")
+
+
+def merge_spread(spreads) -> Dict[str, np.ndarray]:
+    """The report of a whole run from its shards' Engine.gossip_spread() results (same floods, same
+    bins): reached, sum_ticks and hist add, min_ticks and max_ticks are the extremes.  A shard no
+    flood has reached carries the neutral values (0, 0, 0xFFFFFFFF, 0), so it merges like any other."""
+    spreads = list(spreads)
+    if not spreads:
+        raise ValueError("merge_spread: no spreads")
+    if any(s["hist"].shape != spreads[0]["hist"].shape for s in spreads):
+        raise ValueError("merge_spread: the shards' histograms differ in shape")
+    return {
+        "reached": np.sum([s["reached"] for s in spreads], axis=0, dtype=np.uint64),
+        "sum_ticks": np.sum([s["sum_ticks"] for s in spreads], axis=0, dtype=np.uint64),
+        "min_ticks": np.min([s["min_ticks"] for s in spreads], axis=0).astype(np.uint32),
+        "max_ticks": np.max([s["max_ticks"] for s in spreads], axis=0).astype(np.uint32),
+        "hist": np.sum([s["hist"] for s in spreads], axis=0, dtype=np.uint64),
+    }
+
+
+def spread_coverage(spread: Dict[str, np.ndarray], bin_ticks: int, n_peers: int, fractions) -> np.ndarray:
+    """The propagation curve read off a spread's histogram: out[f, i] = the upper edge, in ticks after
+    flood f's start, of the first bin at which the cumulative count reaches ceil(fractions[i] * n_peers)
+    peers; -1 where the flood has not reached that many, or reaches them only in the last bin (which
+    collects every hold beyond the histogram, so it has no upper edge)."""
+    hist = np.asarray(spread["hist"], dtype=np.uint64)
+    n_floods, n_bins = hist.shape
+    out = np.full((n_floods, len(fractions)), -1, dtype=np.int64)
+    if n_bins == 0:
+        return out
+    cum = np.cumsum(hist, axis=1)
+    for i, frac in enumerate(fractions):
+        need = int(np.ceil(frac * n_peers - 1e-9))  # (0.9 * 1000 is 900.0000000000001 in binary)
+        hit = cum >= need
+        b = np.argmax(hit, axis=1)
+        ok = hit.any(axis=1) & (b < n_bins - 1)
+        out[ok, i] = (b[ok] + 1) * bin_ticks
+    return out
+
+
 # ---------------------------------------------------------------------------------------------
 # C5: epochs of C3 traffic with mid-run reshaping and a barrier per epoch.
 EPOCH_TICKS = 1000
