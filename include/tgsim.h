@@ -395,6 +395,78 @@ int64_t tgsim_gossip_spread(void* engine, uint32_t bin_ticks, uint32_t n_bins,
  * cap < n * n_floods. */
 int64_t tgsim_gossip_times(void* engine, uint32_t peer, uint32_t n, uint32_t* out, size_t cap);
 
+/* ---- ping mesh (C1/C2 and plans/verify as one closed loop on the device) -------------------- */
+/* Every peer probes the targets in its slots on a fixed schedule; echo replies are generated on the
+ * device from each window's delivered records, wait in a device calendar for the window that holds
+ * their tick, and loss and round-trip time are folded per (peer, slot) pair as replies are
+ * delivered.  No delivery has to reach the host.
+ *
+ *   Request  peer s, slot k, probe j: one packet s -> targets[s * fanout + k], seq = j * fanout + k,
+ *            `len` bytes, at tick start_tick + j * interval_ticks.  A target is a peer id other
+ *            than s, TGSIM_EXTERNAL, or TGSIM_PING_NONE (an empty slot sends nothing and is not a
+ *            pair).
+ *   Reply    a delivered request record with neither TGSIM_FLAG_DUP nor TGSIM_FLAG_CORRUPT,
+ *            addressed to r, from q, delivered at d, makes r offer one packet r -> q, seq =
+ *            0x80000000 | request seq, `len` bytes, at tick floor(d / tick_ns) + 1.  Clones and
+ *            corrupted copies are ignored and counted (dup_ignored first, else corrupt_ignored).  A
+ *            non-clone record exists at most once per offered packet, so a probe has at most one
+ *            counted reply.
+ *   Receipt  a delivered reply with neither flag, at d, credits the pair (dst, k = (seq &
+ *            0x7FFFFFFF) % fanout) with rtt_ns = d - (start_tick + j * interval_ticks) * tick_ns,
+ *            j = (seq & 0x7FFFFFFF) / fanout.  Records count when a step emits them (when
+ *            tgsim_drain would show them).  A record that matches no probe of the schedule (traffic
+ *            queued before the driver was armed) is neither answered nor credited.
+ *   Order    within one source's window the offered packets are ordered by (tick, seq, dst).
+ *   Loop     as for gossip, every later window <= lookahead_ns <= the minimum netem delay.  A
+ *            calendar entry whose tick precedes the window being generated is a late receipt:
+ *            tgsim_gen_ping fails with -EINVAL (tgsim_last_error names the tick), nothing is
+ *            generated, and the error stays until the next tgsim_ping_init; the reports stay
+ *            readable.
+ * Single engine only (it must own every peer): replies are generated at the destination's shard, so
+ * a sharded form can follow. */
+#define TGSIM_PING_NONE 0xFFFFFFFEu      /* targets[] entry: empty slot */
+typedef struct {
+    uint32_t fanout;         /* target slots per peer, 1..64                              */
+    uint32_t count;          /* probes per slot, 1..65535                                 */
+    uint32_t interval_ticks; /* >= 1; probe j of every slot is offered at start + j*interval */
+    uint32_t len;            /* bytes on the wire, 1..65535, request and reply            */
+    uint64_t start_tick;     /* absolute tick of probe 0, >= the engine's next window     */
+    uint64_t bin_ns;         /* RTT histogram bin width, >= 1 when n_bins > 0             */
+    uint32_t n_bins;         /* 0..256; the last bin collects everything beyond           */
+    uint32_t _pad;
+} tgsim_ping;                /* 40 B */
+typedef struct {             /* one (peer, slot); 32 B */
+    uint32_t sent;           /* probes of this slot offered so far (start + j*interval < now_tick) */
+    uint32_t received;       /* counted replies                                            */
+    uint64_t sum_ns, min_ns /* UINT64_MAX when none */, max_ns /* 0 when none */;
+} tgsim_ping_pair;
+typedef struct {
+    uint64_t pairs, sent, received, sum_ns, min_ns, max_ns;
+    uint64_t pairs_all;       /* sent > 0 and received == sent  */
+    uint64_t pairs_none;      /* sent > 0 and received == 0     */
+    uint64_t dup_ignored, corrupt_ignored; /* records skipped on either leg                */
+    uint64_t pending_replies; /* replies recorded but not yet offered (the calendar)       */
+} tgsim_ping_summary;
+/* Arms the driver (targets: [n_peers][fanout]).  -EINVAL (with a tgsim_last_error text) for an
+ * engine that does not own every peer, a bad field, a target that is the peer itself or out of range
+ * (the text names the entry), or a start tick in the past; -EBUSY while the gossip driver is armed
+ * or while host packets or generated windows are pending.  While armed, tgsim_submit,
+ * tgsim_gen_storm, tgsim_gossip_init and the tgsim_step_sim* / tgsim_comm_* steps return -EBUSY and
+ * tgsim_step_n runs its windows one by one.  tgsim_configure between windows is allowed: a purged or
+ * disconnected leg simply never produces a receipt.  tgsim_ping_init(engine, NULL, NULL) disarms and
+ * frees the state. */
+int tgsim_ping_init(void* engine, const tgsim_ping* p, const uint32_t* targets);
+/* Generates the next n_ticks window on the device, like tgsim_gen_storm: the scheduled probes and the
+ * calendar's replies due in it; the entries not yet due stay in the calendar.  One window at a time
+ * (-EBUSY while a generated window is pending). */
+int tgsim_gen_ping(void* engine, uint32_t n_ticks);
+/* The summary over every pair, reduced on the device, and (n_bins > 0) hist[b] = counted replies
+ * with min(rtt_ns / bin_ns, n_bins - 1) == b; hist_cap >= n_bins.  Returns n_bins. */
+int64_t tgsim_ping_report(void* engine, tgsim_ping_summary* out, uint64_t* hist, size_t hist_cap);
+/* The pair rows of peers [peer, peer + n), row-major [n][fanout] (an empty slot: sent 0, received 0);
+ * returns the rows written, -ENOSPC when cap < n * fanout. */
+int64_t tgsim_ping_pairs(void* engine, uint32_t peer, uint32_t n, tgsim_ping_pair* out, size_t cap);
+
 /* ---- sync counters (sync-service SignalEntry / Barrier) ------------------------------------ */
 /* K7: TGSIM_SYNC_STATES u64 counters in device memory, incremented by a kernel on the engine's sync
  * stream (never behind a queued simulation) that also writes the new value into a pinned host

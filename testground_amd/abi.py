@@ -113,6 +113,26 @@ GOSSIP_FLOOD_DTYPE = np.dtype([("reached", "<u8"), ("sum_ticks", "<u8"), ("min_t
 GOSSIP_MAX_BINS = 256
 
 
+# Ping mesh driver (tgsim_ping_*).
+PING_NONE = 0xFFFFFFFE  # targets[] entry: empty slot
+PING_MAX_BINS = 256
+
+
+class Ping(C.Structure):
+    _fields_ = [("fanout", C.c_uint32), ("count", C.c_uint32), ("interval_ticks", C.c_uint32), ("len", C.c_uint32),
+                ("start_tick", C.c_uint64), ("bin_ns", C.c_uint64), ("n_bins", C.c_uint32), ("_pad", C.c_uint32)]
+
+
+PING_PAIR_DTYPE = np.dtype([("sent", "<u4"), ("received", "<u4"), ("sum_ns", "<u8"), ("min_ns", "<u8"),
+                            ("max_ns", "<u8")])
+PING_SUMMARY_FIELDS = ("pairs", "sent", "received", "sum_ns", "min_ns", "max_ns", "pairs_all", "pairs_none",
+                       "dup_ignored", "corrupt_ignored", "pending_replies")
+
+
+class PingSummary(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in PING_SUMMARY_FIELDS]
+
+
 class CommInfo(C.Structure):
     _fields_ = [("rank", C.c_int32), ("nranks", C.c_int32), ("exchanged_records", C.c_uint64),
                 ("max_rank_count", C.c_uint64), ("slot_cap", C.c_uint64), ("bounds", C.c_uint32 * 9),
@@ -134,6 +154,7 @@ CONFIG_DTYPE = np.dtype([("network", "<u8"), ("enable", "u1"), ("routing_policy"
 assert SHAPE_DTYPE.itemsize == 56 and CONFIG_DTYPE.itemsize == 104
 assert PKT_DTYPE.itemsize == 16 and DELIVERY_DTYPE.itemsize == 24
 assert C.sizeof(GossipFlood) == 24 and GOSSIP_FLOOD_DTYPE.itemsize == 24
+assert C.sizeof(Ping) == 40 and PING_PAIR_DTYPE.itemsize == 32 and C.sizeof(PingSummary) == 88
 assert C.sizeof(CommInfo) == 72 and C.sizeof(Gossip) == 24 and C.sizeof(Opts) == 56 and C.sizeof(Shape) == 56 and C.sizeof(Config) == 104
 
 # Every symbol include/tgsim.h declares (checked by tests/test_abi.py).
@@ -149,6 +170,7 @@ EXPORTS = [
     "tgsim_debug_fused_windows", "tgsim_debug_sparse_windows", "tgsim_debug_carry_bytes", "tgsim_debug_bucket_records", "tgsim_debug_exec_faults", "tgsim_step_n",
     "tgsim_gossip_init", "tgsim_gen_gossip", "tgsim_gossip_reached", "tgsim_gossip_spread",
     "tgsim_gossip_times", "tgsim_metrics",
+    "tgsim_ping_init", "tgsim_gen_ping", "tgsim_ping_report", "tgsim_ping_pairs",
     "tgsim_comm_id", "tgsim_comm_init", "tgsim_comm_step", "tgsim_comm_launch", "tgsim_comm_finish", "tgsim_comm_run", "tgsim_comm_barrier", "tgsim_comm_info",
     "tgsim_bridge_create", "tgsim_bridge_destroy", "tgsim_bridge_send", "tgsim_bridge_step",
     "tgsim_bridge_recv", "tgsim_bridge_pending", "tgsim_bridge_in_flight", "tgsim_bridge_now_tick",
@@ -219,6 +241,10 @@ def declare(lib: C.CDLL, prefix: str) -> None:
     f("gossip_reached", C.c_int64, vp, C.c_void_p, C.c_size_t)
     f("gossip_spread", C.c_int64, vp, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t)
     f("gossip_times", C.c_int64, vp, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t)
+    f("ping_init", C.c_int, vp, C.POINTER(Ping), C.c_void_p)
+    f("gen_ping", C.c_int, vp, C.c_uint32)
+    f("ping_report", C.c_int64, vp, C.POINTER(PingSummary), C.c_void_p, C.c_size_t)
+    f("ping_pairs", C.c_int64, vp, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t)
     f("offered", C.c_int64, vp, C.c_void_p, C.c_size_t)
     f("metrics", C.c_int64, vp, C.c_uint32, C.c_void_p, C.c_size_t)
     f("comm_id", C.c_int, vp)

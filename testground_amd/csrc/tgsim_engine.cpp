@@ -449,6 +449,24 @@ struct tgsim_engine_s {
   DevBuf<uint64_t> d_gspread;  // tgsim_gossip_spread's result tables, kSpreadReplicas x 64 x (n_bins + 3) words
   DevBuf<uint32_t> d_gtimes;   // tgsim_gossip_times' rows
 
+  // ping mesh driver (tgsim_ping_*)
+  bool ping_on = false;
+  bool ping_late = false;        // sticky until tgsim_ping_init: a calendar entry preceded a generated window
+  uint64_t ping_late_tick = 0;
+  tgsim_ping ping{};
+  uint64_t ping_pairs = 0;       // non-empty slots
+  uint32_t ping_cur = 0;         // the calendar buffer being appended to
+  uint64_t ping_kept = 0;        // its entries behind the last generation (those not yet due then)
+  uint64_t ping_appended = 0;    // entries made since tgsim_ping_init, as of the last generation
+  DevBuf<uint32_t> d_ptgt, d_pslots, d_pcur;
+  DevBuf<tgsim_ping_pair> d_ppair, d_prows;
+  DevBuf<unsigned long long> d_phist, d_pctr, d_pres;
+  DevBuf<PingCal> d_pcal[2];
+  DevBuf<InRec> d_ptmp;          // a generated window's rows before the order pass
+  hipEvent_t ev_ping = nullptr;  // after the last k_ping_recv (delivery stream)
+  uint64_t* h_ppub = nullptr;    // pinned: the driver's counters as of the last generation, then a sequence word
+  uint64_t* dm_ppub = nullptr;
+
   int fail(int code, const char* fmt, ...) {
     char buf[512];
     va_list ap;
@@ -1405,6 +1423,56 @@ GossipArgs gossip_args(Eng* E, uint64_t win0, uint32_t n_ticks) {
   return g;
 }
 
+// Ping mesh driver: probes per slot whose tick precedes t (the schedule's closed form).
+uint32_t ping_probes_before(const tgsim_ping& p, uint64_t t) {
+  if (t <= p.start_tick) return 0;
+  return static_cast<uint32_t>(std::min<uint64_t>(p.count, (t - p.start_tick - 1) / p.interval_ticks + 1));
+}
+
+void ping_release(Eng* E) {
+  E->d_ptgt.release(); E->d_pslots.release(); E->d_pcur.release(); E->d_ppair.release(); E->d_prows.release();
+  E->d_phist.release(); E->d_pctr.release(); E->d_pres.release(); E->d_pcal[0].release(); E->d_pcal[1].release();
+  E->d_ptmp.release();
+  E->ping_on = false;
+  E->ping_late = false;
+}
+
+PingArgs ping_args(Eng* E, uint64_t win0, uint32_t n_ticks) {
+  PingArgs a{};
+  a.targets = E->d_ptgt.p;
+  a.pairs = E->d_ppair.p;
+  a.hist = E->d_phist.p;
+  a.ctr = E->d_pctr.p;
+  a.cal = E->d_pcal[E->ping_cur].p;
+  a.cal_next = E->d_pcal[E->ping_cur ^ 1u].p;
+  a.cal_cap = std::min(E->d_pcal[0].cap, E->d_pcal[1].cap);
+  a.cal_cur = E->ping_cur;
+  a.n_peers = E->N;
+  a.fanout = E->ping.fanout;
+  a.count = E->ping.count;
+  a.interval = E->ping.interval_ticks;
+  a.len = E->ping.len;
+  a.n_bins = E->ping.n_bins;
+  a.start = E->ping.start_tick;
+  a.tick_ns = E->o.tick_ns;
+  a.bin_ns = E->ping.n_bins ? E->ping.bin_ns : 1;
+  a.win0 = win0;
+  a.n_ticks = n_ticks;
+  a.j_lo = ping_probes_before(E->ping, win0);
+  a.j_hi = ping_probes_before(E->ping, win0 + n_ticks);
+  a.sent = ping_probes_before(E->ping, E->now_tick);
+  return a;
+}
+
+// The receipts of one window's delivery-ordered records (off[nd] of them; n bounds the count), behind
+// its per-destination sort on the delivery stream; the next generation waits for ev_ping.
+int ping_recv(Eng* E, const tgsim_delivery* recs, const uint64_t* off, uint32_t nd, uint64_t n, hipStream_t sq) {
+  launch_ping_recv(ping_args(E, 0, 0), recs, off, nd, n, sq);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(E->ev_ping, sq));
+  return 0;
+}
+
 // Output of a delivery sort of n records: the drain buffer (grown, undrained tail compacted to the
 // front) or, with TGSIM_OPT_DISCARD_DELIVERIES, a scratch buffer.
 int delivery_out(Eng* E, uint64_t n, tgsim_delivery** out, hipStream_t sq) {
@@ -1517,6 +1585,10 @@ int deliver(Eng* E, const tgsim_delivery* in, uint64_t n, hipEvent_t wait, bool 
     launch_metrics_dst(dst, E->d_doff.p, nd, E->d_mdst.p, E->d_mhist.p, sq);
     HIPCHK(hipGetLastError());
   }
+  if (E->ping_on && n_win == 1) {
+    int prc = ping_recv(E, dst, E->d_doff.p, nd, n, sq);
+    if (prc) return prc;
+  }
   if (timed) {
     HIPCHK(hipEventRecord(dv1, sq));
     E->dv_pending.push_back({dv0, dv1, n_win});
@@ -1606,6 +1678,10 @@ int deliver_local_from(Eng* E, const EmitRead& emit, uint32_t* emit_n, uint64_t*
     launch_metrics_dst(dst, doff.p, nd, E->d_mdst.p, E->d_mhist.p, sq);
     HIPCHK(hipGetLastError());
   }
+  if (E->ping_on) {
+    int prc = ping_recv(E, dst, doff.p, nd, n, sq);
+    if (prc) return prc;
+  }
   if (timed) {
     HIPCHK(hipEventRecord(dv1, sq));
     E->dv_pending.push_back({dv0, dv1, 1u});
@@ -1635,7 +1711,7 @@ int deliver_local(Eng* E) {
 // dense windows on an engine that owns every peer, no host packets, no per-window diagnostics.
 bool fusable(Eng* E, uint32_t n_ticks, uint32_t g, bool routed = false) {
   if (g < 2 || (E->S != E->N && !routed) || !E->staged.empty() || E->gen_q.size() < g || E->metrics_on ||
-      E->gossip_on || E->sparse_mode == 1 || kSpw != 1)
+      E->gossip_on || E->ping_on || E->sparse_mode == 1 || kSpw != 1)
     return false;
   for (uint32_t i = 0; i < g; ++i)
     if (E->gen_q[i].ticks != n_ticks || E->gen_q[i].n < 64ull * E->S) return false;  // sparse windows
@@ -1877,6 +1953,7 @@ void engine_shard(void* e, uint32_t* begin, uint32_t* end) {
 }
 int engine_fail(void* e, int code, const char* msg) { return as_eng(e)->fail(code, "%s", msg); }
 void engine_persist_routed(void* e, uint32_t pct) { as_eng(e)->routed_pct = pct; }
+bool engine_ping_armed(void* e) { return as_eng(e)->ping_on; }
 const uint64_t* engine_route_counts_dev(void* e) {
   Eng* E = as_eng(e);
   return E->route_n && E->d_rsend.p ? E->d_rsend.p + 16 * E->route_head : nullptr;
@@ -2152,6 +2229,9 @@ void tgsim_destroy(void* e) {
   if (E->h_err) (void)hipHostFree(E->h_err);
   if (E->h_xerr) (void)hipHostFree(E->h_xerr);
   if (E->h_work) (void)hipHostFree(E->h_work);
+  ping_release(E);
+  if (E->h_ppub) (void)hipHostFree(E->h_ppub);
+  if (E->ev_ping) (void)hipEventDestroy(E->ev_ping);
   if (E->h_gerr) (void)hipHostFree(E->h_gerr);
   if (E->h_pub) (void)hipHostFree(E->h_pub);
   if (E->ev_gpub) (void)hipEventDestroy(E->ev_gpub);
@@ -2232,6 +2312,7 @@ int tgsim_submit(void* e, const tgsim_pkt* pkts, size_t n) {
   Eng* E = as_eng(e);
   if (!E || (!pkts && n)) return -EINVAL;
   if (!E->gen_q.empty()) return E->fail(-EBUSY, "generated traffic already pending for the next step");
+  if (E->ping_on) return E->fail(-EBUSY, "%s: the ping driver is armed (tgsim_ping_init(engine, NULL, NULL) disarms it)", "submit");
   for (size_t i = 0; i < n; ++i) {
     if (pkts[i].src < E->o.shard_begin || pkts[i].src >= E->o.shard_end)
       return E->fail(-EINVAL, "packet %zu: src %u not owned by this shard", i, pkts[i].src);
@@ -2247,6 +2328,7 @@ int tgsim_gen_storm(void* e, double lambda, uint32_t n_ticks) {
   Eng* E = as_eng(e);
   if (!E || !(lambda >= 0.0) || lambda > 4.0 || n_ticks == 0 || n_ticks > 65536) return -EINVAL;
   if (!E->staged.empty()) return E->fail(-EBUSY, "host packets already pending for the next step");
+  if (E->ping_on) return E->fail(-EBUSY, "%s: the ping driver is armed (tgsim_ping_init(engine, NULL, NULL) disarms it)", "gen_storm");
   HIPCHK(hipSetDevice(E->dev));
   GenArgsHost g;
   double p = std::exp(-lambda), F = p;
@@ -2289,6 +2371,7 @@ int tgsim_gossip_init(void* e, const tgsim_gossip* g) {
   if (!E || !g || g->n_floods == 0 || g->n_floods > 64 || g->degree == 0 || g->degree > 64 ||
       g->msg_len == 0 || g->msg_len > 65535 || E->N < 2)
     return -EINVAL;
+  if (E->ping_on) return E->fail(-EBUSY, "%s: the ping driver is armed (tgsim_ping_init(engine, NULL, NULL) disarms it)", "gossip_init");
   if (g->start_tick < E->now_tick + E->gen_q_ticks) return E->fail(-EINVAL, "gossip: start tick in the past");
   HIPCHK(hipSetDevice(E->dev));
   E->gossip = *g;
@@ -2475,6 +2558,221 @@ int64_t tgsim_gossip_times(void* e, uint32_t peer, uint32_t n, uint32_t* out, si
   return static_cast<int64_t>(words);
 }
 
+// Ping mesh driver (include/tgsim.h).
+// Both calendar buffers at `need` entries or more, the live one's entries kept.
+static int ping_grow_calendar(Eng* E, uint64_t need, uint64_t live) {
+  if (need <= std::min(E->d_pcal[0].cap, E->d_pcal[1].cap)) return 0;
+  HIPCHK(hipStreamSynchronize(E->st));
+  HIPCHK(hipStreamSynchronize(E->dst_st));
+  DevBuf<PingCal> nb;
+  HIPCHK(nb.ensure(need));
+  if (live)
+    HIPCHK(hipMemcpy(nb.p, E->d_pcal[E->ping_cur].p, sizeof(PingCal) * live, hipMemcpyDeviceToDevice));
+  E->d_pcal[E->ping_cur].release();
+  E->d_pcal[E->ping_cur] = nb;
+  E->d_pcal[E->ping_cur ^ 1u].release();  // (holds nothing between generations)
+  HIPCHK(E->d_pcal[E->ping_cur ^ 1u].ensure_exact(nb.cap));
+  return 0;
+}
+
+int tgsim_ping_init(void* e, const tgsim_ping* p, const uint32_t* targets) {
+  Eng* E = as_eng(e);
+  if (!E) return -EINVAL;
+  HIPCHK(hipSetDevice(E->dev));
+  if (!p) {  // disarm
+    if (targets) return E->fail(-EINVAL, "ping: a target table without parameters");
+    int rc = sync_stream(E);
+    if (rc) return rc;
+    ping_release(E);
+    return 0;
+  }
+  if (!targets) return E->fail(-EINVAL, "ping: no target table");
+  if (E->S != E->N)
+    return E->fail(-EINVAL, "ping: this engine owns peers [%u, %u) of %u (the driver needs one engine for every peer)",
+                   E->o.shard_begin, E->o.shard_end, E->N);
+  if (p->fanout == 0 || p->fanout > 64) return E->fail(-EINVAL, "ping: fanout %u outside 1..64", p->fanout);
+  if (p->count == 0 || p->count > 65535) return E->fail(-EINVAL, "ping: count %u outside 1..65535", p->count);
+  if (p->interval_ticks == 0) return E->fail(-EINVAL, "ping: interval_ticks 0");
+  if (p->len == 0 || p->len > 65535) return E->fail(-EINVAL, "ping: len %u outside 1..65535", p->len);
+  if (p->n_bins > kPingMaxBins) return E->fail(-EINVAL, "ping: n_bins %u above %u", p->n_bins, kPingMaxBins);
+  if (p->n_bins && p->bin_ns == 0) return E->fail(-EINVAL, "ping: bin_ns 0 with %u bins", p->n_bins);
+  if (E->gossip_on) return E->fail(-EBUSY, "ping: the gossip driver is armed");
+  if (!E->staged.empty()) return E->fail(-EBUSY, "ping: host packets are pending for the next step");
+  if (!E->gen_q.empty() || E->route_n) return E->fail(-EBUSY, "ping: generated windows or launched steps are pending");
+  if (p->start_tick < E->now_tick)
+    return E->fail(-EINVAL, "ping: start tick %llu in the past (now %llu)", static_cast<unsigned long long>(p->start_tick),
+                   static_cast<unsigned long long>(E->now_tick));
+  if (p->start_tick + static_cast<uint64_t>(p->count) * p->interval_ticks >= (1ull << 31))
+    return E->fail(-EINVAL, "ping: the schedule ends beyond tick 2^31");
+  const uint64_t n_slots = static_cast<uint64_t>(E->N) * p->fanout;
+  std::vector<uint32_t> slots(E->N, 0);
+  uint64_t pairs = 0;
+  for (uint64_t i = 0; i < n_slots; ++i) {
+    const uint32_t t = targets[i], s = static_cast<uint32_t>(i / p->fanout);
+    if (t == TGSIM_PING_NONE) continue;
+    if (t == s || (t != TGSIM_EXTERNAL && t >= E->N))
+      return E->fail(-EINVAL, "ping: targets[%u][%u] = %u is %s", s, static_cast<uint32_t>(i % p->fanout), t,
+                     t == s ? "the peer itself" : "out of range");
+    ++slots[s];
+    ++pairs;
+  }
+  int rc = sync_stream(E);  // a re-init: the last delivery's receipts may still run
+  if (rc) return rc;
+  if (!E->ev_ping) HIPCHK(hipEventCreateWithFlags(&E->ev_ping, hipEventDisableTiming));
+  if (!E->h_ppub) {
+    HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&E->h_ppub), (kPingPubWords + 1) * sizeof(uint64_t),
+                         hipHostMallocCoherent | hipHostMallocMapped));
+    memset(E->h_ppub, 0, (kPingPubWords + 1) * sizeof(uint64_t));
+    HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&E->dm_ppub), E->h_ppub, 0));
+  }
+  ping_release(E);
+  E->ping = *p;
+  E->ping_pairs = pairs;
+  E->ping_cur = 0;
+  E->ping_kept = 0;
+  E->ping_appended = 0;
+  HIPCHK(E->d_ptgt.ensure_exact(n_slots));
+  HIPCHK(E->d_pslots.ensure_exact(E->N));
+  HIPCHK(E->d_pcur.ensure_exact(E->N));
+  HIPCHK(E->d_ppair.ensure_exact(n_slots));
+  HIPCHK(E->d_phist.ensure_exact(static_cast<size_t>(kPingReplicas) * kPingMaxBins));
+  HIPCHK(E->d_pctr.ensure_exact(kPingCtrWords));
+  HIPCHK(E->d_pres.ensure_exact(8 + kPingMaxBins));
+  // one entry per pair to start with: a probe in flight per pair; tgsim_gen_ping grows it for more
+  HIPCHK(E->d_pcal[0].ensure_exact(std::max<uint64_t>(pairs, 1024)));
+  HIPCHK(E->d_pcal[1].ensure_exact(std::max<uint64_t>(pairs, 1024)));
+  HIPCHK(hipMemcpy(E->d_ptgt.p, targets, sizeof(uint32_t) * n_slots, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(E->d_pslots.p, slots.data(), sizeof(uint32_t) * E->N, hipMemcpyHostToDevice));
+  launch_ping_init(ping_args(E, 0, 0), E->st);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(E->st));
+  HIPCHK(hipEventRecord(E->ev_ping, E->dst_st));
+  E->ping_on = true;
+  return 0;
+}
+
+int tgsim_gen_ping(void* e, uint32_t n_ticks) {
+  Eng* E = as_eng(e);
+  if (!E || n_ticks == 0 || n_ticks > 65536) return -EINVAL;
+  if (!E->ping_on) return E->fail(-EINVAL, "ping: the driver is not armed (tgsim_ping_init)");
+  if (!E->staged.empty()) return E->fail(-EBUSY, "host packets already pending for the next step");
+  if (!E->gen_q.empty()) return E->fail(-EBUSY, "ping: a generated window is pending (one window at a time)");
+  if (E->ping_late)
+    return E->fail(-EINVAL, "ping: a reply due at tick %llu preceded an earlier window (tgsim_ping_init starts again)",
+                   static_cast<unsigned long long>(E->ping_late_tick));
+  const uint64_t win0 = E->now_tick, win1 = win0 + n_ticks;
+  if (win1 >= (1ull << 31)) return E->fail(-EOVERFLOW, "ping: the window ends beyond tick 2^31");
+  HIPCHK(hipSetDevice(E->dev));
+  HIPCHK(hipStreamWaitEvent(E->st, E->ev_ping, 0));  // the last delivery's receipts (delivery stream)
+  PingArgs a = ping_args(E, win0, n_ticks);
+  Eng::GenWindow w;  // a free window's offsets may still be read by a delivery
+  int rc = take_gen(E, &w);
+  if (rc) return rc;
+  HIPCHK(E->d_cnt.ensure(E->S));
+  launch_ping_count(a, E->d_pslots.p, E->d_cnt.p, E->d_pcur.p, a.cal_cap, E->st);
+  HIPCHK(hipGetLastError());
+  const uint64_t seq = ++E->pub_seq;
+  launch_publish_words(reinterpret_cast<const uint64_t*>(E->d_pctr.p), kPingPubWords, E->dm_ppub, seq, E->st);
+  HIPCHK(hipGetLastError());
+  uint64_t total = 0;
+  rc = scan_counts(E, E->d_cnt, w.off, E->d_blk, E->d_tot, E->S, &total);
+  if (!rc) rc = wait_published(E, &E->h_ppub[kPingPubWords], seq, E->ev_pub, "ping generation (counters)");
+  if (rc) {
+    (void)retire_gen(E, std::move(w));
+    return rc;
+  }
+  uint64_t c[kPingPubWords];
+  for (uint32_t i = 0; i < kPingPubWords; ++i) c[i] = __atomic_load_n(&E->h_ppub[i], __ATOMIC_ACQUIRE);
+  const uint64_t cal_n = c[E->ping_cur];
+  E->ping_appended += cal_n - E->ping_kept;  // what the deliveries since the last generation added
+  E->ping_kept = cal_n;
+  if (c[kPcOverflow]) {
+    (void)retire_gen(E, std::move(w));
+    return E->fail(-ENOSPC, "ping: %llu replies found the calendar full", static_cast<unsigned long long>(c[kPcOverflow]));
+  }
+  if (c[kPcLate] != ~0ull) {  // nothing was written: the calendar and the pair table stay as they are
+    (void)retire_gen(E, std::move(w));
+    E->ping_late = true;
+    E->ping_late_tick = c[kPcLate];
+    return E->fail(-EINVAL, "ping: a reply due at tick %llu precedes the window at tick %llu (a window longer than "
+                            "the lookahead, or a lookahead longer than the minimum netem delay)",
+                   static_cast<unsigned long long>(c[kPcLate]), static_cast<unsigned long long>(win0));
+  }
+  // the calendar until the next generation: what stays, plus a reply for every probe offered by the
+  // end of this window that has none yet
+  const uint64_t offered = E->ping_pairs * a.j_hi;
+  rc = ping_grow_calendar(E, cal_n + (offered > E->ping_appended ? offered - E->ping_appended : 0), cal_n);
+  if (!rc) rc = E->hip(w.in.ensure(total ? total : 1), "generated window");
+  if (!rc) rc = E->hip(E->d_ptmp.ensure(total ? total : 1), "generated window");
+  if (rc) {
+    (void)retire_gen(E, std::move(w));
+    return rc;
+  }
+  a = ping_args(E, win0, n_ticks);
+  launch_ping_write(a, w.off.p, E->d_pcur.p, E->d_ptmp.p, w.in.p, cal_n, E->st);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemsetAsync(E->d_pctr.p + E->ping_cur, 0, sizeof(unsigned long long), E->st));
+  E->ping_cur ^= 1u;
+  E->ping_kept = cal_n - (total - E->ping_pairs * (a.j_hi - a.j_lo));  // less the replies due in this window
+  w.n = total;
+  w.ticks = n_ticks;
+  E->gen_q_ticks += n_ticks;
+  E->gen_q.push_back(std::move(w));
+  return 0;
+}
+
+int64_t tgsim_ping_report(void* e, tgsim_ping_summary* out, uint64_t* hist, size_t hist_cap) {
+  Eng* E = as_eng(e);
+  if (!E) return -EINVAL;
+  if (!E->ping_on) return E->fail(-EINVAL, "ping_report: the ping driver is not armed (tgsim_ping_init)");
+  if (!out) return E->fail(-EINVAL, "ping_report: no summary buffer");
+  const uint32_t nb = E->ping.n_bins;
+  if (nb && (!hist || hist_cap < nb)) return E->fail(-EINVAL, "ping_report: %zu histogram words for %u bins", hist ? hist_cap : size_t{0}, nb);
+  HIPCHK(hipSetDevice(E->dev));
+  int rc = sync_stream(E);  // the receipts of the last delivery are folded on the delivery stream
+  if (rc) return rc;
+  launch_ping_report(ping_args(E, 0, 0), E->d_pres.p, E->st);
+  HIPCHK(hipGetLastError());
+  unsigned long long res[8 + kPingMaxBins], ctr[kPingCtrWords];
+  HIPCHK(hipMemcpyAsync(res, E->d_pres.p, sizeof(unsigned long long) * (8 + nb), hipMemcpyDeviceToHost, E->st));
+  HIPCHK(hipMemcpyAsync(ctr, E->d_pctr.p, sizeof ctr, hipMemcpyDeviceToHost, E->st));
+  HIPCHK(hipStreamSynchronize(E->st));
+  out->pairs = res[0];
+  out->sent = res[1];
+  out->received = res[2];
+  out->sum_ns = res[3];
+  out->min_ns = res[4];
+  out->max_ns = res[5];
+  out->pairs_all = res[6];
+  out->pairs_none = res[7];
+  out->dup_ignored = ctr[kPcDup];
+  out->corrupt_ignored = ctr[kPcCorrupt];
+  out->pending_replies = ctr[E->ping_cur];
+  for (uint32_t b = 0; b < nb; ++b) hist[b] = res[8 + b];
+  return nb;
+}
+
+int64_t tgsim_ping_pairs(void* e, uint32_t peer, uint32_t n, tgsim_ping_pair* out, size_t cap) {
+  Eng* E = as_eng(e);
+  if (!E) return -EINVAL;
+  if (!E->ping_on) return E->fail(-EINVAL, "ping_pairs: the ping driver is not armed (tgsim_ping_init)");
+  if (peer > E->N || n > E->N - peer)
+    return E->fail(-EINVAL, "ping_pairs: peers [%u, %llu) outside [0, %u)", peer, static_cast<unsigned long long>(peer) + n, E->N);
+  const size_t rows = static_cast<size_t>(n) * E->ping.fanout;
+  if (cap < rows) return E->fail(-ENOSPC, "ping_pairs: %zu rows for %zu", cap, rows);
+  if (rows && !out) return E->fail(-EINVAL, "ping_pairs: no output buffer");
+  HIPCHK(hipSetDevice(E->dev));
+  int rc = sync_stream(E);
+  if (rc) return rc;
+  if (!rows) return 0;
+  HIPCHK(E->d_prows.ensure(rows));
+  launch_ping_pairs(ping_args(E, 0, 0), static_cast<uint64_t>(peer) * E->ping.fanout, rows, E->d_prows.p, E->st);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(out, E->d_prows.p, sizeof(tgsim_ping_pair) * rows, hipMemcpyDeviceToHost, E->st));
+  HIPCHK(hipStreamSynchronize(E->st));
+  return static_cast<int64_t>(rows);
+}
+
 int64_t tgsim_sim_capacity(void* e) {
   Eng* E = as_eng(e);
   if (!E) return -EINVAL;
@@ -2496,6 +2794,7 @@ int tgsim_step_sim_launch(void* e, uint32_t n_ticks, uint32_t n_ranks, const uin
   if (!E || n_ticks == 0 || n_ranks == 0 || n_ranks > 8 || !bounds || (!d_out && out_cap)) return -EINVAL;
   if (bounds[0] != 0 || bounds[n_ranks] != E->N) return E->fail(-EINVAL, "rank bounds must cover [0, n_peers)");
   if (E->route_n == Eng::kRouteSlots) return E->fail(-EBUSY, "two launched steps are not finished yet");
+  if (E->ping_on) return E->fail(-EBUSY, "%s: the ping driver is armed (tgsim_ping_init(engine, NULL, NULL) disarms it)", "step_sim_launch");
   HIPCHK(hipSetDevice(E->dev));
   int rc = run_sim(E, n_ticks);
   if (rc) return rc;
@@ -2522,6 +2821,7 @@ int tgsim_step_sim_launch_slotted(void* e, uint32_t n_ticks, uint32_t n_ranks, c
   if (!E || n_ticks == 0 || n_ranks == 0 || n_ranks > 8 || !bounds || !d_out || slot_cap == 0) return -EINVAL;
   if (bounds[0] != 0 || bounds[n_ranks] != E->N) return E->fail(-EINVAL, "rank bounds must cover [0, n_peers)");
   if (E->route_n == Eng::kRouteSlots) return E->fail(-EBUSY, "two launched steps are not released yet");
+  if (E->ping_on) return E->fail(-EBUSY, "%s: the ping driver is armed (tgsim_ping_init(engine, NULL, NULL) disarms it)", "step_sim_launch_slotted");
   HIPCHK(hipSetDevice(E->dev));
   int rc = run_sim(E, n_ticks);
   if (rc) return rc;
@@ -2539,6 +2839,7 @@ int tgsim_step_sim_launch_slotted_n(void* e, uint32_t n_ticks, uint32_t n_win, u
     return tgsim_step_sim_launch_slotted(e, n_ticks, n_ranks, bounds, d_out, slot_cap, routed_event);
   if (bounds[0] != 0 || bounds[n_ranks] != E->N) return E->fail(-EINVAL, "rank bounds must cover [0, n_peers)");
   if (E->route_n == Eng::kRouteSlots) return E->fail(-EBUSY, "two launched steps are not released yet");
+  if (E->ping_on) return E->fail(-EBUSY, "%s: the ping driver is armed (tgsim_ping_init(engine, NULL, NULL) disarms it)", "step_sim_launch_slotted_n");
   HIPCHK(hipSetDevice(E->dev));
   if (!fusable(E, n_ticks, n_win, true))
     return E->fail(-EINVAL, "step_sim_launch_slotted_n: the next %u windows are not generated dense windows of %u ticks",

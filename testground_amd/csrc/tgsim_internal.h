@@ -315,6 +315,45 @@ struct GossipSpreadArgs {
   uint32_t bin_ticks, bin_rcp, n_bins;  // bin_rcp = fastmod_rcp(bin_ticks); n_bins 0: no histogram
 };
 
+// Ping mesh driver (tgsim_ping_*) of an engine that owns every peer.
+constexpr uint32_t kPingMaxBins = 256;
+constexpr uint32_t kPingReplicas = 8;  // RTT histogram tables the workgroups' flushes are spread over
+// A reply waiting for its tick (16 B): made by k_ping_recv from a delivered request, consumed by the
+// generation of the window that holds its tick.
+struct alignas(16) PingCal {
+  uint32_t tick;       // absolute tick at which `responder` offers the reply
+  uint32_t responder;  // the request's destination
+  uint32_t requester;  // the request's source
+  uint32_t seq;        // the request's sequence number
+};
+static_assert(sizeof(PingCal) == 16, "PingCal must stay 16 B");
+// The driver's counters (u64 words in device memory; the first kPingPubWords are published to the
+// host at every generation).
+enum PingCtr {
+  kPcCal0 = 0, kPcCal1 = 1,  // entries in calendar buffer 0 / 1
+  kPcDup = 2, kPcCorrupt = 3,  // records ignored for TGSIM_FLAG_DUP / TGSIM_FLAG_CORRUPT
+  kPcLate = 4,      // the earliest calendar tick that preceded a generated window (all-ones: none)
+  kPcOverflow = 5,  // entries that found the calendar full (never written)
+  kPingPubWords = 6,
+  kPingCtrWords = 8
+};
+struct PingArgs {
+  const uint32_t* targets;   // [n_peers][fanout]
+  tgsim_ping_pair* pairs;    // [n_peers][fanout]; `sent` is filled in by the readers
+  unsigned long long* hist;  // [kPingReplicas][kPingMaxBins]
+  unsigned long long* ctr;   // [kPingCtrWords]
+  PingCal* cal;              // the calendar being appended to / read
+  PingCal* cal_next;         // generation: the entries not yet due move here
+  uint64_t cal_cap;          // entries either calendar buffer holds
+  uint32_t cal_cur;          // 0 / 1: which counter belongs to `cal`
+  uint32_t n_peers, fanout, count, interval, len, n_bins;
+  uint64_t start, tick_ns, bin_ns;
+  // generation of the window [win0, win0 + n_ticks): its scheduled probes are j_lo <= j < j_hi
+  uint64_t win0;
+  uint32_t n_ticks, j_lo, j_hi;
+  uint32_t sent;             // reports: probes per slot offered so far
+};
+
 // Engine hooks of the RCCL exchange layer (tgsim_comm.cpp), which drives the engine through the
 // public ABI and keeps its own state in the engine's comm slot (freed by tgsim_destroy).
 struct CommSlot {
@@ -329,6 +368,8 @@ int engine_fail(void* engine, int code, const char* msg);
 // Grid of a sharded fused group: 0 = one workgroup per ticket,
 // else a persistent grid of pct % of the resident workgroups.
 void engine_persist_routed(void* engine, uint32_t pct);
+// The ping mesh driver is armed (tgsim_ping_init): the exchange's steps refuse with -EBUSY.
+bool engine_ping_armed(void* engine);
 // Records `ev` on the routing stream after every routing enqueued so far (the exchange of a launched
 // window waits for it on the device, not only for the host's view of the published edges).
 int engine_record_routed(void* engine, hipEvent_t ev);

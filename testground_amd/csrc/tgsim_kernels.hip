@@ -3106,6 +3106,330 @@ __global__ __launch_bounds__(256) void k_gossip_times(const uint32_t* __restrict
 }
 
 // ---------------------------------------------------------------------------------------------
+// Ping mesh driver (tgsim_ping_*).
+//
+// k_ping_recv: one pass over a window's delivery-ordered records (n = off[n_dst], read here: the host
+// knows only a bound).  A request becomes a calendar entry; a reply credits its pair (a pair sees at
+// most `count` of these atomics in a whole run) and the workgroup's RTT histogram in LDS, flushed to
+// replica blockIdx mod kPingReplicas.  A workgroup takes tiles of 1,024 records and claims the
+// calendar slots of a tile with ONE atomic (wave scan, then the four wave totals through LDS): adds
+// to one address serialize at ~12 ns each, and one per wavefront (50,000 a window at 100,000 peers,
+// fanout 8) made this pass 1.25 ms long; one per tile makes it 3,100.
+constexpr uint32_t kPingRecvItems = 4;
+__global__ __launch_bounds__(256) void k_ping_recv(PingArgs a, const tgsim_delivery* __restrict__ recs,
+                                                   const uint64_t* __restrict__ off, uint32_t n_dst, uint64_t n_bound) {
+  __shared__ uint32_t hist[kPingMaxBins];
+  __shared__ uint32_t w_cnt[4];
+  __shared__ unsigned long long s_base;
+  for (uint32_t i = threadIdx.x; i < a.n_bins; i += 256) hist[i] = 0u;
+  __syncthreads();
+  const uint64_t n = off[n_dst] < n_bound ? off[n_dst] : n_bound;  // (never past the buffer the bound sized)
+  const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+  const uint64_t tile = 256 * kPingRecvItems;
+  const uint32_t n_req = a.count * a.fanout;  // (count <= 65535, fanout <= 64)
+  uint32_t dups = 0, cors = 0;
+  for (uint64_t base = blockIdx.x * tile; base < n; base += gridDim.x * tile) {  // (uniform in the workgroup)
+    PingCal e[kPingRecvItems];
+    bool request[kPingRecvItems];
+#pragma unroll
+    for (uint32_t u = 0; u < kPingRecvItems; ++u) {
+      const uint64_t i = base + u * 256 + threadIdx.x;
+      request[u] = false;
+      e[u] = PingCal{};
+      if (i >= n) continue;
+      const tgsim_delivery r = recs[i];
+      const uint32_t q = r.seq & 0x7FFFFFFFu, k = q % a.fanout, j = q / a.fanout;
+      if (r.flags & TGSIM_FLAG_DUP) {
+        ++dups;
+      } else if (r.flags & TGSIM_FLAG_CORRUPT) {
+        ++cors;
+      } else if (!(r.seq >> 31)) {
+        if (q < n_req && r.src < a.n_peers && a.targets[(uint64_t)r.src * a.fanout + k] == r.dst) {
+          request[u] = true;
+          e[u].tick = (uint32_t)(r.t_ns / a.tick_ns + 1);
+          e[u].responder = r.dst;
+          e[u].requester = r.src;
+          e[u].seq = r.seq;
+        }
+      } else if (j < a.count && r.dst < a.n_peers && a.targets[(uint64_t)r.dst * a.fanout + k] == r.src) {
+        const uint64_t t0 = (a.start + (uint64_t)j * a.interval) * a.tick_ns;
+        if (r.t_ns >= t0) {
+          const uint64_t rtt = r.t_ns - t0;
+          tgsim_ping_pair* p = a.pairs + (uint64_t)r.dst * a.fanout + k;
+          atomicAdd(&p->received, 1u);
+          atomicAdd(reinterpret_cast<unsigned long long*>(&p->sum_ns), (unsigned long long)rtt);
+          atomicMin(reinterpret_cast<unsigned long long*>(&p->min_ns), (unsigned long long)rtt);
+          atomicMax(reinterpret_cast<unsigned long long*>(&p->max_ns), (unsigned long long)rtt);
+          if (a.n_bins) {
+            const uint64_t b = rtt / a.bin_ns;
+            atomicAdd(&hist[b < a.n_bins ? (uint32_t)b : a.n_bins - 1], 1u);
+          }
+        }
+      }
+    }
+    uint32_t c = 0;
+#pragma unroll
+    for (uint32_t u = 0; u < kPingRecvItems; ++u) c += request[u] ? 1u : 0u;
+    const uint32_t incl = (uint32_t)scan_sum_i32((int32_t)c);
+    const uint32_t w_tot = readlane32(incl, kWave - 1);
+    if (lane == 0) w_cnt[wv] = w_tot;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      const uint32_t tot = w_cnt[0] + w_cnt[1] + w_cnt[2] + w_cnt[3];
+      unsigned long long at = 0;
+      if (tot) {
+        at = atomicAdd(&a.ctr[a.cal_cur], (unsigned long long)tot);
+        if (at + tot > a.cal_cap) {  // (the host sizes the calendar for every probe in flight)
+          atomicAdd(&a.ctr[kPcOverflow], (unsigned long long)tot);
+          atomicAdd(&a.ctr[a.cal_cur], 0ull - tot);
+          at = ~0ull;
+        }
+      }
+      s_base = at;
+    }
+    __syncthreads();
+    if (c && s_base != ~0ull) {
+      uint64_t pos = s_base + (incl - c);
+      for (uint32_t w = 0; w < wv; ++w) pos += w_cnt[w];
+#pragma unroll
+      for (uint32_t u = 0; u < kPingRecvItems; ++u)
+        if (request[u]) a.cal[pos++] = e[u];
+    }
+    __syncthreads();  // (w_cnt and s_base are the next tile's)
+  }
+  const uint64_t td = wave_sum(dups), tc = wave_sum(cors);
+  if (lane == 0) {
+    if (td) atomicAdd(&a.ctr[kPcDup], (unsigned long long)td);
+    if (tc) atomicAdd(&a.ctr[kPcCorrupt], (unsigned long long)tc);
+  }
+  __syncthreads();
+  unsigned long long* rep = a.hist + (uint64_t)(blockIdx.x % kPingReplicas) * kPingMaxBins;
+  for (uint32_t i = threadIdx.x; i < a.n_bins; i += 256)
+    if (hist[i]) atomicAdd(&rep[i], (unsigned long long)hist[i]);
+}
+
+// Generation, count pass: the scheduled probes of the window (closed form: j_hi - j_lo probes on each
+// of the source's non-empty slots), which also start the source's row cursor ...
+__global__ __launch_bounds__(256) void k_ping_count_sched(PingArgs a, const uint32_t* __restrict__ n_slots,
+                                                          uint64_t* counts, uint32_t* cursor) {
+  const uint32_t s = blockIdx.x * 256 + threadIdx.x;
+  if (s >= a.n_peers) return;
+  const uint32_t c = n_slots[s] * (a.j_hi - a.j_lo);
+  counts[s] = c;
+  cursor[s] = c;
+}
+
+// ... and the calendar entries due in it, counted on their responder; an entry before the window is a
+// late receipt (kPcLate keeps the earliest such tick).
+__global__ __launch_bounds__(256) void k_ping_count_cal(PingArgs a, uint64_t* counts) {
+  const uint64_t n = a.ctr[a.cal_cur], win1 = a.win0 + a.n_ticks;
+  for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256) {
+    const PingCal e = a.cal[i];
+    if (e.tick < a.win0) atomicMin(&a.ctr[kPcLate], (unsigned long long)e.tick);
+    else if (e.tick < win1 && e.responder < a.n_peers) atomicAdd(reinterpret_cast<unsigned long long*>(&counts[e.responder]), 1ull);
+  }
+}
+
+// Generation, write pass: a wavefront per source, lane = slot; probe j of the k-th non-empty slot goes
+// to (j - j_lo) * n_slots + k of the source's row, which is the row's (tick, seq) order already.
+__global__ __launch_bounds__(256) void k_ping_write_sched(PingArgs a, const uint64_t* __restrict__ off, InRec* out) {
+  const uint32_t s = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
+  if (s >= a.n_peers) return;
+  const uint32_t tgt = lane < a.fanout ? a.targets[(uint64_t)s * a.fanout + lane] : TGSIM_PING_NONE;
+  const uint64_t m = __ballot(tgt != TGSIM_PING_NONE);
+  if (tgt == TGSIM_PING_NONE) return;
+  const uint32_t ns = (uint32_t)__popcll(m), rank = (uint32_t)__popcll(m & ((1ull << lane) - 1));
+  const uint64_t o = off[s];
+  for (uint32_t j = a.j_lo; j < a.j_hi; ++j) {
+    InRec rec;
+    rec.dst = tgt;
+    rec.seq = j * a.fanout + lane;
+    rec.tick = (uint32_t)(a.start + (uint64_t)j * a.interval - a.win0);
+    rec.len = a.len;
+    out[o + (uint64_t)(j - a.j_lo) * ns + rank] = rec;
+  }
+}
+
+// The calendar: an entry due in the window becomes a reply behind its responder's scheduled probes
+// (the cursor; the order pass sorts the row), an entry not yet due moves to the other buffer (one
+// atomic per workgroup and 256 entries, as in k_ping_recv).  Runs only when no entry is late.
+__global__ __launch_bounds__(256) void k_ping_write_cal(PingArgs a, const uint64_t* __restrict__ off, uint32_t* cursor,
+                                                        InRec* out) {
+  __shared__ uint32_t w_cnt[4];
+  __shared__ unsigned long long s_base;
+  const uint64_t n = a.ctr[a.cal_cur], win1 = a.win0 + a.n_ticks;
+  const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+  for (uint64_t base = (uint64_t)blockIdx.x * 256; base < n; base += (uint64_t)gridDim.x * 256) {
+    const uint64_t i = base + threadIdx.x;
+    bool keep = false;
+    PingCal e{};
+    if (i < n) {
+      e = a.cal[i];
+      keep = e.tick >= win1;
+      if (!keep && e.tick >= a.win0 && e.responder < a.n_peers) {
+        InRec rec;
+        rec.dst = e.requester;
+        rec.seq = 0x80000000u | e.seq;
+        rec.tick = (uint32_t)(e.tick - a.win0);
+        rec.len = a.len;
+        out[off[e.responder] + atomicAdd(&cursor[e.responder], 1u)] = rec;
+      }
+    }
+    const uint64_t m = __ballot(keep);
+    if (lane == 0) w_cnt[wv] = (uint32_t)__popcll(m);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      const uint32_t tot = w_cnt[0] + w_cnt[1] + w_cnt[2] + w_cnt[3];
+      s_base = tot ? atomicAdd(&a.ctr[a.cal_cur ^ 1u], (unsigned long long)tot) : 0ull;
+    }
+    __syncthreads();
+    if (keep) {  // (at most n <= cal_cap entries in all)
+      uint64_t pos = s_base + __popcll(m & ((1ull << lane) - 1));
+      for (uint32_t w = 0; w < wv; ++w) pos += w_cnt[w];
+      a.cal_next[pos] = e;
+    }
+    __syncthreads();  // (w_cnt and s_base are the next round's)
+  }
+}
+
+// Row order: a wavefront per source puts its row into (tick, seq, dst) order by counting, for each
+// entry, the entries before it (the keys are distinct; the index breaks a tie all the same, so the
+// ranks are a permutation).  A row of up to 64 entries is compared in LDS, one entry per lane; a longer
+// one (a hot responder) against the row in memory, a broadcast load per comparison.
+__global__ __launch_bounds__(256) void k_ping_order(const uint64_t* __restrict__ off, const InRec* __restrict__ in,
+                                                    InRec* __restrict__ out, uint32_t n_src) {
+  __shared__ uint64_t k_hi[4][kWave];
+  __shared__ uint32_t k_lo[4][kWave];
+  const uint32_t wv = threadIdx.x >> 6, lane = threadIdx.x & 63u, s = blockIdx.x * 4 + wv;
+  if (s >= n_src) return;
+  const uint64_t b = off[s];
+  const uint32_t n = (uint32_t)(off[s + 1] - b);
+  if (n <= kWave) {
+    InRec r{};
+    if (lane < n) {
+      r = in[b + lane];
+      k_hi[wv][lane] = (uint64_t)r.tick << 32 | r.seq;
+      k_lo[wv][lane] = r.dst;
+    }
+    wave_lds_sync();
+    if (lane < n) {
+      const uint64_t hi = (uint64_t)r.tick << 32 | r.seq;
+      uint32_t rank = 0;
+      for (uint32_t i = 0; i < n; ++i) {
+        const uint64_t h = k_hi[wv][i];
+        const uint32_t l = k_lo[wv][i];
+        rank += h < hi || (h == hi && (l < r.dst || (l == r.dst && i < lane)));
+      }
+      out[b + rank] = r;
+    }
+    return;
+  }
+  for (uint32_t x = lane; x < n; x += kWave) {
+    const InRec r = in[b + x];
+    const uint64_t hi = (uint64_t)r.tick << 32 | r.seq;
+    uint32_t rank = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+      const InRec o = in[b + i];
+      const uint64_t h = (uint64_t)o.tick << 32 | o.seq;
+      rank += h < hi || (h == hi && (o.dst < r.dst || (o.dst == r.dst && i < x)));
+    }
+    out[b + rank] = r;
+  }
+}
+
+// tgsim_ping_report.  res: [0] pairs [1] sent [2] received [3] sum [4] min [5] max [6] pairs_all
+// [7] pairs_none, then n_bins histogram words.  k_ping_report_init sets the neutral values and folds
+// the histogram replicas; k_ping_report is one pass over the [n_peers][fanout] pair table: a
+// workgroup reduces in LDS and ends with one set of atomics.
+constexpr uint32_t kPingResWords = 8;
+__device__ __forceinline__ uint64_t wave_min_max_u64(uint64_t v, bool want_max) {  // (every lane takes part)
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const uint32_t lo = __shfl_xor((uint32_t)v, o, 64);
+    const uint32_t hi = __shfl_xor((uint32_t)(v >> 32), o, 64);
+    const uint64_t x = ((uint64_t)hi << 32) | lo;
+    v = (want_max ? x > v : x < v) ? x : v;
+  }
+  return v;
+}
+__global__ __launch_bounds__(256) void k_ping_report_init(PingArgs a, unsigned long long* res) {
+  const uint32_t i = threadIdx.x;
+  if (i < kPingResWords) res[i] = i == 4 ? ~0ull : 0ull;
+  if (i < a.n_bins) {
+    unsigned long long v = 0;
+    for (uint32_t r = 0; r < kPingReplicas; ++r) v += a.hist[(uint64_t)r * kPingMaxBins + i];
+    res[kPingResWords + i] = v;
+  }
+}
+
+__global__ __launch_bounds__(256) void k_ping_report(PingArgs a, unsigned long long* res) {
+  __shared__ unsigned long long acc[kPingResWords];
+  if (threadIdx.x < kPingResWords) acc[threadIdx.x] = threadIdx.x == 4 ? ~0ull : 0ull;
+  __syncthreads();
+  const uint64_t n = (uint64_t)a.n_peers * a.fanout;
+  uint64_t pairs = 0, received = 0, sum = 0, mn = ~0ull, mx = 0, all = 0, none = 0;
+  for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256) {
+    if (a.targets[i] == TGSIM_PING_NONE) continue;
+    const tgsim_ping_pair p = a.pairs[i];
+    ++pairs;
+    received += p.received;
+    sum += p.sum_ns;
+    mn = p.min_ns < mn ? p.min_ns : mn;
+    mx = p.max_ns > mx ? p.max_ns : mx;
+    all += a.sent && p.received == a.sent;
+    none += a.sent && p.received == 0;
+  }
+  const uint64_t t_pairs = wave_sum(pairs), t_recv = wave_sum(received), t_sum = wave_sum(sum), t_all = wave_sum(all),
+                 t_none = wave_sum(none);
+  const uint64_t t_mn = wave_min_max_u64(mn, false), t_mx = wave_min_max_u64(mx, true);
+  if ((threadIdx.x & 63u) == 0) {
+    atomicAdd(&acc[0], (unsigned long long)t_pairs);
+    atomicAdd(&acc[2], (unsigned long long)t_recv);
+    atomicAdd(&acc[3], (unsigned long long)t_sum);
+    atomicMin(&acc[4], (unsigned long long)t_mn);
+    atomicMax(&acc[5], (unsigned long long)t_mx);
+    atomicAdd(&acc[6], (unsigned long long)t_all);
+    atomicAdd(&acc[7], (unsigned long long)t_none);
+  }
+  __syncthreads();
+  if (threadIdx.x == 0 && acc[0]) {
+    atomicAdd(&res[0], acc[0]);
+    atomicAdd(&res[1], acc[0] * a.sent);
+    atomicAdd(&res[2], acc[2]);
+    atomicAdd(&res[3], acc[3]);
+    atomicMin(&res[4], acc[4]);
+    atomicMax(&res[5], acc[5]);
+    atomicAdd(&res[6], acc[6]);
+    atomicAdd(&res[7], acc[7]);
+  }
+}
+
+// tgsim_ping_init: the pair table (no reply yet) and the histogram replicas.
+__global__ __launch_bounds__(256) void k_ping_init(PingArgs a) {
+  const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < (uint64_t)a.n_peers * a.fanout) {
+    tgsim_ping_pair p;
+    p.sent = 0;
+    p.received = 0;
+    p.sum_ns = 0;
+    p.min_ns = ~0ull;
+    p.max_ns = 0;
+    a.pairs[i] = p;
+  }
+  if (i < kPingReplicas * kPingMaxBins) a.hist[i] = 0ull;
+  if (i < kPingCtrWords) a.ctr[i] = i == kPcLate ? ~0ull : 0ull;
+}
+
+// tgsim_ping_pairs: rows [i0, i0 + n) of the pair table with `sent` filled in (an empty slot: 0).
+__global__ __launch_bounds__(256) void k_ping_pairs(PingArgs a, uint64_t i0, uint64_t n, tgsim_ping_pair* out) {
+  const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  tgsim_ping_pair p = a.pairs[i0 + i];
+  p.sent = a.targets[i0 + i] == TGSIM_PING_NONE ? 0u : a.sent;
+  out[i] = p;
+}
+
+// ---------------------------------------------------------------------------------------------
 // Exclusive scan (u64), three phases, 1024 elements per block.
 __device__ __forceinline__ uint64_t block_excl_scan(uint64_t v, uint64_t* sh, uint64_t& total) {
   const uint32_t t = threadIdx.x, lane = t & 63u, w = t >> 6;
@@ -4140,6 +4464,44 @@ void launch_gossip_spread(GossipSpreadArgs a, hipStream_t st) {
 void launch_gossip_times(const uint32_t* first, const uint64_t* fwd, uint32_t s0, uint32_t n, uint32_t n_floods,
                          uint32_t* out, hipStream_t st) {
   if (n) hipLaunchKernelGGL(k_gossip_times, dim3(n / 4 + (n % 4 ? 1u : 0u)), dim3(256), 0, st, first, fwd, s0, n, n_floods, out);
+}
+
+namespace {
+// Workgroups of a grid-stride pass over up to n items (the exact count is read on the device).
+uint32_t ping_grid(uint64_t n) { return (uint32_t)std::min<uint64_t>(std::max<uint64_t>((n + 255) / 256, 1), 2048); }
+}  // namespace
+
+void launch_ping_init(const PingArgs& a, hipStream_t st) {
+  const uint64_t n = std::max<uint64_t>((uint64_t)a.n_peers * a.fanout, kPingReplicas * kPingMaxBins);
+  hipLaunchKernelGGL(k_ping_init, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, a);
+}
+
+void launch_ping_recv(const PingArgs& a, const tgsim_delivery* recs, const uint64_t* off, uint32_t n_dst,
+                      uint64_t n_bound, hipStream_t st) {
+  hipLaunchKernelGGL(k_ping_recv, dim3(ping_grid(n_bound)), dim3(256), 0, st, a, recs, off, n_dst, n_bound);
+}
+
+void launch_ping_count(const PingArgs& a, const uint32_t* n_slots, uint64_t* counts, uint32_t* cursor,
+                       uint64_t cal_bound, hipStream_t st) {
+  hipLaunchKernelGGL(k_ping_count_sched, dim3((a.n_peers + 255) / 256), dim3(256), 0, st, a, n_slots, counts, cursor);
+  if (cal_bound) hipLaunchKernelGGL(k_ping_count_cal, dim3(ping_grid(cal_bound)), dim3(256), 0, st, a, counts);
+}
+
+void launch_ping_write(const PingArgs& a, const uint64_t* off, uint32_t* cursor, InRec* tmp, InRec* out,
+                       uint64_t cal_bound, hipStream_t st) {
+  if (a.j_hi > a.j_lo) hipLaunchKernelGGL(k_ping_write_sched, dim3((a.n_peers + 3) / 4), dim3(256), 0, st, a, off, tmp);
+  if (cal_bound) hipLaunchKernelGGL(k_ping_write_cal, dim3(ping_grid(cal_bound)), dim3(256), 0, st, a, off, cursor, tmp);
+  hipLaunchKernelGGL(k_ping_order, dim3((a.n_peers + 3) / 4), dim3(256), 0, st, off, tmp, out, a.n_peers);
+}
+
+void launch_ping_report(const PingArgs& a, unsigned long long* res, hipStream_t st) {
+  hipLaunchKernelGGL(k_ping_report_init, dim3(1), dim3(256), 0, st, a, res);
+  // (few workgroups: each ends with eight atomics on the same eight words, which serialize)
+  hipLaunchKernelGGL(k_ping_report, dim3(std::min(ping_grid((uint64_t)a.n_peers * a.fanout), 256u)), dim3(256), 0, st, a, res);
+}
+
+void launch_ping_pairs(const PingArgs& a, uint64_t i0, uint64_t n, tgsim_ping_pair* out, hipStream_t st) {
+  if (n) hipLaunchKernelGGL(k_ping_pairs, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, a, i0, n, out);
 }
 
 void launch_gossip(const GossipArgs& g, const tgsim_delivery* recs, uint64_t n, uint64_t* counts,

@@ -69,6 +69,21 @@ void launch_gossip_spread(GossipSpreadArgs a, hipStream_t st);
 // Forward ticks of local peers [s0, s0 + n), rows of n_floods words (unforwarded: 0xFFFFFFFF).
 void launch_gossip_times(const uint32_t* first, const uint64_t* fwd, uint32_t s0, uint32_t n, uint32_t n_floods,
                          uint32_t* out, hipStream_t st);
+// Ping mesh driver (tgsim_ping_*).  _init: the pair table, histogram replicas and counters.  _recv: the
+// receipts of a window's delivery-ordered records (off[n_dst] records; n_bound sizes the grid).
+// _count: per-source counts of the window (scheduled probes, which also start `cursor`, plus due
+// calendar entries; cal_bound: at least the calendar's size, 0: empty).  _write: the rows into tmp,
+// the entries not yet due into a.cal_next, then the rows in (tick, seq, dst) order into out.
+// _report: res = 8 summary words + n_bins histogram words.  _pairs: rows with `sent` filled in.
+void launch_ping_init(const PingArgs& a, hipStream_t st);
+void launch_ping_recv(const PingArgs& a, const tgsim_delivery* recs, const uint64_t* off, uint32_t n_dst,
+                      uint64_t n_bound, hipStream_t st);
+void launch_ping_count(const PingArgs& a, const uint32_t* n_slots, uint64_t* counts, uint32_t* cursor,
+                       uint64_t cal_bound, hipStream_t st);
+void launch_ping_write(const PingArgs& a, const uint64_t* off, uint32_t* cursor, InRec* tmp, InRec* out,
+                       uint64_t cal_bound, hipStream_t st);
+void launch_ping_report(const PingArgs& a, unsigned long long* res, hipStream_t st);
+void launch_ping_pairs(const PingArgs& a, uint64_t i0, uint64_t n, tgsim_ping_pair* out, hipStream_t st);
 // Exclusive scan of in[0..n) into out[0..n] (out[n] = total, also stored at *total when non-null);
 // pos (optional) receives a copy of out[0..n), the scatter cursors.
 // clear: the input counts, zeroed as they are read (the histogram free for its next window), or null

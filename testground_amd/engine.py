@@ -187,6 +187,49 @@ class CABIEngine:
         self._check(fn(self._h, peer, n, out.ctypes.data, len(out)), "gossip_times")
         return out.reshape(n, n_floods)
 
+    # -- ping mesh (tgsim_ping_*) ----------------------------------------------------------------
+    def ping_init(self, targets=None, count: int = 1, interval_ticks: int = 1, length: int = 64,
+                  start_tick: Optional[int] = None, bin_ns: int = 0, n_bins: int = 0) -> None:
+        """Arms the device ping driver: `targets` is [n_peers, fanout] (a peer id, abi.EXTERNAL or
+        abi.PING_NONE per slot); probe j of every slot is offered at start_tick + j * interval_ticks
+        (start_tick None: the engine's current tick).  ping_init(None) disarms it."""
+        fn = self._gossip_fn("ping_init")
+        if targets is None:
+            self._check(fn(self._h, None, None), "ping_init")
+            self._ping = None
+            return
+        t = np.ascontiguousarray(targets, dtype=np.uint32)
+        if t.ndim != 2 or t.shape[0] != self.n_peers:
+            raise ValueError(f"ping_init: targets must be [{self.n_peers}, fanout]")
+        p = abi.Ping(t.shape[1], count, interval_ticks, length,
+                     self.stats()["now_tick"] if start_tick is None else start_tick, bin_ns, n_bins, 0)
+        self._check(fn(self._h, C.byref(p), t.ctypes.data), "ping_init")
+        self._ping = p
+
+    def gen_ping(self, n_ticks: int) -> None:
+        self._check(self._gossip_fn("gen_ping")(self._h, n_ticks), "gen_ping")
+
+    def ping_report(self) -> dict:
+        """The summary over every pair (abi.PING_SUMMARY_FIELDS) and `hist` [n_bins], reduced on the
+        device (tgsim_ping_report)."""
+        fn = self._gossip_fn("ping_report")
+        s = abi.PingSummary()
+        hist = np.zeros(abi.PING_MAX_BINS, dtype=np.uint64)
+        n = self._check(fn(self._h, C.byref(s), hist.ctypes.data, len(hist)), "ping_report")
+        out = {k: int(getattr(s, k)) for k in abi.PING_SUMMARY_FIELDS}
+        out["hist"] = hist[:n].copy()
+        return out
+
+    def ping_pairs(self, peer: int = 0, n: Optional[int] = None) -> np.ndarray:
+        """[n, fanout] abi.PING_PAIR_DTYPE rows of peers [peer, peer + n) (tgsim_ping_pairs)."""
+        fn = self._gossip_fn("ping_pairs")
+        p = getattr(self, "_ping", None)
+        fanout = p.fanout if p is not None else 1  # (unarmed: the call says so)
+        n = self.n_peers - peer if n is None else n
+        out = np.zeros(n * fanout, dtype=abi.PING_PAIR_DTYPE)
+        self._check(fn(self._h, peer, n, out.ctypes.data, len(out)), "ping_pairs")
+        return out.reshape(n, fanout)
+
     def step(self, n_ticks: int) -> None:
         self._check(self._fn("step")(self._h, n_ticks), "step")
 

@@ -63,3 +63,26 @@ def gossip_lines(spread: Dict[str, np.ndarray], bin_ticks: int, plan: str, run: 
         out += [f"{meas},{tags},flood={f},bin={b * int(bin_ticks)} value={int(c)}i {ts_ns}"
                 for b, c in enumerate(row) if c]
     return out
+
+
+PING_METRICS = [("ping.pairs", "pairs"), ("ping.sent", "sent"), ("ping.received", "received"),
+                ("ping.rtt_sum_ns", "sum_ns"), ("ping.rtt_min_ns", "min_ns"), ("ping.rtt_max_ns", "max_ns"),
+                ("ping.pairs_all", "pairs_all"), ("ping.pairs_none", "pairs_none"),
+                ("ping.dup_ignored", "dup_ignored"), ("ping.corrupt_ignored", "corrupt_ignored"),
+                ("ping.pending_replies", "pending_replies")]
+
+
+def ping_lines(report: Dict, bin_ns: int, plan: str, run: str, ts_ns: int) -> List[str]:
+    """The ping mesh report (Engine.ping_report()) in the shape of lines(): one line per summary
+    field (the RTT minimum and maximum only once a reply has been counted) and one per non-zero RTT
+    histogram bin (tag `bin`: the bin's lower edge b * bin_ns in nanoseconds; the last bin holds
+    everything from its edge on)."""
+    tags = f"run={_escape(run)}"
+    out: List[str] = []
+    for name, key in PING_METRICS:
+        if key in ("min_ns", "max_ns") and not report["received"]:
+            continue
+        out.append(f"{_escape(f'results.{plan}.{name}')},{tags} value={int(report[key])}i {ts_ns}")
+    meas = _escape(f"results.{plan}.ping.rtt_hist")
+    out += [f"{meas},{tags},bin={b * int(bin_ns)} value={int(c)}i {ts_ns}" for b, c in enumerate(report["hist"]) if c]
+    return out

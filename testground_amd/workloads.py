@@ -189,6 +189,202 @@ def pingpong_round(eng, start_tick: int, seq0: int, pkt_len: int = 66, chunk: in
 
 
 # ---------------------------------------------------------------------------------------------
+# Ping mesh: C1, C2 and plans/verify as one closed loop.  The HIP engine runs it on the device
+# (tgsim_ping_init / tgsim_gen_ping, include/tgsim.h); PingModel is the same loop driven from the
+# host over any engine-shaped object, the model the device loop is compared with.
+def ping_targets_all(n: int) -> np.ndarray:
+    """[n, n - 1]: every peer probes every other peer, slot k of peer s -> k + (k >= s)."""
+    k = np.arange(n - 1, dtype=np.uint32)[None, :]
+    s = np.arange(n, dtype=np.uint32)[:, None]
+    return (k + (k >= s)).astype(np.uint32)
+
+
+def ping_targets_mesh(n: int, fanout: int, seed: int = SEED) -> np.ndarray:
+    """[n, fanout]: `fanout` distinct random peers other than the peer itself, per peer."""
+    if not 1 <= fanout <= n - 1:
+        raise ValueError("ping_targets_mesh: fanout must be in 1..n-1")
+    rng = np.random.default_rng(seed & 0xFFFFFFFF)
+    off = rng.integers(1, n, (n, fanout))  # target = (s + off) mod n, off in 1..n-1
+    while True:
+        srt = np.sort(off, axis=1)
+        rows = np.nonzero((srt[:, 1:] == srt[:, :-1]).any(axis=1))[0]
+        if not len(rows):
+            break
+        off[rows] = rng.integers(1, n, (len(rows), fanout))
+    return ((np.arange(n)[:, None] + off) % n).astype(np.uint32)
+
+
+def ping_probes_before(ping: Dict, tick: int) -> int:
+    """Probes per slot whose tick start + j * interval precedes `tick`."""
+    if tick <= ping["start_tick"]:
+        return 0
+    return min(ping["count"], (tick - ping["start_tick"] - 1) // ping["interval_ticks"] + 1)
+
+
+class PingLate(ValueError):
+    """A reply's tick precedes the window being generated (the engine's -EINVAL)."""
+
+
+class PingModel:
+    """The ping loop of include/tgsim.h driven from the host: submit / step / verdicts / drain per
+    window.  `ping` holds Engine.ping_init's keywords (count, interval_ticks, length, start_tick and,
+    optionally, bin_ns, n_bins)."""
+
+    def __init__(self, eng, ping: Dict, targets: np.ndarray):
+        self.eng = eng
+        self.ping = dict(bin_ns=0, n_bins=0, **{k: v for k, v in ping.items() if k not in ("bin_ns", "n_bins")})
+        self.ping.update({k: ping[k] for k in ("bin_ns", "n_bins") if k in ping})
+        self.targets = np.ascontiguousarray(targets, dtype=np.uint32)
+        self.n, self.fanout = self.targets.shape
+        self.now = eng.stats()["now_tick"]
+        self.tick_ns = eng.tick_ns
+        self.src, self.slot = np.nonzero(self.targets != abi.PING_NONE)  # row-major: (s, k) ascending
+        self.dst = self.targets[self.src, self.slot]
+        self.cal = np.zeros((0, 4), dtype=np.int64)  # tick, responder, requester, seq
+        self.received = np.zeros(self.n * self.fanout, dtype=np.uint32)
+        self.sum_ns = np.zeros(self.n * self.fanout, dtype=np.uint64)
+        self.min_ns = np.full(self.n * self.fanout, np.iinfo(np.uint64).max, dtype=np.uint64)
+        self.max_ns = np.zeros(self.n * self.fanout, dtype=np.uint64)
+        self.hist = np.zeros(self.ping["n_bins"], dtype=np.uint64)
+        self.dup_ignored = self.corrupt_ignored = 0
+        # what the run exercised (the tests' conditions): the most windows ahead a calendar entry has been
+        # due, the longest row, rows with equal (tick, seq), clones ignored per leg
+        self.carried_max = self.max_row = self.ties = self.dup_requests = self.dup_replies = 0
+        self.tie_sources: set = set()  # sources that offered two packets with equal (tick, seq)
+        self.windows = 0
+
+    def window_packets(self, window: int) -> np.ndarray:
+        """The window's offered packets in (src, tick, seq, dst) order; the due entries leave the calendar."""
+        p, win0, win1 = self.ping, self.now, self.now + window
+        j = np.arange(ping_probes_before(p, win0), ping_probes_before(p, win1), dtype=np.int64)
+        src = np.tile(self.src, len(j))
+        dst = np.tile(self.dst, len(j))
+        seq = (j[:, None] * self.fanout + self.slot[None, :]).ravel()
+        tick = np.repeat(p["start_tick"] + j * p["interval_ticks"], len(self.src))
+        if len(self.cal) and self.cal[:, 0].min() < win0:
+            raise PingLate(f"ping: a reply due at tick {int(self.cal[:, 0].min())} precedes the window at tick {win0}")
+        due = self.cal[:, 0] < win1
+        rep, self.cal = self.cal[due], self.cal[~due]
+        src = np.concatenate([src, rep[:, 1]])
+        dst = np.concatenate([dst.astype(np.int64), rep[:, 2]])
+        seq = np.concatenate([seq, rep[:, 3] | 0x80000000])
+        tick = np.concatenate([tick, rep[:, 0]])
+        order = np.lexsort((dst, seq, tick, src))
+        if len(order):
+            s_, t_, q_ = src[order], tick[order], seq[order]
+            self.max_row = max(self.max_row, int(np.bincount(s_).max()))
+            tie = (s_[1:] == s_[:-1]) & (t_[1:] == t_[:-1]) & (q_[1:] == q_[:-1])
+            self.ties += int(tie.sum())
+            self.tie_sources.update(np.unique(s_[1:][tie]).tolist())
+        pk = np.zeros(len(order), dtype=abi.PKT_DTYPE)
+        pk["src"], pk["dst"], pk["seq"] = src[order], dst[order], seq[order]
+        pk["len"], pk["tick"] = p["length"], tick[order] - win0
+        return pk
+
+    def receive(self, d: np.ndarray) -> None:
+        """Folds one window's drained records: requests into the calendar, replies into the pairs."""
+        p = self.ping
+        flags = d["flags"]
+        dup = (flags & abi.FLAG_DUP) != 0
+        cor = ~dup & ((flags & abi.FLAG_CORRUPT) != 0)
+        self.dup_ignored += int(dup.sum())
+        self.dup_replies += int((dup & ((d["seq"] >> 31) != 0)).sum())
+        self.dup_requests += int((dup & ((d["seq"] >> 31) == 0)).sum())
+        self.corrupt_ignored += int(cor.sum())
+        d = d[~dup & ~cor]
+        seq = d["seq"].astype(np.int64)
+        q = seq & 0x7FFFFFFF
+        k, j = q % self.fanout, q // self.fanout
+        src, dst = d["src"].astype(np.int64), d["dst"].astype(np.int64)
+        is_rep = (seq >> 31) != 0
+        tgt = self.targets.astype(np.int64)
+        req = ~is_rep & (q < p["count"] * self.fanout) & (src < self.n)
+        req[req] = tgt[src[req], k[req]] == dst[req]
+        new = np.stack([d["t_ns"][req].astype(np.int64) // self.tick_ns + 1, dst[req], src[req], seq[req]], axis=1)
+        self.cal = np.concatenate([self.cal, new.reshape(-1, 4)])
+        t0 = (p["start_tick"] + j * p["interval_ticks"]) * self.tick_ns
+        t = d["t_ns"].astype(np.int64)
+        rep = is_rep & (j < p["count"]) & (dst < self.n)
+        rep[rep] = (tgt[dst[rep], k[rep]] == src[rep]) & (t[rep] >= t0[rep])
+        idx = dst[rep] * self.fanout + k[rep]
+        rtt = (t[rep] - t0[rep]).astype(np.uint64)
+        np.add.at(self.received, idx, 1)
+        np.add.at(self.sum_ns, idx, rtt)
+        np.minimum.at(self.min_ns, idx, rtt)
+        np.maximum.at(self.max_ns, idx, rtt)
+        if p["n_bins"]:
+            np.add.at(self.hist, np.minimum(rtt // np.uint64(p["bin_ns"]), np.uint64(p["n_bins"] - 1)).astype(np.int64), 1)
+
+    def step(self, window: int) -> Tuple[np.ndarray, np.ndarray]:
+        pk = self.window_packets(window)
+        if len(pk):
+            self.eng.submit(pk)
+        self.eng.step(window)
+        self.now += window
+        v, d = self.eng.verdicts(), self.eng.drain()
+        self.receive(d)
+        self.windows += 1
+        if len(self.cal):  # 1: due in the next window; 2 and more: moved to the other calendar buffer first
+            self.carried_max = max(self.carried_max, int((self.cal[:, 0].max() - self.now) // window) + 1)
+        return v, d
+
+    def pairs(self) -> np.ndarray:
+        out = np.zeros((self.n, self.fanout), dtype=abi.PING_PAIR_DTYPE)
+        out["sent"] = np.where(self.targets != abi.PING_NONE, ping_probes_before(self.ping, self.now), 0)
+        for key in ("received", "sum_ns", "min_ns", "max_ns"):
+            out[key] = getattr(self, key).reshape(self.n, self.fanout)
+        return out
+
+    def report(self) -> Dict:
+        pr = self.pairs()[self.targets != abi.PING_NONE]
+        got = pr["received"] > 0
+        sent = pr["sent"] > 0
+        return {"pairs": len(pr), "sent": int(pr["sent"].sum(dtype=np.uint64)),
+                "received": int(pr["received"].sum(dtype=np.uint64)), "sum_ns": int(pr["sum_ns"].sum(dtype=np.uint64)),
+                "min_ns": int(pr["min_ns"][got].min()) if got.any() else int(np.iinfo(np.uint64).max),
+                "max_ns": int(pr["max_ns"].max()) if len(pr) else 0,
+                "pairs_all": int((sent & (pr["received"] == pr["sent"])).sum()),
+                "pairs_none": int((sent & ~got).sum()),
+                "dup_ignored": self.dup_ignored, "corrupt_ignored": self.corrupt_ignored,
+                "pending_replies": len(self.cal), "hist": self.hist.copy()}
+
+
+def ping_reference(eng, ping: Dict, targets: np.ndarray, n_windows: int, window: int, probe_at=(), before=None) -> Dict:
+    """The ping loop driven from the host over `eng` (submit / step / verdicts / drain): per-window
+    (verdicts, deliveries) under "windows", the final "pairs", "summary" (report fields and hist),
+    and under "probes" the (pairs, summary) after each window index in probe_at.  before(w) runs
+    ahead of window w (a reshape, a disconnect).  The model itself is under "model"."""
+    m = PingModel(eng, ping, targets)
+    out = {"windows": [], "probes": {}, "model": m}
+    for w in range(n_windows):
+        if before is not None:
+            before(w)
+        out["windows"].append(m.step(window))
+        if w in probe_at:
+            out["probes"][w] = (m.pairs(), m.report())
+    out["pairs"], out["summary"] = m.pairs(), m.report()
+    out["hist"] = out["summary"]["hist"]
+    return out
+
+
+def ping_run(eng, n_windows: int, window: int, collect: bool = False, probe_at=(), before=None) -> Dict:
+    """The device loop on an armed engine (Engine.ping_init): n_windows of gen_ping + step.  Nothing
+    reaches the host unless asked for: collect keeps each window's (verdicts, deliveries), probe_at
+    the (pairs, report) after those windows."""
+    out = {"windows": [], "probes": {}}
+    for w in range(n_windows):
+        if before is not None:
+            before(w)
+        eng.gen_ping(window)
+        eng.step(window)
+        if collect:
+            out["windows"].append((eng.verdicts(), eng.drain()))
+        if w in probe_at:
+            out["probes"][w] = (eng.ping_pairs(), eng.ping_report())
+    return out
+
+
+# ---------------------------------------------------------------------------------------------
 # C4: gossip flood.  The engine generates and consumes the traffic on the device
 # (tgsim_gossip_init / tgsim_gen_gossip); this module only shapes the peers and runs windows.
 GOSSIP_MIN_LAT = 5 * Millisecond
