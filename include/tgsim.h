@@ -467,6 +467,41 @@ int64_t tgsim_ping_report(void* engine, tgsim_ping_summary* out, uint64_t* hist,
  * returns the rows written, -ENOSPC when cap < n * fanout. */
 int64_t tgsim_ping_pairs(void* engine, uint32_t peer, uint32_t n, tgsim_ping_pair* out, size_t cap);
 
+/* ---- per-group traffic matrix (who offered what to whom, and what became of it) -------------- */
+/* Every peer belongs to one group (a region, a composition group); the engine folds each window's
+ * traffic into a matrix of (group of src, group of dst) cells on the device, whoever made the traffic
+ * (tgsim_submit, tgsim_gen_storm, the gossip and ping drivers, bridge datagrams), so no delivery and
+ * no per-instance table has to reach the host.  Words of a cell:
+ *    0      offered packets (originals), since arming or the last reset
+ *    1      offered bytes (len)
+ *    2..9   verdict counts 0..7: the low nibble of every verdict byte, plus the high nibble when it
+ *           is not TGSIM_V_NONE (the rule of TGSIM_METRICS_SRC columns 2..9)
+ *    10     delivered records
+ *    11     delivered bytes
+ *    12     delivered records with TGSIM_FLAG_DUP
+ *    13     delivered records with TGSIM_FLAG_CORRUPT
+ * Words 0..9 are counted at the source's shard when the window is simulated, words 10..13 at the
+ * destination's shard when a step emits the record (when tgsim_drain would show it).  A record purged
+ * as lost_in_flight, or flushed, is never delivered: word 2 can stay above word 10.  The column
+ * gd == n_groups is TGSIM_EXTERNAL (its words 10..13 are always 0).  The matrices of the shards of
+ * one run merge by plain sum.
+ * While armed, tgsim_step_n runs its windows one by one and tgsim_step_sim_launch_slotted_n returns
+ * -EINVAL (as with TGSIM_OPT_METRICS: nothing is folded inside a fused launch); unlike
+ * TGSIM_OPT_METRICS the report leaves the sparse windows' direct destination buckets on. */
+#define TGSIM_GROUP_MAX   64u   /* groups per run */
+#define TGSIM_GROUP_WORDS 14u
+/* Arms the report: group_of[n_peers] (every entry < n_groups, 1 <= n_groups <= TGSIM_GROUP_MAX), the same
+ * table on every shard.  Zeroes the matrix.  (engine, NULL, 0) disarms and frees.  Re-arming replaces
+ * the table and zeroes.  -EINVAL (with a tgsim_last_error text) for n_groups 0 or above
+ * TGSIM_GROUP_MAX, a NULL table with n_groups != 0, or an entry >= n_groups (the text names the
+ * peer); -EBUSY while launched steps, generated windows or host packets are pending. */
+int tgsim_groups_init(void* engine, const uint16_t* group_of, uint32_t n_groups);
+/* out[(gs * (n_groups + 1) + gd) * TGSIM_GROUP_WORDS + w]; column gd == n_groups is TGSIM_EXTERNAL.
+ * reset != 0 zeroes the matrix behind the copy, in stream order (interval series).  Returns the words
+ * written (n_groups * (n_groups + 1) * TGSIM_GROUP_WORDS); -ENOSPC when cap is smaller; -EINVAL ("not
+ * armed") on an engine without the report.  Synchronizes like tgsim_stats. */
+int64_t tgsim_group_matrix(void* engine, uint64_t* out, size_t cap, int reset);
+
 /* ---- sync counters (sync-service SignalEntry / Barrier) ------------------------------------ */
 /* K7: TGSIM_SYNC_STATES u64 counters in device memory, incremented by a kernel on the engine's sync
  * stream (never behind a queued simulation) that also writes the new value into a pinned host

@@ -133,6 +133,14 @@ class PingSummary(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in PING_SUMMARY_FIELDS]
 
 
+# Per-group traffic matrix (tgsim_groups_init / tgsim_group_matrix): the words of a cell.
+GROUP_MAX = 64
+GROUP_WORDS = 14
+GROUP_NAMES = (["offered", "offered_bytes"] + VERDICT_NAMES
+               + ["delivered", "delivered_bytes", "delivered_dup", "delivered_corrupt"])
+assert len(GROUP_NAMES) == GROUP_WORDS
+
+
 class CommInfo(C.Structure):
     _fields_ = [("rank", C.c_int32), ("nranks", C.c_int32), ("exchanged_records", C.c_uint64),
                 ("max_rank_count", C.c_uint64), ("slot_cap", C.c_uint64), ("bounds", C.c_uint32 * 9),
@@ -171,6 +179,7 @@ EXPORTS = [
     "tgsim_gossip_init", "tgsim_gen_gossip", "tgsim_gossip_reached", "tgsim_gossip_spread",
     "tgsim_gossip_times", "tgsim_metrics",
     "tgsim_ping_init", "tgsim_gen_ping", "tgsim_ping_report", "tgsim_ping_pairs",
+    "tgsim_groups_init", "tgsim_group_matrix",
     "tgsim_comm_id", "tgsim_comm_init", "tgsim_comm_step", "tgsim_comm_launch", "tgsim_comm_finish", "tgsim_comm_run", "tgsim_comm_barrier", "tgsim_comm_info",
     "tgsim_bridge_create", "tgsim_bridge_destroy", "tgsim_bridge_send", "tgsim_bridge_step",
     "tgsim_bridge_recv", "tgsim_bridge_pending", "tgsim_bridge_in_flight", "tgsim_bridge_now_tick",
@@ -245,6 +254,8 @@ def declare(lib: C.CDLL, prefix: str) -> None:
     f("gen_ping", C.c_int, vp, C.c_uint32)
     f("ping_report", C.c_int64, vp, C.POINTER(PingSummary), C.c_void_p, C.c_size_t)
     f("ping_pairs", C.c_int64, vp, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t)
+    f("groups_init", C.c_int, vp, C.c_void_p, C.c_uint32)
+    f("group_matrix", C.c_int64, vp, C.c_void_p, C.c_size_t, C.c_int)
     f("offered", C.c_int64, vp, C.c_void_p, C.c_size_t)
     f("metrics", C.c_int64, vp, C.c_uint32, C.c_void_p, C.c_size_t)
     f("comm_id", C.c_int, vp)

@@ -467,6 +467,12 @@ struct tgsim_engine_s {
   uint64_t* h_ppub = nullptr;    // pinned: the driver's counters as of the last generation, then a sequence word
   uint64_t* dm_ppub = nullptr;
 
+  // per-group traffic matrix (tgsim_groups_init / tgsim_group_matrix)
+  bool groups_on = false;
+  uint32_t n_groups = 0;
+  DevBuf<uint16_t> d_gof;                   // group_of[N]
+  DevBuf<unsigned long long> d_gmat, d_gout;  // the matrix [G][G + 1][14] and the copy the host reads
+
   int fail(int code, const char* fmt, ...) {
     char buf[512];
     va_list ap;
@@ -1130,6 +1136,24 @@ uint32_t bucket_log(uint64_t n_in, uint32_t n_dst) {
   return l;
 }
 
+GroupArgs group_args(Eng* E) {
+  GroupArgs g{};
+  g.group_of = E->d_gof.p;
+  g.m = E->d_gmat.p;
+  g.n_groups = E->n_groups;
+  g.n_peers = E->N;
+  g.shard_begin = E->o.shard_begin;
+  return g;
+}
+
+void groups_release(Eng* E) {
+  E->d_gof.release();
+  E->d_gmat.release();
+  E->d_gout.release();
+  E->groups_on = false;
+  E->n_groups = 0;
+}
+
 int run_sim(Eng* E, uint32_t n_ticks, bool local_hist = false) {
   int erc = check_sim_error(E);
   if (erc) return erc;
@@ -1254,7 +1278,8 @@ int run_sim(Eng* E, uint32_t n_ticks, bool local_hist = false) {
   if (timed) {
     HIPCHK(hipEventRecord(ev1, E->st));
     E->ev_pending.push_back({ev0, ev1, 1u});
-    if (!E->metrics_on) E->ev_sim_t = ev1;  // (k_metrics_src follows k_sim on the stream)
+    if (!E->metrics_on) E->ev_sim_t = ev1;  // (k_metrics_src follows k_sim on the stream; so does k_group_src, which
+                                            // the delivery need not wait for: it reads no record)
   }
   if (sparse) {
     E->sparse_seen = true;
@@ -1272,6 +1297,14 @@ int run_sim(Eng* E, uint32_t n_ticks, bool local_hist = false) {
     m.src = E->d_msrc.p;
     m.hist = E->d_mhist.p;
     launch_metrics_src(m, E->st);
+    HIPCHK(hipGetLastError());
+  }
+  if (E->groups_on) {  // words 0..9 from the step's input and verdict bytes (never the emit records)
+    if (!E->ev_sim_t) {  // the delivery waits for k_sim, not for this fold
+      HIPCHK(hipEventRecord(E->ev_sim, E->st));
+      E->ev_sim_t = E->ev_sim;
+    }
+    launch_group_src(group_args(E), E->d_off.p, E->d_in.p, E->d_verdict.p, E->S, E->n_in, E->st);
     HIPCHK(hipGetLastError());
   }
   // (no heavy-first order kernel behind a single window: on the simulate stream it delayed the next
@@ -1589,6 +1622,10 @@ int deliver(Eng* E, const tgsim_delivery* in, uint64_t n, hipEvent_t wait, bool 
     int prc = ping_recv(E, dst, E->d_doff.p, nd, n, sq);
     if (prc) return prc;
   }
+  if (E->groups_on) {
+    launch_group_dst(group_args(E), dst, E->d_doff.p, nseg, nd, n, std::max<uint64_t>(E->n_in, 1), sq);
+    HIPCHK(hipGetLastError());
+  }
   if (timed) {
     HIPCHK(hipEventRecord(dv1, sq));
     E->dv_pending.push_back({dv0, dv1, n_win});
@@ -1682,6 +1719,10 @@ int deliver_local_from(Eng* E, const EmitRead& emit, uint32_t* emit_n, uint64_t*
     int prc = ping_recv(E, dst, doff.p, nd, n, sq);
     if (prc) return prc;
   }
+  if (E->groups_on) {
+    launch_group_dst(group_args(E), dst, doff.p, nd, nd, n, need_n ? n : n_in, sq);
+    HIPCHK(hipGetLastError());
+  }
   if (timed) {
     HIPCHK(hipEventRecord(dv1, sq));
     E->dv_pending.push_back({dv0, dv1, 1u});
@@ -1711,7 +1752,7 @@ int deliver_local(Eng* E) {
 // dense windows on an engine that owns every peer, no host packets, no per-window diagnostics.
 bool fusable(Eng* E, uint32_t n_ticks, uint32_t g, bool routed = false) {
   if (g < 2 || (E->S != E->N && !routed) || !E->staged.empty() || E->gen_q.size() < g || E->metrics_on ||
-      E->gossip_on || E->ping_on || E->sparse_mode == 1 || kSpw != 1)
+      E->gossip_on || E->ping_on || E->groups_on || E->sparse_mode == 1 || kSpw != 1)
     return false;
   for (uint32_t i = 0; i < g; ++i)
     if (E->gen_q[i].ticks != n_ticks || E->gen_q[i].n < 64ull * E->S) return false;  // sparse windows
@@ -2230,6 +2271,7 @@ void tgsim_destroy(void* e) {
   if (E->h_xerr) (void)hipHostFree(E->h_xerr);
   if (E->h_work) (void)hipHostFree(E->h_work);
   ping_release(E);
+  groups_release(E);
   if (E->h_ppub) (void)hipHostFree(E->h_ppub);
   if (E->ev_ping) (void)hipEventDestroy(E->ev_ping);
   if (E->h_gerr) (void)hipHostFree(E->h_gerr);
@@ -2771,6 +2813,57 @@ int64_t tgsim_ping_pairs(void* e, uint32_t peer, uint32_t n, tgsim_ping_pair* ou
   HIPCHK(hipMemcpyAsync(out, E->d_prows.p, sizeof(tgsim_ping_pair) * rows, hipMemcpyDeviceToHost, E->st));
   HIPCHK(hipStreamSynchronize(E->st));
   return static_cast<int64_t>(rows);
+}
+
+// Per-group traffic matrix (include/tgsim.h).
+int tgsim_groups_init(void* e, const uint16_t* group_of, uint32_t n_groups) {
+  Eng* E = as_eng(e);
+  if (!E) return -EINVAL;
+  if (!group_of && n_groups) return E->fail(-EINVAL, "groups: no group table for n_groups %u", n_groups);
+  if (group_of && (n_groups == 0 || n_groups > kGroupMax))
+    return E->fail(-EINVAL, "groups: n_groups %u outside 1..%u", n_groups, kGroupMax);
+  if (group_of)
+    for (uint32_t i = 0; i < E->N; ++i)
+      if (group_of[i] >= n_groups)
+        return E->fail(-EINVAL, "groups: group_of[%u] = %u is not below n_groups %u (peer %u)", i, group_of[i], n_groups, i);
+  if (E->route_n) return E->fail(-EBUSY, "groups: launched steps are pending (finish or release them first)");
+  if (!E->gen_q.empty()) return E->fail(-EBUSY, "groups: generated windows are pending");
+  if (!E->staged.empty()) return E->fail(-EBUSY, "groups: host packets are pending for the next step");
+  HIPCHK(hipSetDevice(E->dev));
+  int rc = sync_stream(E);  // the folds of the windows so far read the table and add to the matrix
+  if (rc) return rc;
+  if (!group_of) {
+    groups_release(E);
+    return 0;
+  }
+  const size_t words = static_cast<size_t>(n_groups) * (n_groups + 1) * kGroupWords;
+  E->groups_on = false;
+  HIPCHK(E->d_gof.ensure_exact(E->N));
+  HIPCHK(E->d_gmat.ensure_exact(words));
+  HIPCHK(E->d_gout.ensure_exact(words));
+  HIPCHK(hipMemcpy(E->d_gof.p, group_of, sizeof(uint16_t) * E->N, hipMemcpyHostToDevice));
+  HIPCHK(hipMemset(E->d_gmat.p, 0, sizeof(unsigned long long) * words));
+  E->n_groups = n_groups;
+  E->groups_on = true;
+  return 0;
+}
+
+int64_t tgsim_group_matrix(void* e, uint64_t* out, size_t cap, int reset) {
+  Eng* E = as_eng(e);
+  if (!E) return -EINVAL;
+  if (!E->groups_on) return E->fail(-EINVAL, "group_matrix: the report is not armed (tgsim_groups_init)");
+  const size_t words = static_cast<size_t>(E->n_groups) * (E->n_groups + 1) * kGroupWords;
+  if (cap < words) return E->fail(-ENOSPC, "group_matrix: %zu words for %zu", cap, words);
+  if (!out) return E->fail(-EINVAL, "group_matrix: no output buffer");
+  HIPCHK(hipSetDevice(E->dev));
+  int rc = sync_stream(E);  // words 0..9 are folded on the simulate stream, 10..13 on the delivery stream
+  if (rc) return rc;
+  if ((rc = check_sim_error(E))) return rc;
+  launch_group_read(group_args(E), E->d_gout.p, reset != 0, E->st);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(out, E->d_gout.p, sizeof(uint64_t) * words, hipMemcpyDeviceToHost, E->st));
+  HIPCHK(hipStreamSynchronize(E->st));
+  return static_cast<int64_t>(words);
 }
 
 int64_t tgsim_sim_capacity(void* e) {

@@ -354,6 +354,18 @@ struct PingArgs {
   uint32_t sent;             // reports: probes per slot offered so far
 };
 
+// Per-group traffic matrix (tgsim_groups_init / tgsim_group_matrix).
+constexpr uint32_t kGroupWords = TGSIM_GROUP_WORDS, kGroupMax = TGSIM_GROUP_MAX;
+// Up to kGroupFull groups a workgroup keeps the whole matrix in LDS; above, each of its wavefronts one
+// row (k_group_src) or one column (k_group_dst) of it, the one its contiguous input is in.
+constexpr uint32_t kGroupFull = 16;
+constexpr uint32_t kGroupCells = kGroupFull * (kGroupFull + 1);  // LDS cells per workgroup
+struct GroupArgs {
+  const uint16_t* group_of;  // [n_peers], every entry < n_groups
+  unsigned long long* m;     // [n_groups][n_groups + 1][kGroupWords]
+  uint32_t n_groups, n_peers, shard_begin;
+};
+
 // Engine hooks of the RCCL exchange layer (tgsim_comm.cpp), which drives the engine through the
 // public ABI and keeps its own state in the engine's comm slot (freed by tgsim_destroy).
 struct CommSlot {

@@ -4288,6 +4288,201 @@ __global__ __launch_bounds__(256) void k_metrics_dst(const tgsim_delivery* recs,
 }
 
 // ---------------------------------------------------------------------------------------------
+// Per-group traffic matrix (tgsim_groups_init / tgsim_group_matrix).
+//
+// All traffic lands on at most 64 x 65 cells, so nothing is added to the matrix per packet: the cells
+// live in LDS, are fed with LDS adds and reach the matrix as u64 atomics on their non-zero words.
+// Every wavefront takes a contiguous range of the input (sources for k_group_src, destination
+// segments for k_group_dst) in passes of 64 / 2^lg ranges, 2^lg lanes to a range (2^lg about the
+// items a range holds: 64 for a storm's sources, 16 for a gossip window's, 1 for nearly idle ones).
+// Up to kGroupFull groups the cells are the whole matrix, shared by the workgroup's four wavefronts,
+// whatever the assignment of peers to groups (an interleaved one changes group at every source).
+// Above, each wavefront keeps the row (column) of the group its input is in and flushes it when that
+// group changes: contiguous groups change it n_groups times in all; a packet of another group than
+// the held one (the first lane of a pass decides which) goes to the matrix directly, where 17 x 18
+// cells and more spread the adds.
+// A flush takes each count with an LDS exchange, so any wavefront may flush the shared cells at any
+// time: what others add meanwhile stays for the next flush, and every wavefront flushes once more
+// after its last add.  Counts are u32 in LDS: a wavefront flushes before it has folded 2^27 items
+// since its last flush (four wavefronts share a count); bytes are u64 (ds_add_u64).
+template <uint32_t NC>
+struct GroupLds {
+  unsigned long long bytes[kGroupCells];
+  uint32_t cnt[kGroupCells][NC];
+};
+constexpr uint32_t kGroupRowStride = kGroupCells / 4;  // row form: the cells of one wavefront
+static_assert(kGroupRowStride >= kGroupMax + 1, "a wavefront's row must hold the widest matrix's");
+constexpr uint32_t kGroupChunkLog = 20;  // items a lane folds between two looks at the flush bound
+constexpr uint64_t kGroupFlushEvery = 1ull << 26;
+
+__device__ __forceinline__ void group_add(unsigned long long* p, unsigned long long v) {
+  if (v) atomicAdd(p, v);
+}
+
+// Words 0..9.  cnt[c][v]: originals with verdict v, cnt[c][8 + v]: clones with verdict v; offered =
+// the originals (every packet has one verdict), so a packet costs two LDS adds, three with a clone.
+__global__ __launch_bounds__(256) void k_group_src(GroupArgs g, const uint64_t* __restrict__ off,
+                                                   const InRec* __restrict__ in, const uint8_t* __restrict__ verdict,
+                                                   uint32_t n_src, uint32_t per_wave, uint32_t lg) {
+  __shared__ GroupLds<16> L;
+  {
+    uint32_t* z = reinterpret_cast<uint32_t*>(&L);
+    for (uint32_t i = threadIdx.x; i < sizeof(L) / 4; i += 256) z[i] = 0u;
+  }
+  __syncthreads();  // (the only workgroup barrier: every wavefront is still here)
+  const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+  const uint64_t w0 = ((uint64_t)blockIdx.x * 4 + wv) * per_wave;
+  if (w0 >= n_src) return;
+  const uint32_t s0 = (uint32_t)w0, s1 = (uint32_t)(w0 + per_wave < n_src ? w0 + per_wave : n_src);
+  const uint32_t G = g.n_groups, W = G + 1;
+  const bool full = G <= kGroupFull;
+  const uint32_t base = full ? 0u : wv * kGroupRowStride, n_cells = full ? G * W : W;
+  const uint32_t sub = lane >> lg, l = lane & ((1u << lg) - 1u), per_pass = kWave >> lg;
+  uint32_t cur = 0;  // (row form) the row this wavefront holds
+  uint64_t folded = 0;
+  auto flush = [&]() {
+    for (uint32_t c = lane; c < n_cells; c += kWave) {
+      unsigned long long* cell = g.m + (size_t)(full ? c : cur * W + c) * kGroupWords;
+      uint32_t sum = 0;
+#pragma unroll
+      for (uint32_t k = 0; k < 8; ++k) {
+        const uint32_t v = atomicExch(&L.cnt[base + c][k], 0u);
+        sum += v;
+        group_add(cell + 2 + k, (unsigned long long)v + atomicExch(&L.cnt[base + c][8 + k], 0u));
+      }
+      group_add(cell, sum);
+      group_add(cell + 1, atomicExch(&L.bytes[base + c], 0ull));
+    }
+    folded = 0;
+  };
+  auto add = [&](uint32_t gs, uint64_t i) {
+    const InRec r = in[i];
+    const uint32_t vb = verdict[i], vo = vb & 7u, vc = vb >> 4, len = r.len & 0xFFFFu;
+    const uint32_t gd = r.dst < g.n_peers ? g.group_of[r.dst] : G;  // (TGSIM_EXTERNAL: the last column)
+    if (full || gs == cur) {
+      const uint32_t c = base + (full ? gs * W + gd : gd);
+      atomicAdd(&L.bytes[c], (unsigned long long)len);
+      atomicAdd(&L.cnt[c][vo], 1u);
+      if (vc < 8u) atomicAdd(&L.cnt[c][8 + vc], 1u);
+    } else {
+      unsigned long long* cell = g.m + (size_t)(gs * W + gd) * kGroupWords;
+      atomicAdd(cell, 1ull);
+      atomicAdd(cell + 1, (unsigned long long)len);
+      atomicAdd(cell + 2 + vo, 1ull);
+      if (vc < 8u) atomicAdd(cell + 2 + vc, 1ull);
+    }
+  };
+  for (uint32_t t = s0; t < s1; t += per_pass) {
+    const uint32_t s = t + sub;
+    const bool have = s < s1;
+    const uint64_t b1 = have ? off[s + 1] : 0ull;
+    uint64_t i = (have ? off[s] : 0ull) + l;
+    const uint32_t gs = have ? g.group_of[g.shard_begin + s] : 0u;
+    const uint32_t first = readlane32(gs, 0);
+    if (!full && first != cur) {
+      flush();
+      cur = first;
+    }
+    for (;;) {
+      const uint64_t room = (uint64_t)1 << (kGroupChunkLog + lg);
+      const uint64_t stop = b1 > i && b1 - i > room ? i + room : b1;
+      for (; i < stop; i += 1u << lg) add(gs, i);
+      if (!__ballot(i < b1)) break;  // (wave-uniform; a range of more than 2^20 items per lane goes on)
+      flush();
+    }
+    const uint32_t te = t + per_pass < s1 ? t + per_pass : s1;
+    folded += off[te] - off[t];
+    if (folded >= kGroupFlushEvery) flush();
+  }
+  flush();
+}
+
+// Words 10..13 from the delivery-ordered records: segment sg holds destination sg % n_dst of this
+// shard.  cnt[c][0]: records, [1]: with TGSIM_FLAG_DUP, [2]: with TGSIM_FLAG_CORRUPT.  off[] holds the
+// exact counts; no record at or past n_bound (what the buffer was sized for) is read.
+__global__ __launch_bounds__(256) void k_group_dst(GroupArgs g, const tgsim_delivery* __restrict__ recs,
+                                                   const uint64_t* __restrict__ off, uint64_t n_seg, uint32_t n_dst,
+                                                   uint64_t n_bound, uint32_t per_wave, uint32_t lg) {
+  __shared__ GroupLds<3> L;
+  {
+    uint32_t* z = reinterpret_cast<uint32_t*>(&L);
+    for (uint32_t i = threadIdx.x; i < sizeof(L) / 4; i += 256) z[i] = 0u;
+  }
+  __syncthreads();  // (the only workgroup barrier: every wavefront is still here)
+  const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+  const uint64_t s0 = ((uint64_t)blockIdx.x * 4 + wv) * per_wave;
+  if (s0 >= n_seg) return;
+  const uint64_t s1 = s0 + per_wave < n_seg ? s0 + per_wave : n_seg;
+  const uint32_t G = g.n_groups, W = G + 1;
+  const bool full = G <= kGroupFull;
+  const uint32_t base = full ? 0u : wv * kGroupRowStride, n_cells = full ? G * W : G;
+  const uint32_t sub = lane >> lg, l = lane & ((1u << lg) - 1u), per_pass = kWave >> lg;
+  uint32_t cur = 0;  // (column form) the column this wavefront holds
+  uint64_t folded = 0;
+  auto flush = [&]() {
+    for (uint32_t c = lane; c < n_cells; c += kWave) {
+      unsigned long long* cell = g.m + (size_t)(full ? c : c * W + cur) * kGroupWords + 10;
+      group_add(cell, atomicExch(&L.cnt[base + c][0], 0u));
+      group_add(cell + 1, atomicExch(&L.bytes[base + c], 0ull));
+      group_add(cell + 2, atomicExch(&L.cnt[base + c][1], 0u));
+      group_add(cell + 3, atomicExch(&L.cnt[base + c][2], 0u));
+    }
+    folded = 0;
+  };
+  auto add = [&](uint32_t gd, uint64_t i) {
+    const tgsim_delivery r = recs[i];
+    if (r.src >= g.n_peers) return;
+    const uint32_t gs = g.group_of[r.src];
+    if (full || gd == cur) {
+      const uint32_t c = base + (full ? gs * W + gd : gs);
+      atomicAdd(&L.cnt[c][0], 1u);
+      atomicAdd(&L.bytes[c], (unsigned long long)r.len);
+      if (r.flags & TGSIM_FLAG_DUP) atomicAdd(&L.cnt[c][1], 1u);
+      if (r.flags & TGSIM_FLAG_CORRUPT) atomicAdd(&L.cnt[c][2], 1u);
+    } else {
+      unsigned long long* cell = g.m + (size_t)(gs * W + gd) * kGroupWords + 10;
+      atomicAdd(cell, 1ull);
+      atomicAdd(cell + 1, (unsigned long long)r.len);
+      if (r.flags & TGSIM_FLAG_DUP) atomicAdd(cell + 2, 1ull);
+      if (r.flags & TGSIM_FLAG_CORRUPT) atomicAdd(cell + 3, 1ull);
+    }
+  };
+  auto clamp = [&](uint64_t x) { return x < n_bound ? x : n_bound; };
+  for (uint64_t t = s0; t < s1; t += per_pass) {
+    const uint64_t sg = t + sub;
+    const bool have = sg < s1;
+    const uint64_t b1 = have ? clamp(off[sg + 1]) : 0ull;
+    uint64_t i = (have ? clamp(off[sg]) : 0ull) + l;
+    const uint32_t gd = have ? g.group_of[g.shard_begin + (uint32_t)(sg % n_dst)] : 0u;
+    const uint32_t first = readlane32(gd, 0);
+    if (!full && first != cur) {
+      flush();
+      cur = first;
+    }
+    for (;;) {
+      const uint64_t room = (uint64_t)1 << (kGroupChunkLog + lg);
+      const uint64_t stop = b1 > i && b1 - i > room ? i + room : b1;
+      for (; i < stop; i += 1u << lg) add(gd, i);
+      if (!__ballot(i < b1)) break;  // (wave-uniform)
+      flush();
+    }
+    const uint64_t te = t + per_pass < s1 ? t + per_pass : s1;
+    folded += clamp(off[te]) - clamp(off[t]);
+    if (folded >= kGroupFlushEvery) flush();
+  }
+  flush();
+}
+
+// tgsim_group_matrix: the copy the host reads, and the matrix zeroed behind it (reset).
+__global__ __launch_bounds__(256) void k_group_read(unsigned long long* m, unsigned long long* out, uint32_t words,
+                                                    uint32_t reset) {
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= words) return;
+  out[i] = m[i];
+  if (reset) m[i] = 0ull;
+}
+
+// ---------------------------------------------------------------------------------------------
 // Host-side launchers.
 
 void launch_sim(const SimArgs& a, uint32_t n_wg, hipStream_t st) {
@@ -4419,6 +4614,46 @@ void launch_metrics_src(const MetricsArgs& m, hipStream_t st) {
 void launch_metrics_dst(const tgsim_delivery* recs, const uint64_t* off, uint32_t n_dst, unsigned long long* dst,
                         unsigned long long* hist, hipStream_t st) {
   if (n_dst) hipLaunchKernelGGL(k_metrics_dst, dim3((n_dst + 3) / 4), dim3(256), 0, st, recs, off, n_dst, dst, hist);
+}
+
+namespace {
+// The group folds' grids: n ranges of the input holding n_items items in all.  2^lg lanes to a range
+// (about the items per range), 64 / 2^lg ranges to a pass, whole passes to a wavefront, and at most 512
+// workgroups (8 wavefronts per CU hide the dependent loads of a pass: offsets, records, group gather),
+// so that the flushes at the end of the kernel do not queue on the matrix (the 256-workgroup lesson of
+// k_ping_report, DESIGN §5.6: here 512 x the few cells a workgroup touched).
+struct GroupGrid {
+  uint32_t per_wave, grid, lg;
+};
+GroupGrid group_grid(uint64_t n, uint64_t n_items) {
+  GroupGrid r;
+  const uint64_t avg = n_items / n;
+  r.lg = avg < 2 ? 0u : avg < 8 ? 2u : avg < 48 ? 4u : 6u;
+  const uint64_t unit = kWave >> r.lg, units = (n + unit - 1) / unit;
+  const uint64_t waves = std::min<uint64_t>(units, 512 * 4);
+  r.per_wave = (uint32_t)((units + waves - 1) / waves * unit);
+  r.grid = (uint32_t)(((n + r.per_wave - 1) / r.per_wave + 3) / 4);
+  return r;
+}
+}  // namespace
+
+void launch_group_src(const GroupArgs& g, const uint64_t* off, const InRec* in, const uint8_t* verdict, uint32_t n_src,
+                      uint64_t n_in, hipStream_t st) {
+  if (!n_src || !n_in) return;
+  const GroupGrid r = group_grid(n_src, n_in);
+  hipLaunchKernelGGL(k_group_src, dim3(r.grid), dim3(256), 0, st, g, off, in, verdict, n_src, r.per_wave, r.lg);
+}
+
+void launch_group_dst(const GroupArgs& g, const tgsim_delivery* recs, const uint64_t* off, uint64_t n_seg,
+                      uint32_t n_dst, uint64_t n_bound, uint64_t n_hint, hipStream_t st) {
+  if (!n_seg || !n_dst || !n_bound) return;
+  const GroupGrid r = group_grid(n_seg, n_hint);
+  hipLaunchKernelGGL(k_group_dst, dim3(r.grid), dim3(256), 0, st, g, recs, off, n_seg, n_dst, n_bound, r.per_wave, r.lg);
+}
+
+void launch_group_read(const GroupArgs& g, unsigned long long* out, bool reset, hipStream_t st) {
+  const uint32_t words = g.n_groups * (g.n_groups + 1) * kGroupWords;
+  hipLaunchKernelGGL(k_group_read, dim3((words + 255) / 256), dim3(256), 0, st, g.m, out, words, reset ? 1u : 0u);
 }
 
 void launch_gossip_nbr(const GossipArgs& g, uint32_t* nbr, hipStream_t st) {

@@ -84,6 +84,16 @@ void launch_ping_write(const PingArgs& a, const uint64_t* off, uint32_t* cursor,
                        uint64_t cal_bound, hipStream_t st);
 void launch_ping_report(const PingArgs& a, unsigned long long* res, hipStream_t st);
 void launch_ping_pairs(const PingArgs& a, uint64_t i0, uint64_t n, tgsim_ping_pair* out, hipStream_t st);
+// Per-group traffic matrix (tgsim_group_matrix).  _src: words 0..9 from a window's input (off[n_src + 1],
+// in, verdict) behind its simulate kernel; n_in: the window's offered packets (picks the lanes per
+// source).  _dst: words 10..13 from delivery-ordered records, segment sg = off[sg] ..
+// off[sg + 1] holding destination sg % n_dst of this shard; no record at or past n_bound is read;
+// n_hint: about how many records.  _read: out = m, and m zeroed behind the copy when reset.
+void launch_group_src(const GroupArgs& g, const uint64_t* off, const InRec* in, const uint8_t* verdict, uint32_t n_src,
+                      uint64_t n_in, hipStream_t st);
+void launch_group_dst(const GroupArgs& g, const tgsim_delivery* recs, const uint64_t* off, uint64_t n_seg,
+                      uint32_t n_dst, uint64_t n_bound, uint64_t n_hint, hipStream_t st);
+void launch_group_read(const GroupArgs& g, unsigned long long* out, bool reset, hipStream_t st);
 // Exclusive scan of in[0..n) into out[0..n] (out[n] = total, also stored at *total when non-null);
 // pos (optional) receives a copy of out[0..n), the scatter cursors.
 // clear: the input counts, zeroed as they are read (the histogram free for its next window), or null

@@ -230,6 +230,37 @@ class CABIEngine:
         self._check(fn(self._h, peer, n, out.ctypes.data, len(out)), "ping_pairs")
         return out.reshape(n, fanout)
 
+    # -- per-group traffic matrix (tgsim_groups_init / tgsim_group_matrix) ------------------------
+    def groups_init(self, group_of=None, n_groups: Optional[int] = None) -> None:
+        """Arms the per-group traffic matrix: group_of[n_peers] names every peer's group (the same
+        table on every shard), n_groups defaults to max(group_of) + 1.  Zeroes the matrix;
+        groups_init(None) disarms it."""
+        fn = self._gossip_fn("groups_init")
+        if group_of is None:
+            self._check(fn(self._h, None, 0 if n_groups is None else n_groups), "groups_init")
+            self._n_groups = None
+            return
+        g = np.asarray(group_of)
+        if g.shape != (self.n_peers,):
+            raise ValueError(f"groups_init: group_of must be [{self.n_peers}]")
+        if len(g) and (g.min() < 0 or g.max() > 0xFFFF):
+            raise ValueError("groups_init: a group id outside 0..65535")
+        g = np.ascontiguousarray(g, dtype=np.uint16)
+        n_groups = int(g.max()) + 1 if n_groups is None else n_groups
+        self._check(fn(self._h, g.ctypes.data, n_groups), "groups_init")
+        self._n_groups = n_groups
+
+    def group_matrix(self, reset: bool = False) -> np.ndarray:
+        """[n_groups, n_groups + 1, 14] u64, cell (group of src, group of dst), the last column
+        abi.EXTERNAL, words abi.GROUP_NAMES, accumulated since arming or the last reset=True read
+        (tgsim_group_matrix).  The matrices of a run's shards merge by sum
+        (workloads.merge_group_matrices)."""
+        fn = self._gossip_fn("group_matrix")
+        g = getattr(self, "_n_groups", None) or 1  # (unarmed: the call says so)
+        out = np.zeros(g * (g + 1) * abi.GROUP_WORDS, dtype=np.uint64)
+        self._check(fn(self._h, out.ctypes.data, len(out), 1 if reset else 0), "group_matrix")
+        return out.reshape(g, g + 1, abi.GROUP_WORDS)
+
     def step(self, n_ticks: int) -> None:
         self._check(self._fn("step")(self._h, n_ticks), "step")
 

@@ -86,3 +86,22 @@ def ping_lines(report: Dict, bin_ns: int, plan: str, run: str, ts_ns: int) -> Li
     meas = _escape(f"results.{plan}.ping.rtt_hist")
     out += [f"{meas},{tags},bin={b * int(bin_ns)} value={int(c)}i {ts_ns}" for b, c in enumerate(report["hist"]) if c]
     return out
+
+
+def group_lines(m: np.ndarray, names, plan: str, run: str, ts_ns: int) -> List[str]:
+    """The per-group traffic matrix (Engine.group_matrix(), or workloads.merge_group_matrices of the
+    shards') in the shape of lines(): one line per non-zero word of every cell, measurement
+    `results.<plan>.group.<word name>` (abi.GROUP_NAMES), tags `run`, `src_group` and `dst_group`
+    (names[g]; `external` for the last column)."""
+    m = np.asarray(m)
+    g = m.shape[0]
+    if m.shape != (g, g + 1, abi.GROUP_WORDS) or len(names) != g:
+        raise ValueError("group_lines: m must be [G, G + 1, 14] with one name per group")
+    tags = f"run={_escape(run)}"
+    col = [_escape(str(n)) for n in names] + ["external"]
+    out: List[str] = []
+    for w, name in enumerate(abi.GROUP_NAMES):
+        meas = _escape(f"results.{plan}.group.{name}")
+        out += [f"{meas},{tags},src_group={col[a]},dst_group={col[b]} value={int(m[a, b, w])}i {ts_ns}"
+                for a in range(g) for b in range(g + 1) if m[a, b, w]]
+    return out

@@ -385,6 +385,68 @@ def ping_run(eng, n_windows: int, window: int, collect: bool = False, probe_at=(
 
 
 # ---------------------------------------------------------------------------------------------
+# Per-group traffic matrix (tgsim_groups_init / tgsim_group_matrix, include/tgsim.h): the host model
+# the device's folds are compared with, in numpy: the word definitions and nothing cleverer.
+class GroupMatrix:
+    """m[gs, gd, w]: cell (group of src, group of dst), column n_groups for abi.EXTERNAL, words
+    abi.GROUP_NAMES.  fold() adds one window: its offered packets (abi.PKT_DTYPE), their verdict bytes
+    (in the packets' order) and the records the step delivered (abi.DELIVERY_DTYPE)."""
+
+    def __init__(self, group_of, n_groups: int):
+        self.group_of = np.asarray(group_of, dtype=np.int64)
+        self.n_groups = int(n_groups)
+        if not 1 <= self.n_groups <= abi.GROUP_MAX:
+            raise ValueError(f"GroupMatrix: n_groups {n_groups} outside 1..{abi.GROUP_MAX}")
+        if len(self.group_of) and (self.group_of.min() < 0 or self.group_of.max() >= self.n_groups):
+            raise ValueError("GroupMatrix: a group id outside 0..n_groups-1")
+        self.m = np.zeros((self.n_groups, self.n_groups + 1, abi.GROUP_WORDS), dtype=np.uint64)
+
+    def _col(self, dst: np.ndarray) -> np.ndarray:
+        dst = dst.astype(np.int64)
+        ext = dst == abi.EXTERNAL
+        return np.where(ext, self.n_groups, self.group_of[np.where(ext, 0, dst)])
+
+    def fold(self, pkts=None, verdicts=None, drained=None) -> "GroupMatrix":
+        if pkts is not None and len(pkts):
+            v = np.asarray(verdicts, dtype=np.uint8)
+            if len(v) != len(pkts):
+                raise ValueError("GroupMatrix.fold: one verdict byte per offered packet")
+            gs, gd = self.group_of[pkts["src"].astype(np.int64)], self._col(pkts["dst"])
+            np.add.at(self.m[:, :, 0], (gs, gd), np.uint64(1))
+            np.add.at(self.m[:, :, 1], (gs, gd), pkts["len"].astype(np.uint64))
+            lo, hi = (v & 15).astype(np.int64), (v >> 4).astype(np.int64)
+            np.add.at(self.m, (gs, gd, 2 + lo), np.uint64(1))
+            clone = hi != abi.V_NONE
+            np.add.at(self.m, (gs[clone], gd[clone], 2 + hi[clone]), np.uint64(1))
+        if drained is not None and len(drained):
+            gs, gd = self.group_of[drained["src"].astype(np.int64)], self._col(drained["dst"])
+            np.add.at(self.m[:, :, 10], (gs, gd), np.uint64(1))
+            np.add.at(self.m[:, :, 11], (gs, gd), drained["len"].astype(np.uint64))
+            np.add.at(self.m[:, :, 12], (gs, gd), ((drained["flags"] & abi.FLAG_DUP) != 0).astype(np.uint64))
+            np.add.at(self.m[:, :, 13], (gs, gd), ((drained["flags"] & abi.FLAG_CORRUPT) != 0).astype(np.uint64))
+        return self
+
+
+def merge_group_matrices(ms) -> np.ndarray:
+    """The matrix of a whole run from its shards' Engine.group_matrix() results: the plain sum."""
+    ms = [np.asarray(m, dtype=np.uint64) for m in ms]
+    if not ms:
+        raise ValueError("merge_group_matrices: no matrices")
+    if any(m.shape != ms[0].shape for m in ms):
+        raise ValueError("merge_group_matrices: the shards' matrices differ in shape")
+    return np.sum(ms, axis=0, dtype=np.uint64)
+
+
+def group_reachability(m, round_trip: bool = False) -> np.ndarray:
+    """ok[gs, gd] = some record from group gs was delivered to group gd (word 10 > 0); [G, G], without
+    the external column, where nothing is ever delivered.  round_trip: both directions deliver, which
+    is what a request and its reply need (splitbrain's expectErrors, negated)."""
+    m = np.asarray(m)
+    ok = m[:, :m.shape[0], 10] > 0
+    return ok & ok.T if round_trip else ok
+
+
+# ---------------------------------------------------------------------------------------------
 # C4: gossip flood.  The engine generates and consumes the traffic on the device
 # (tgsim_gossip_init / tgsim_gen_gossip); this module only shapes the peers and runs windows.
 GOSSIP_MIN_LAT = 5 * Millisecond
