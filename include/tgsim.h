@@ -352,9 +352,10 @@ typedef struct {
 int tgsim_comm_info(void* engine, tgsim_comm_info_t* out);
 
 /* ---- gossip workload (C4) ------------------------------------------------------------------ */
-/* Arms the gossip driver: resets the per-peer receipt state of this shard and schedules the
- * floods whose origin it owns.  Requires lookahead_ns >= the window of every later step and
- * <= the minimum netem delay, so that a window's receipts are known before the next window. */
+/* Arms the gossip driver (-EBUSY while the ping or flow driver is armed): resets the per-peer receipt
+ * state of this shard and schedules the floods whose origin it owns.  Requires lookahead_ns >= the
+ * window of every later step and <= the minimum netem delay, so that a window's receipts are known
+ * before the next window. */
 int tgsim_gossip_init(void* engine, const tgsim_gossip* g);
 /* Generates the next n_ticks window of gossip traffic on the device (origins + forwards of the
  * receipts delivered so far), like tgsim_gen_storm.  The generation runs ahead of the host, so a
@@ -449,12 +450,12 @@ typedef struct {
 } tgsim_ping_summary;
 /* Arms the driver (targets: [n_peers][fanout]).  -EINVAL (with a tgsim_last_error text) for an
  * engine that does not own every peer, a bad field, a target that is the peer itself or out of range
- * (the text names the entry), or a start tick in the past; -EBUSY while the gossip driver is armed
+ * (the text names the entry), or a start tick in the past; -EBUSY while the gossip or flow driver is armed
  * or while host packets or generated windows are pending.  While armed, tgsim_submit,
  * tgsim_gen_storm, tgsim_gossip_init and the tgsim_step_sim* / tgsim_comm_* steps return -EBUSY and
  * tgsim_step_n runs its windows one by one.  tgsim_configure between windows is allowed: a purged or
  * disconnected leg simply never produces a receipt.  tgsim_ping_init(engine, NULL, NULL) disarms and
- * frees the state. */
+ * frees the state (a no-op when the ping driver is not armed, an armed flow driver included). */
 int tgsim_ping_init(void* engine, const tgsim_ping* p, const uint32_t* targets);
 /* Generates the next n_ticks window on the device, like tgsim_gen_storm: the scheduled probes and the
  * calendar's replies due in it; the entries not yet due stay in the calendar.  One window at a time
@@ -466,6 +467,110 @@ int64_t tgsim_ping_report(void* engine, tgsim_ping_summary* out, uint64_t* hist,
 /* The pair rows of peers [peer, peer + n), row-major [n][fanout] (an empty slot: sent 0, received 0);
  * returns the rows written, -ENOSPC when cap < n * fanout. */
 int64_t tgsim_ping_pairs(void* engine, uint32_t peer, uint32_t n, tgsim_ping_pair* out, size_t cap);
+
+/* ---- reliable transfers (windowed flows, per-segment ACKs and retransmission timers) --------- */
+/* "Send n_seg segments reliably from a to b" as a closed loop on the device: how
+ * long a transfer takes and what goodput it reaches on links with this latency, loss, bandwidth and
+ * netem queue limit.  It is NOT TCP: no handshake, no congestion control, no cumulative ACK.  A fixed
+ * window, a selective ACK per delivered segment, a retransmission timer per segment: the smallest
+ * protocol that completes under loss, saturates a link whose bandwidth-delay product the window
+ * covers, and is a pure function of the delivered records.
+ *
+ *   Table    flow f = {src, dst, n_seg, start_tick}, sorted by src (non-decreasing): a source's flows
+ *            are contiguous and a flow's slot is its rank among them, at most TGSIM_FLOW_SLOTS per
+ *            source.  dst is a peer other than src (not TGSIM_EXTERNAL), 1 <= n_seg <= 2^23,
+ *            start_tick >= the engine's next window; every tick the schedule can reach is < 2^31.
+ *   Seq      bit 31 ACK | bits 27..30 attempt | bits 23..26 slot | bits 0..22 segment.  The attempt is
+ *            in the key on purpose: Philox is keyed by (seed, src, dst, seq), so a retransmission
+ *            draws afresh.
+ *   Sender   per flow: base (lowest unacknowledged segment), next (lowest segment never released;
+ *            always min(base + window, n_seg)), an acked bitmap over [base, base + 64), per in-flight
+ *            segment a due tick and an attempt count, counters, done_ns.  At arming base = 0 and the
+ *            segments [0, min(window, n_seg)) are due at start_tick with attempt 0.
+ *   Offer    generating the window [T, T + n): every unacknowledged in-flight segment i of a live flow
+ *            with T <= due_i < T + n is offered as one packet src -> dst of seg_len bytes at tick
+ *            due_i, seq = attempt_i << 27 | slot << 23 | i; then due_i += rto_ticks, attempt_i += 1.
+ *            A segment that becomes due with attempt_i == max_attempts fails the flow: with F the
+ *            earliest such due tick of the flow in the window, segments due before F are still
+ *            offered, nothing is offered at or after F, and the flow is FAILED with fail_tick = F (by
+ *            tick, not by window: the result does not depend on the step length).  n > rto_ticks is
+ *            -EINVAL: a segment is offered at most once per window.
+ *   ACK      the receiver is stateless.  A delivered data record with neither TGSIM_FLAG_DUP nor
+ *            TGSIM_FLAG_CORRUPT, addressed to r, from q, whose slot is below q's flow count, whose
+ *            flow's dst == r and whose segment is < n_seg, makes r offer one packet r -> q of ack_len
+ *            bytes, seq = 0x80000000 | data seq, at tick floor(d / tick_ns) + 1 (d: the delivery time;
+ *            the ping reply rule).  Every delivered attempt is acknowledged.  Clones and corrupted
+ *            copies are ignored and counted on either leg (dup_ignored first, else corrupt_ignored).
+ *   Receipt  a flow's ACKs take effect in delivery order, (t_ns, src, seq) within the sender's
+ *            records.  An unflagged ACK delivered at d matches flow (its dst, its slot) when the slot
+ *            is valid, the flow's dst equals the ACK's src and the segment is < n_seg.  A matching
+ *            ACK is stale (counted in stale_acks, nothing else) when the flow is DONE or FAILED, or
+ *            seg < base, or seg >= next, or the segment is already acknowledged.  Otherwise the
+ *            segment is marked acknowledged; base advances over the acknowledged prefix; every
+ *            segment that enters [base, base + window) and is < n_seg is released with due =
+ *            floor(d / tick_ns) + 1, attempt 0; when base == n_seg the flow is DONE with done_ns = d.
+ *            Flow completion time (FCT) = done_ns - start_tick * tick_ns.  Records count when a step
+ *            emits them (when tgsim_drain would show them); traffic that matches no flow is neither
+ *            acknowledged nor credited.
+ *   Order    within one source's window the offered packets are ordered by (tick, seq, dst).
+ *   Loop     as for ping, every later window <= lookahead_ns <= the minimum netem delay.  A calendar
+ *            ACK, or a released segment, whose tick precedes the window being generated is a late
+ *            receipt: tgsim_gen_flow fails with -EINVAL (tgsim_last_error names the tick), nothing is
+ *            generated, no flow state changes, and the error stays until the next tgsim_flow_init;
+ *            the reports stay readable.
+ *   Verdicts the sender learns nothing from them: a filtered, lost or queue-full segment is recovered
+ *            by its timer only.
+ * Single engine only (it must own every peer), as for ping. */
+#define TGSIM_FLOW_SLOTS 16u
+enum tgsim_flow_state { TGSIM_FLOW_ACTIVE = 0, TGSIM_FLOW_DONE = 1, TGSIM_FLOW_FAILED = 2 };
+typedef struct {
+    uint32_t seg_len;      /* bytes on the wire of a data segment, 1..65535            */
+    uint32_t ack_len;      /* bytes on the wire of an ACK, 1..65535                    */
+    uint32_t window;       /* segments in flight, 1..64                                */
+    uint32_t rto_ticks;    /* retransmission timer, >= 1                               */
+    uint32_t max_attempts; /* offers per segment before the flow fails, 1..16          */
+    uint32_t n_bins;       /* FCT histogram, 0..256; the last bin collects everything beyond */
+    uint64_t bin_ns;       /* >= 1 when n_bins > 0                                     */
+} tgsim_flow;              /* 32 B */
+typedef struct {
+    uint32_t src, dst, n_seg, start_tick;
+} tgsim_flow_spec;         /* 16 B */
+typedef struct {           /* one flow; 32 B */
+    uint32_t state;        /* enum tgsim_flow_state                                    */
+    uint32_t acked;        /* segments acknowledged                                    */
+    uint32_t offered;      /* data packets offered                                     */
+    uint32_t retransmits;  /* of them, offers with attempt > 0                         */
+    uint32_t stale_acks;
+    uint32_t base;
+    uint64_t done_ns;      /* DONE: delivery time of the last ACK; FAILED: fail_tick * tick_ns; ACTIVE: 0 */
+} tgsim_flow_row;
+typedef struct {
+    uint64_t flows, done, failed, active;
+    uint64_t segs_acked, bytes_acked; /* bytes_acked = segs_acked * seg_len                    */
+    uint64_t data_offered, retransmits, stale_acks;
+    uint64_t dup_ignored, corrupt_ignored; /* records skipped on either leg                    */
+    uint64_t pending_acks;            /* ACKs recorded but not yet offered (the calendar)      */
+    uint64_t fct_sum_ns, fct_min_ns /* UINT64_MAX when none */, fct_max_ns; /* over DONE flows */
+} tgsim_flow_summary;      /* 120 B */
+/* Arms the driver.  -EINVAL (with a tgsim_last_error text that names the entry) for an engine that
+ * does not own every peer, a bad field, an unsorted table, a 17th flow of a source, dst == src or out
+ * of range, or a start tick in the past; -EBUSY while the gossip or ping driver is armed or while host
+ * packets, generated windows or launched steps are pending.  While armed, tgsim_submit,
+ * tgsim_gen_storm, tgsim_gossip_init, tgsim_ping_init and the tgsim_step_sim* / tgsim_comm_* steps
+ * return -EBUSY, tgsim_step_n runs its windows one by one, and one generated window may be pending.
+ * tgsim_configure between windows is allowed; that is the point: reshape or partition a link
+ * mid-transfer.  tgsim_flow_init(engine, NULL, NULL, 0) disarms and frees the state. */
+int tgsim_flow_init(void* engine, const tgsim_flow* p, const tgsim_flow_spec* flows, uint64_t n_flows);
+/* Generates the next n_ticks window on the device, like tgsim_gen_ping: the segments due in it and the
+ * calendar's ACKs due in it.  One window at a time (-EBUSY while a generated window is pending). */
+int tgsim_gen_flow(void* engine, uint32_t n_ticks);
+/* The summary over every flow, reduced on the device, and (n_bins > 0) hist[b] = DONE flows with
+ * min(fct / bin_ns, n_bins - 1) == b; hist_cap >= n_bins.  Returns n_bins.  Synchronizes, and fails,
+ * like tgsim_ping_report. */
+int64_t tgsim_flow_report(void* engine, tgsim_flow_summary* out, uint64_t* hist, size_t hist_cap);
+/* The rows of flows [first, first + n) of the table; returns the rows written, -EINVAL for a range
+ * outside the table, -ENOSPC when cap < n (as tgsim_ping_pairs). */
+int64_t tgsim_flow_rows(void* engine, uint64_t first, uint64_t n, tgsim_flow_row* out, size_t cap);
 
 /* ---- per-group traffic matrix (who offered what to whom, and what became of it) -------------- */
 /* Every peer belongs to one group (a region, a composition group); the engine folds each window's

@@ -133,6 +133,29 @@ class PingSummary(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in PING_SUMMARY_FIELDS]
 
 
+# Flow driver (tgsim_flow_*): windowed transfers with per-segment ACKs and retransmission timers.
+FLOW_SLOTS = 16
+FLOW_ACTIVE, FLOW_DONE, FLOW_FAILED = 0, 1, 2
+FLOW_ACK, FLOW_ATTEMPT_SHIFT, FLOW_SLOT_SHIFT, FLOW_SEG_MASK = 0x80000000, 27, 23, 0x7FFFFF
+
+
+class Flow(C.Structure):
+    _fields_ = [("seg_len", C.c_uint32), ("ack_len", C.c_uint32), ("window", C.c_uint32), ("rto_ticks", C.c_uint32),
+                ("max_attempts", C.c_uint32), ("n_bins", C.c_uint32), ("bin_ns", C.c_uint64)]
+
+
+FLOW_SPEC_DTYPE = np.dtype([("src", "<u4"), ("dst", "<u4"), ("n_seg", "<u4"), ("start_tick", "<u4")])
+FLOW_ROW_DTYPE = np.dtype([("state", "<u4"), ("acked", "<u4"), ("offered", "<u4"), ("retransmits", "<u4"),
+                           ("stale_acks", "<u4"), ("base", "<u4"), ("done_ns", "<u8")])
+FLOW_SUMMARY_FIELDS = ("flows", "done", "failed", "active", "segs_acked", "bytes_acked", "data_offered", "retransmits",
+                       "stale_acks", "dup_ignored", "corrupt_ignored", "pending_acks", "fct_sum_ns", "fct_min_ns",
+                       "fct_max_ns")
+
+
+class FlowSummary(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in FLOW_SUMMARY_FIELDS]
+
+
 # Per-group traffic matrix (tgsim_groups_init / tgsim_group_matrix): the words of a cell.
 GROUP_MAX = 64
 GROUP_WORDS = 14
@@ -163,6 +186,8 @@ assert SHAPE_DTYPE.itemsize == 56 and CONFIG_DTYPE.itemsize == 104
 assert PKT_DTYPE.itemsize == 16 and DELIVERY_DTYPE.itemsize == 24
 assert C.sizeof(GossipFlood) == 24 and GOSSIP_FLOOD_DTYPE.itemsize == 24
 assert C.sizeof(Ping) == 40 and PING_PAIR_DTYPE.itemsize == 32 and C.sizeof(PingSummary) == 88
+assert C.sizeof(Flow) == 32 and FLOW_SPEC_DTYPE.itemsize == 16 and FLOW_ROW_DTYPE.itemsize == 32
+assert C.sizeof(FlowSummary) == 120
 assert C.sizeof(CommInfo) == 72 and C.sizeof(Gossip) == 24 and C.sizeof(Opts) == 56 and C.sizeof(Shape) == 56 and C.sizeof(Config) == 104
 
 # Every symbol include/tgsim.h declares (checked by tests/test_abi.py).
@@ -179,6 +204,7 @@ EXPORTS = [
     "tgsim_gossip_init", "tgsim_gen_gossip", "tgsim_gossip_reached", "tgsim_gossip_spread",
     "tgsim_gossip_times", "tgsim_metrics",
     "tgsim_ping_init", "tgsim_gen_ping", "tgsim_ping_report", "tgsim_ping_pairs",
+    "tgsim_flow_init", "tgsim_gen_flow", "tgsim_flow_report", "tgsim_flow_rows",
     "tgsim_groups_init", "tgsim_group_matrix",
     "tgsim_comm_id", "tgsim_comm_init", "tgsim_comm_step", "tgsim_comm_launch", "tgsim_comm_finish", "tgsim_comm_run", "tgsim_comm_barrier", "tgsim_comm_info",
     "tgsim_bridge_create", "tgsim_bridge_destroy", "tgsim_bridge_send", "tgsim_bridge_step",
@@ -254,6 +280,10 @@ def declare(lib: C.CDLL, prefix: str) -> None:
     f("gen_ping", C.c_int, vp, C.c_uint32)
     f("ping_report", C.c_int64, vp, C.POINTER(PingSummary), C.c_void_p, C.c_size_t)
     f("ping_pairs", C.c_int64, vp, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t)
+    f("flow_init", C.c_int, vp, C.POINTER(Flow), C.c_void_p, C.c_uint64)
+    f("gen_flow", C.c_int, vp, C.c_uint32)
+    f("flow_report", C.c_int64, vp, C.POINTER(FlowSummary), C.c_void_p, C.c_size_t)
+    f("flow_rows", C.c_int64, vp, C.c_uint64, C.c_uint64, C.c_void_p, C.c_size_t)
     f("groups_init", C.c_int, vp, C.c_void_p, C.c_uint32)
     f("group_matrix", C.c_int64, vp, C.c_void_p, C.c_size_t, C.c_int)
     f("offered", C.c_int64, vp, C.c_void_p, C.c_size_t)

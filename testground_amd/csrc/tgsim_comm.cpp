@@ -465,6 +465,7 @@ int tgsim_comm_launch(void* e, uint32_t n_ticks) {
   if (n_ticks == 0) return -EINVAL;
   if (C->launched) return engine_fail(e, -EBUSY, "comm_launch: the launched window is not finished (tgsim_comm_finish)");
   if (engine_ping_armed(e)) return engine_fail(e, -EBUSY, "comm_launch: the ping driver is armed (single engine, tgsim_step)");
+  if (engine_flow_armed(e)) return engine_fail(e, -EBUSY, "comm_launch: the flow driver is armed (single engine, tgsim_step)");
   CHIP(hipSetDevice(C->dev));
   if (C->local) {  // one rank owns every destination: nothing to route or move, so the window
                          // is the single-shard step with its asynchronous local delivery (the count
@@ -561,6 +562,7 @@ int tgsim_comm_run(void* e, uint32_t n_ticks, uint32_t n_steps, uint32_t fuse, u
   if (n_ticks == 0 || fuse == 0 || fuse > kFuseMax) return -EINVAL;
   if (C->launched) return engine_fail(e, -EBUSY, "comm_run: a launched window is not finished (tgsim_comm_finish)");
   if (engine_ping_armed(e)) return engine_fail(e, -EBUSY, "comm_run: the ping driver is armed (single engine, tgsim_step)");
+  if (engine_flow_armed(e)) return engine_fail(e, -EBUSY, "comm_run: the flow driver is armed (single engine, tgsim_step)");
   if (!n_steps) return 0;
   CHIP(hipSetDevice(C->dev));
   const int nr = C->nranks;

@@ -467,6 +467,22 @@ struct tgsim_engine_s {
   uint64_t* h_ppub = nullptr;    // pinned: the driver's counters as of the last generation, then a sequence word
   uint64_t* dm_ppub = nullptr;
 
+  // flow driver (tgsim_flow_*).  Never armed together with ping: its ACK calendar IS
+  // the ping calendar above (d_pcal, d_pctr, d_phist, d_pres, d_pcur, d_ptmp, ping_cur / ping_kept /
+  // ping_appended, h_ppub), grown by ping_grow_calendar.
+  bool flow_on = false;
+  bool flow_late = false;        // sticky until tgsim_flow_init
+  uint64_t flow_late_tick = 0;
+  tgsim_flow flow{};
+  uint64_t n_flows = 0;
+  uint64_t flow_offered = 0;     // data packets offered since tgsim_flow_init: each makes at most one calendar entry
+  DevBuf<tgsim_flow_spec> d_fspec;
+  DevBuf<tgsim_flow_row> d_frow;
+  DevBuf<uint64_t> d_fbits;
+  DevBuf<uint32_t> d_fdue, d_ffirst, d_fcnt;
+  DevBuf<uint8_t> d_fatt;
+  hipEvent_t ev_flow = nullptr;  // after the last k_flow_recv_ack (delivery stream)
+
   // per-group traffic matrix (tgsim_groups_init / tgsim_group_matrix)
   bool groups_on = false;
   uint32_t n_groups = 0;
@@ -1506,6 +1522,55 @@ int ping_recv(Eng* E, const tgsim_delivery* recs, const uint64_t* off, uint32_t 
   return 0;
 }
 
+// Flow driver: its own tables, and the calendar it shares with the (disarmed) ping driver.
+void flow_release(Eng* E) {
+  ping_release(E);
+  E->d_fspec.release(); E->d_frow.release(); E->d_fbits.release(); E->d_fdue.release(); E->d_ffirst.release();
+  E->d_fcnt.release(); E->d_fatt.release();
+  E->flow_on = false;
+  E->flow_late = false;
+}
+
+FlowArgs flow_args(Eng* E, uint64_t win0, uint32_t n_ticks) {
+  FlowArgs f{};
+  PingArgs& a = f.cal;
+  a.hist = E->d_phist.p;
+  a.ctr = E->d_pctr.p;
+  a.cal = E->d_pcal[E->ping_cur].p;
+  a.cal_next = E->d_pcal[E->ping_cur ^ 1u].p;
+  a.cal_cap = std::min(E->d_pcal[0].cap, E->d_pcal[1].cap);
+  a.cal_cur = E->ping_cur;
+  a.n_peers = E->N;
+  a.len = E->flow.ack_len;
+  a.n_bins = E->flow.n_bins;
+  a.tick_ns = E->o.tick_ns;
+  a.bin_ns = E->flow.n_bins ? E->flow.bin_ns : 1;
+  a.win0 = win0;
+  a.n_ticks = n_ticks;
+  f.spec = E->d_fspec.p;
+  f.rows = E->d_frow.p;
+  f.bitmap = E->d_fbits.p;
+  f.due = E->d_fdue.p;
+  f.att = E->d_fatt.p;
+  f.first = E->d_ffirst.p;
+  f.cnt = E->d_fcnt.p;
+  f.n_flows = E->n_flows;
+  f.seg_len = E->flow.seg_len;
+  f.window = E->flow.window;
+  f.rto = E->flow.rto_ticks;
+  f.max_attempts = E->flow.max_attempts;
+  return f;
+}
+
+// The flow receipts of one window's delivery-ordered records, where ping_recv would run; the next
+// generation waits for ev_flow.
+int flow_recv(Eng* E, const tgsim_delivery* recs, const uint64_t* off, uint32_t nd, uint64_t n, hipStream_t sq) {
+  launch_flow_recv(flow_args(E, 0, 0), recs, off, nd, n, sq);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(E->ev_flow, sq));
+  return 0;
+}
+
 // Output of a delivery sort of n records: the drain buffer (grown, undrained tail compacted to the
 // front) or, with TGSIM_OPT_DISCARD_DELIVERIES, a scratch buffer.
 int delivery_out(Eng* E, uint64_t n, tgsim_delivery** out, hipStream_t sq) {
@@ -1622,6 +1687,10 @@ int deliver(Eng* E, const tgsim_delivery* in, uint64_t n, hipEvent_t wait, bool 
     int prc = ping_recv(E, dst, E->d_doff.p, nd, n, sq);
     if (prc) return prc;
   }
+  if (E->flow_on && n_win == 1) {
+    int prc = flow_recv(E, dst, E->d_doff.p, nd, n, sq);
+    if (prc) return prc;
+  }
   if (E->groups_on) {
     launch_group_dst(group_args(E), dst, E->d_doff.p, nseg, nd, n, std::max<uint64_t>(E->n_in, 1), sq);
     HIPCHK(hipGetLastError());
@@ -1719,6 +1788,10 @@ int deliver_local_from(Eng* E, const EmitRead& emit, uint32_t* emit_n, uint64_t*
     int prc = ping_recv(E, dst, doff.p, nd, n, sq);
     if (prc) return prc;
   }
+  if (E->flow_on) {
+    int prc = flow_recv(E, dst, doff.p, nd, n, sq);
+    if (prc) return prc;
+  }
   if (E->groups_on) {
     launch_group_dst(group_args(E), dst, doff.p, nd, nd, n, need_n ? n : n_in, sq);
     HIPCHK(hipGetLastError());
@@ -1752,7 +1825,7 @@ int deliver_local(Eng* E) {
 // dense windows on an engine that owns every peer, no host packets, no per-window diagnostics.
 bool fusable(Eng* E, uint32_t n_ticks, uint32_t g, bool routed = false) {
   if (g < 2 || (E->S != E->N && !routed) || !E->staged.empty() || E->gen_q.size() < g || E->metrics_on ||
-      E->gossip_on || E->ping_on || E->groups_on || E->sparse_mode == 1 || kSpw != 1)
+      E->gossip_on || E->ping_on || E->flow_on || E->groups_on || E->sparse_mode == 1 || kSpw != 1)
     return false;
   for (uint32_t i = 0; i < g; ++i)
     if (E->gen_q[i].ticks != n_ticks || E->gen_q[i].n < 64ull * E->S) return false;  // sparse windows
@@ -1995,6 +2068,7 @@ void engine_shard(void* e, uint32_t* begin, uint32_t* end) {
 int engine_fail(void* e, int code, const char* msg) { return as_eng(e)->fail(code, "%s", msg); }
 void engine_persist_routed(void* e, uint32_t pct) { as_eng(e)->routed_pct = pct; }
 bool engine_ping_armed(void* e) { return as_eng(e)->ping_on; }
+bool engine_flow_armed(void* e) { return as_eng(e)->flow_on; }
 const uint64_t* engine_route_counts_dev(void* e) {
   Eng* E = as_eng(e);
   return E->route_n && E->d_rsend.p ? E->d_rsend.p + 16 * E->route_head : nullptr;
@@ -2270,10 +2344,11 @@ void tgsim_destroy(void* e) {
   if (E->h_err) (void)hipHostFree(E->h_err);
   if (E->h_xerr) (void)hipHostFree(E->h_xerr);
   if (E->h_work) (void)hipHostFree(E->h_work);
-  ping_release(E);
+  flow_release(E);  // (and the ping driver's state)
   groups_release(E);
   if (E->h_ppub) (void)hipHostFree(E->h_ppub);
   if (E->ev_ping) (void)hipEventDestroy(E->ev_ping);
+  if (E->ev_flow) (void)hipEventDestroy(E->ev_flow);
   if (E->h_gerr) (void)hipHostFree(E->h_gerr);
   if (E->h_pub) (void)hipHostFree(E->h_pub);
   if (E->ev_gpub) (void)hipEventDestroy(E->ev_gpub);
@@ -2355,6 +2430,7 @@ int tgsim_submit(void* e, const tgsim_pkt* pkts, size_t n) {
   if (!E || (!pkts && n)) return -EINVAL;
   if (!E->gen_q.empty()) return E->fail(-EBUSY, "generated traffic already pending for the next step");
   if (E->ping_on) return E->fail(-EBUSY, "%s: the ping driver is armed (tgsim_ping_init(engine, NULL, NULL) disarms it)", "submit");
+  if (E->flow_on) return E->fail(-EBUSY, "%s: the flow driver is armed (tgsim_flow_init(engine, NULL, NULL, 0) disarms it)", "submit");
   for (size_t i = 0; i < n; ++i) {
     if (pkts[i].src < E->o.shard_begin || pkts[i].src >= E->o.shard_end)
       return E->fail(-EINVAL, "packet %zu: src %u not owned by this shard", i, pkts[i].src);
@@ -2371,6 +2447,7 @@ int tgsim_gen_storm(void* e, double lambda, uint32_t n_ticks) {
   if (!E || !(lambda >= 0.0) || lambda > 4.0 || n_ticks == 0 || n_ticks > 65536) return -EINVAL;
   if (!E->staged.empty()) return E->fail(-EBUSY, "host packets already pending for the next step");
   if (E->ping_on) return E->fail(-EBUSY, "%s: the ping driver is armed (tgsim_ping_init(engine, NULL, NULL) disarms it)", "gen_storm");
+  if (E->flow_on) return E->fail(-EBUSY, "%s: the flow driver is armed (tgsim_flow_init(engine, NULL, NULL, 0) disarms it)", "gen_storm");
   HIPCHK(hipSetDevice(E->dev));
   GenArgsHost g;
   double p = std::exp(-lambda), F = p;
@@ -2414,6 +2491,7 @@ int tgsim_gossip_init(void* e, const tgsim_gossip* g) {
       g->msg_len == 0 || g->msg_len > 65535 || E->N < 2)
     return -EINVAL;
   if (E->ping_on) return E->fail(-EBUSY, "%s: the ping driver is armed (tgsim_ping_init(engine, NULL, NULL) disarms it)", "gossip_init");
+  if (E->flow_on) return E->fail(-EBUSY, "%s: the flow driver is armed (tgsim_flow_init(engine, NULL, NULL, 0) disarms it)", "gossip_init");
   if (g->start_tick < E->now_tick + E->gen_q_ticks) return E->fail(-EINVAL, "gossip: start tick in the past");
   HIPCHK(hipSetDevice(E->dev));
   E->gossip = *g;
@@ -2625,7 +2703,7 @@ int tgsim_ping_init(void* e, const tgsim_ping* p, const uint32_t* targets) {
     if (targets) return E->fail(-EINVAL, "ping: a target table without parameters");
     int rc = sync_stream(E);
     if (rc) return rc;
-    ping_release(E);
+    if (E->ping_on) ping_release(E);  // (an armed flow driver owns the calendar: it stays)
     return 0;
   }
   if (!targets) return E->fail(-EINVAL, "ping: no target table");
@@ -2639,6 +2717,7 @@ int tgsim_ping_init(void* e, const tgsim_ping* p, const uint32_t* targets) {
   if (p->n_bins > kPingMaxBins) return E->fail(-EINVAL, "ping: n_bins %u above %u", p->n_bins, kPingMaxBins);
   if (p->n_bins && p->bin_ns == 0) return E->fail(-EINVAL, "ping: bin_ns 0 with %u bins", p->n_bins);
   if (E->gossip_on) return E->fail(-EBUSY, "ping: the gossip driver is armed");
+  if (E->flow_on) return E->fail(-EBUSY, "ping: the flow driver is armed");
   if (!E->staged.empty()) return E->fail(-EBUSY, "ping: host packets are pending for the next step");
   if (!E->gen_q.empty() || E->route_n) return E->fail(-EBUSY, "ping: generated windows or launched steps are pending");
   if (p->start_tick < E->now_tick)
@@ -2815,6 +2894,226 @@ int64_t tgsim_ping_pairs(void* e, uint32_t peer, uint32_t n, tgsim_ping_pair* ou
   return static_cast<int64_t>(rows);
 }
 
+// Flow driver (include/tgsim.h).
+int tgsim_flow_init(void* e, const tgsim_flow* p, const tgsim_flow_spec* flows, uint64_t n_flows) {
+  Eng* E = as_eng(e);
+  if (!E) return -EINVAL;
+  HIPCHK(hipSetDevice(E->dev));
+  if (!p) {  // disarm
+    if (flows || n_flows) return E->fail(-EINVAL, "flow: a flow table without parameters");
+    int rc = sync_stream(E);
+    if (rc) return rc;
+    if (E->flow_on) flow_release(E);
+    return 0;
+  }
+  if (!flows || !n_flows) return E->fail(-EINVAL, "flow: no flow table");
+  if (E->S != E->N)
+    return E->fail(-EINVAL, "flow: this engine owns peers [%u, %u) of %u (the driver needs one engine for every peer)",
+                   E->o.shard_begin, E->o.shard_end, E->N);
+  if (p->seg_len == 0 || p->seg_len > 65535) return E->fail(-EINVAL, "flow: seg_len %u outside 1..65535", p->seg_len);
+  if (p->ack_len == 0 || p->ack_len > 65535) return E->fail(-EINVAL, "flow: ack_len %u outside 1..65535", p->ack_len);
+  if (p->window == 0 || p->window > 64) return E->fail(-EINVAL, "flow: window %u outside 1..64", p->window);
+  if (p->rto_ticks == 0 || p->rto_ticks >= (1u << 31)) return E->fail(-EINVAL, "flow: rto_ticks %u outside 1..2^31-1", p->rto_ticks);
+  if (p->max_attempts == 0 || p->max_attempts > 16) return E->fail(-EINVAL, "flow: max_attempts %u outside 1..16", p->max_attempts);
+  if (p->n_bins > kPingMaxBins) return E->fail(-EINVAL, "flow: n_bins %u above %u", p->n_bins, kPingMaxBins);
+  if (p->n_bins && p->bin_ns == 0) return E->fail(-EINVAL, "flow: bin_ns 0 with %u bins", p->n_bins);
+  if (n_flows > static_cast<uint64_t>(E->N) * TGSIM_FLOW_SLOTS)
+    return E->fail(-EINVAL, "flow: %llu flows for %u peers (at most %u per source)", static_cast<unsigned long long>(n_flows), E->N,
+                   TGSIM_FLOW_SLOTS);
+  if (E->gossip_on) return E->fail(-EBUSY, "flow: the gossip driver is armed");
+  if (E->ping_on) return E->fail(-EBUSY, "flow: the ping driver is armed (tgsim_ping_init(engine, NULL, NULL) disarms it)");
+  if (!E->staged.empty()) return E->fail(-EBUSY, "flow: host packets are pending for the next step");
+  if (!E->gen_q.empty() || E->route_n) return E->fail(-EBUSY, "flow: generated windows or launched steps are pending");
+  std::vector<uint32_t> first(E->N, 0), cnt(E->N, 0);
+  uint64_t in_flight = 0;
+  for (uint64_t i = 0; i < n_flows; ++i) {
+    const tgsim_flow_spec& f = flows[i];
+    const unsigned long long ii = i;
+    if (f.src >= E->N) return E->fail(-EINVAL, "flow: flows[%llu].src = %u is out of range", ii, f.src);
+    if (i && f.src < flows[i - 1].src)
+      return E->fail(-EINVAL, "flow: flows[%llu].src = %u after src %u (the table is sorted by src)", ii, f.src, flows[i - 1].src);
+    if (f.dst == f.src || f.dst >= E->N)  // (TGSIM_EXTERNAL is out of range too)
+      return E->fail(-EINVAL, "flow: flows[%llu].dst = %u is %s", ii, f.dst, f.dst == f.src ? "the source itself" : "out of range");
+    if (f.n_seg == 0 || f.n_seg > (1u << 23)) return E->fail(-EINVAL, "flow: flows[%llu].n_seg = %u outside 1..2^23", ii, f.n_seg);
+    if (f.start_tick < E->now_tick)
+      return E->fail(-EINVAL, "flow: flows[%llu].start_tick %u in the past (now %llu)", ii, f.start_tick,
+                     static_cast<unsigned long long>(E->now_tick));
+    if (f.start_tick >= (1u << 31)) return E->fail(-EINVAL, "flow: flows[%llu].start_tick %u beyond tick 2^31", ii, f.start_tick);
+    if (cnt[f.src] == TGSIM_FLOW_SLOTS)
+      return E->fail(-EINVAL, "flow: flows[%llu] is flow %u of source %u (at most %u per source)", ii, TGSIM_FLOW_SLOTS + 1, f.src,
+                     TGSIM_FLOW_SLOTS);
+    if (!cnt[f.src]) first[f.src] = static_cast<uint32_t>(i);
+    ++cnt[f.src];
+    in_flight += std::min(p->window, f.n_seg);
+  }
+  int rc = sync_stream(E);  // a re-init: the last delivery's receipts may still run
+  if (rc) return rc;
+  if (!E->ev_flow) HIPCHK(hipEventCreateWithFlags(&E->ev_flow, hipEventDisableTiming));
+  if (!E->h_ppub) {
+    HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&E->h_ppub), (kPingPubWords + 1) * sizeof(uint64_t),
+                         hipHostMallocCoherent | hipHostMallocMapped));
+    memset(E->h_ppub, 0, (kPingPubWords + 1) * sizeof(uint64_t));
+    HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&E->dm_ppub), E->h_ppub, 0));
+  }
+  flow_release(E);
+  E->flow = *p;
+  E->n_flows = n_flows;
+  E->flow_offered = 0;
+  E->ping_cur = 0;
+  E->ping_kept = 0;
+  E->ping_appended = 0;
+  HIPCHK(E->d_fspec.ensure_exact(n_flows));
+  HIPCHK(E->d_frow.ensure_exact(n_flows));
+  HIPCHK(E->d_fbits.ensure_exact(n_flows));
+  HIPCHK(E->d_fdue.ensure_exact(n_flows * p->window));
+  HIPCHK(E->d_fatt.ensure_exact(n_flows * p->window));
+  HIPCHK(E->d_ffirst.ensure_exact(E->N));
+  HIPCHK(E->d_fcnt.ensure_exact(E->N));
+  HIPCHK(E->d_pcur.ensure_exact(E->N));
+  HIPCHK(E->d_phist.ensure_exact(static_cast<size_t>(kPingReplicas) * kPingMaxBins));
+  HIPCHK(E->d_pctr.ensure_exact(kPingCtrWords));
+  HIPCHK(E->d_pres.ensure_exact(kFlowResWords + kPingMaxBins));
+  // an ACK per segment in flight to start with; tgsim_gen_flow grows it for retransmissions
+  HIPCHK(E->d_pcal[0].ensure_exact(std::max<uint64_t>(in_flight, 1024)));
+  HIPCHK(E->d_pcal[1].ensure_exact(std::max<uint64_t>(in_flight, 1024)));
+  HIPCHK(hipMemcpy(E->d_fspec.p, flows, sizeof(tgsim_flow_spec) * n_flows, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(E->d_ffirst.p, first.data(), sizeof(uint32_t) * E->N, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(E->d_fcnt.p, cnt.data(), sizeof(uint32_t) * E->N, hipMemcpyHostToDevice));
+  launch_flow_init(flow_args(E, 0, 0), E->st);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(E->st));
+  HIPCHK(hipEventRecord(E->ev_flow, E->dst_st));
+  E->flow_on = true;
+  return 0;
+}
+
+int tgsim_gen_flow(void* e, uint32_t n_ticks) {
+  Eng* E = as_eng(e);
+  if (!E || n_ticks == 0 || n_ticks > 65536) return -EINVAL;
+  if (!E->flow_on) return E->fail(-EINVAL, "flow: the driver is not armed (tgsim_flow_init)");
+  if (n_ticks > E->flow.rto_ticks)
+    return E->fail(-EINVAL, "flow: a window of %u ticks is longer than rto_ticks %u (a segment is offered at most once per window)",
+                   n_ticks, E->flow.rto_ticks);
+  if (!E->staged.empty()) return E->fail(-EBUSY, "host packets already pending for the next step");
+  if (!E->gen_q.empty()) return E->fail(-EBUSY, "flow: a generated window is pending (one window at a time)");
+  if (E->flow_late)
+    return E->fail(-EINVAL, "flow: a receipt due at tick %llu preceded an earlier window (tgsim_flow_init starts again)",
+                   static_cast<unsigned long long>(E->flow_late_tick));
+  const uint64_t win0 = E->now_tick, win1 = win0 + n_ticks;
+  if (win1 >= (1ull << 31)) return E->fail(-EOVERFLOW, "flow: the window ends beyond tick 2^31");
+  HIPCHK(hipSetDevice(E->dev));
+  HIPCHK(hipStreamWaitEvent(E->st, E->ev_flow, 0));  // the last delivery's receipts (delivery stream)
+  FlowArgs f = flow_args(E, win0, n_ticks);
+  Eng::GenWindow w;  // a free window's offsets may still be read by a delivery
+  int rc = take_gen(E, &w);
+  if (rc) return rc;
+  HIPCHK(E->d_cnt.ensure(E->S));
+  launch_flow_count(f, E->d_cnt.p, E->d_pcur.p, f.cal.cal_cap, E->st);
+  HIPCHK(hipGetLastError());
+  const uint64_t seq = ++E->pub_seq;
+  launch_publish_words(reinterpret_cast<const uint64_t*>(E->d_pctr.p), kPingPubWords, E->dm_ppub, seq, E->st);
+  HIPCHK(hipGetLastError());
+  uint64_t total = 0;
+  rc = scan_counts(E, E->d_cnt, w.off, E->d_blk, E->d_tot, E->S, &total);
+  if (!rc) rc = wait_published(E, &E->h_ppub[kPingPubWords], seq, E->ev_pub, "flow generation (counters)");
+  if (rc) {
+    (void)retire_gen(E, std::move(w));
+    return rc;
+  }
+  uint64_t c[kPingPubWords];
+  for (uint32_t i = 0; i < kPingPubWords; ++i) c[i] = __atomic_load_n(&E->h_ppub[i], __ATOMIC_ACQUIRE);
+  const uint64_t cal_n = c[E->ping_cur];
+  E->ping_appended += cal_n - E->ping_kept;  // what the deliveries since the last generation added
+  E->ping_kept = cal_n;
+  if (c[kPcOverflow]) {
+    (void)retire_gen(E, std::move(w));
+    return E->fail(-ENOSPC, "flow: %llu ACKs found the calendar full", static_cast<unsigned long long>(c[kPcOverflow]));
+  }
+  if (c[kPcLate] != ~0ull) {  // nothing was written: the calendar and every flow stay as they are
+    (void)retire_gen(E, std::move(w));
+    E->flow_late = true;
+    E->flow_late_tick = c[kPcLate];
+    return E->fail(-EINVAL, "flow: a receipt due at tick %llu precedes the window at tick %llu (a window longer than "
+                            "the lookahead, or a lookahead longer than the minimum netem delay)",
+                   static_cast<unsigned long long>(c[kPcLate]), static_cast<unsigned long long>(win0));
+  }
+  // the calendar until the next generation: what stays, plus an ACK for every data packet offered by
+  // the end of this window that has none yet
+  const uint64_t offers = c[kPcOffers];
+  E->flow_offered += offers;
+  rc = ping_grow_calendar(E, cal_n + (E->flow_offered > E->ping_appended ? E->flow_offered - E->ping_appended : 0), cal_n);
+  if (!rc) rc = E->hip(w.in.ensure(total ? total : 1), "generated window");
+  if (!rc) rc = E->hip(E->d_ptmp.ensure(total ? total : 1), "generated window");
+  if (rc) {
+    (void)retire_gen(E, std::move(w));
+    return rc;
+  }
+  f = flow_args(E, win0, n_ticks);
+  launch_flow_write(f, w.off.p, E->d_pcur.p, E->d_ptmp.p, w.in.p, cal_n, E->st);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemsetAsync(E->d_pctr.p + E->ping_cur, 0, sizeof(unsigned long long), E->st));
+  E->ping_cur ^= 1u;
+  E->ping_kept = cal_n - (total - offers);  // less the ACKs due in this window
+  w.n = total;
+  w.ticks = n_ticks;
+  E->gen_q_ticks += n_ticks;
+  E->gen_q.push_back(std::move(w));
+  return 0;
+}
+
+int64_t tgsim_flow_report(void* e, tgsim_flow_summary* out, uint64_t* hist, size_t hist_cap) {
+  Eng* E = as_eng(e);
+  if (!E) return -EINVAL;
+  if (!E->flow_on) return E->fail(-EINVAL, "flow_report: the flow driver is not armed (tgsim_flow_init)");
+  if (!out) return E->fail(-EINVAL, "flow_report: no summary buffer");
+  const uint32_t nb = E->flow.n_bins;
+  if (nb && (!hist || hist_cap < nb)) return E->fail(-EINVAL, "flow_report: %zu histogram words for %u bins", hist ? hist_cap : size_t{0}, nb);
+  HIPCHK(hipSetDevice(E->dev));
+  int rc = sync_stream(E);  // the receipts of the last delivery are folded on the delivery stream
+  if (rc) return rc;
+  launch_flow_report(flow_args(E, 0, 0), E->d_pres.p, E->st);
+  HIPCHK(hipGetLastError());
+  unsigned long long res[kFlowResWords + kPingMaxBins], ctr[kPingCtrWords];
+  HIPCHK(hipMemcpyAsync(res, E->d_pres.p, sizeof(unsigned long long) * (kFlowResWords + nb), hipMemcpyDeviceToHost, E->st));
+  HIPCHK(hipMemcpyAsync(ctr, E->d_pctr.p, sizeof ctr, hipMemcpyDeviceToHost, E->st));
+  HIPCHK(hipStreamSynchronize(E->st));
+  out->flows = res[0];
+  out->done = res[1];
+  out->failed = res[2];
+  out->active = res[3];
+  out->segs_acked = res[4];
+  out->bytes_acked = res[4] * E->flow.seg_len;
+  out->data_offered = res[5];
+  out->retransmits = res[6];
+  out->stale_acks = res[7];
+  out->dup_ignored = ctr[kPcDup];
+  out->corrupt_ignored = ctr[kPcCorrupt];
+  out->pending_acks = ctr[E->ping_cur];
+  out->fct_sum_ns = res[8];
+  out->fct_min_ns = res[9];
+  out->fct_max_ns = res[10];
+  for (uint32_t b = 0; b < nb; ++b) hist[b] = res[kFlowResWords + b];
+  return nb;
+}
+
+int64_t tgsim_flow_rows(void* e, uint64_t first, uint64_t n, tgsim_flow_row* out, size_t cap) {
+  Eng* E = as_eng(e);
+  if (!E) return -EINVAL;
+  if (!E->flow_on) return E->fail(-EINVAL, "flow_rows: the flow driver is not armed (tgsim_flow_init)");
+  if (first > E->n_flows || n > E->n_flows - first)
+    return E->fail(-EINVAL, "flow_rows: flows [%llu, %llu) outside [0, %llu)", static_cast<unsigned long long>(first),
+                   static_cast<unsigned long long>(first + n), static_cast<unsigned long long>(E->n_flows));
+  if (cap < n) return E->fail(-ENOSPC, "flow_rows: %zu rows for %llu", cap, static_cast<unsigned long long>(n));
+  if (n && !out) return E->fail(-EINVAL, "flow_rows: no output buffer");
+  HIPCHK(hipSetDevice(E->dev));
+  int rc = sync_stream(E);
+  if (rc) return rc;
+  if (!n) return 0;
+  HIPCHK(hipMemcpyAsync(out, E->d_frow.p + first, sizeof(tgsim_flow_row) * n, hipMemcpyDeviceToHost, E->st));
+  HIPCHK(hipStreamSynchronize(E->st));
+  return static_cast<int64_t>(n);
+}
+
 // Per-group traffic matrix (include/tgsim.h).
 int tgsim_groups_init(void* e, const uint16_t* group_of, uint32_t n_groups) {
   Eng* E = as_eng(e);
@@ -2888,6 +3187,7 @@ int tgsim_step_sim_launch(void* e, uint32_t n_ticks, uint32_t n_ranks, const uin
   if (bounds[0] != 0 || bounds[n_ranks] != E->N) return E->fail(-EINVAL, "rank bounds must cover [0, n_peers)");
   if (E->route_n == Eng::kRouteSlots) return E->fail(-EBUSY, "two launched steps are not finished yet");
   if (E->ping_on) return E->fail(-EBUSY, "%s: the ping driver is armed (tgsim_ping_init(engine, NULL, NULL) disarms it)", "step_sim_launch");
+  if (E->flow_on) return E->fail(-EBUSY, "%s: the flow driver is armed (tgsim_flow_init(engine, NULL, NULL, 0) disarms it)", "step_sim_launch");
   HIPCHK(hipSetDevice(E->dev));
   int rc = run_sim(E, n_ticks);
   if (rc) return rc;
@@ -2915,6 +3215,7 @@ int tgsim_step_sim_launch_slotted(void* e, uint32_t n_ticks, uint32_t n_ranks, c
   if (bounds[0] != 0 || bounds[n_ranks] != E->N) return E->fail(-EINVAL, "rank bounds must cover [0, n_peers)");
   if (E->route_n == Eng::kRouteSlots) return E->fail(-EBUSY, "two launched steps are not released yet");
   if (E->ping_on) return E->fail(-EBUSY, "%s: the ping driver is armed (tgsim_ping_init(engine, NULL, NULL) disarms it)", "step_sim_launch_slotted");
+  if (E->flow_on) return E->fail(-EBUSY, "%s: the flow driver is armed (tgsim_flow_init(engine, NULL, NULL, 0) disarms it)", "step_sim_launch_slotted");
   HIPCHK(hipSetDevice(E->dev));
   int rc = run_sim(E, n_ticks);
   if (rc) return rc;
@@ -2933,6 +3234,7 @@ int tgsim_step_sim_launch_slotted_n(void* e, uint32_t n_ticks, uint32_t n_win, u
   if (bounds[0] != 0 || bounds[n_ranks] != E->N) return E->fail(-EINVAL, "rank bounds must cover [0, n_peers)");
   if (E->route_n == Eng::kRouteSlots) return E->fail(-EBUSY, "two launched steps are not released yet");
   if (E->ping_on) return E->fail(-EBUSY, "%s: the ping driver is armed (tgsim_ping_init(engine, NULL, NULL) disarms it)", "step_sim_launch_slotted_n");
+  if (E->flow_on) return E->fail(-EBUSY, "%s: the flow driver is armed (tgsim_flow_init(engine, NULL, NULL, 0) disarms it)", "step_sim_launch_slotted_n");
   HIPCHK(hipSetDevice(E->dev));
   if (!fusable(E, n_ticks, n_win, true))
     return E->fail(-EINVAL, "step_sim_launch_slotted_n: the next %u windows are not generated dense windows of %u ticks",

@@ -334,7 +334,8 @@ enum PingCtr {
   kPcDup = 2, kPcCorrupt = 3,  // records ignored for TGSIM_FLAG_DUP / TGSIM_FLAG_CORRUPT
   kPcLate = 4,      // the earliest calendar tick that preceded a generated window (all-ones: none)
   kPcOverflow = 5,  // entries that found the calendar full (never written)
-  kPingPubWords = 6,
+  kPcOffers = 6,    // flow driver: data packets the window being generated offers (count pass)
+  kPingPubWords = 7,
   kPingCtrWords = 8
 };
 struct PingArgs {
@@ -352,6 +353,23 @@ struct PingArgs {
   uint64_t win0;
   uint32_t n_ticks, j_lo, j_hi;
   uint32_t sent;             // reports: probes per slot offered so far
+};
+
+// Flow driver (tgsim_flow_*) of an engine that owns every peer.  Its ACK calendar is
+// the ping driver's (PingCal, the kPc* counters, k_ping_count_cal / k_ping_write_cal / k_ping_order):
+// `cal` carries the calendar's buffers and counters, the window and ack_len as `len`.
+constexpr uint32_t kFlowResWords = 11;  // flows done failed active segs offered retransmits stale fct_sum fct_min fct_max
+struct FlowArgs {
+  PingArgs cal;
+  const tgsim_flow_spec* spec;  // [n_flows], sorted by src
+  tgsim_flow_row* rows;         // [n_flows]
+  uint64_t* bitmap;             // [n_flows] acknowledged segments of [base, base + 64)
+  uint32_t* due;                // [n_flows][window] ring indexed seg % window
+  uint8_t* att;                 // [n_flows][window]
+  const uint32_t* first;        // [n_peers] first flow of the source
+  const uint32_t* cnt;          // [n_peers] its flows (<= TGSIM_FLOW_SLOTS)
+  uint64_t n_flows;
+  uint32_t seg_len, window, rto, max_attempts;
 };
 
 // Per-group traffic matrix (tgsim_groups_init / tgsim_group_matrix).
@@ -382,6 +400,8 @@ int engine_fail(void* engine, int code, const char* msg);
 void engine_persist_routed(void* engine, uint32_t pct);
 // The ping mesh driver is armed (tgsim_ping_init): the exchange's steps refuse with -EBUSY.
 bool engine_ping_armed(void* engine);
+// The same for the flow driver (tgsim_flow_init).
+bool engine_flow_armed(void* engine);
 // Records `ev` on the routing stream after every routing enqueued so far (the exchange of a launched
 // window waits for it on the device, not only for the host's view of the published edges).
 int engine_record_routed(void* engine, hipEvent_t ev);

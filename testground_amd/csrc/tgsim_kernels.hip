@@ -3116,6 +3116,44 @@ __global__ __launch_bounds__(256) void k_gossip_times(const uint32_t* __restrict
 // to one address serialize at ~12 ns each, and one per wavefront (50,000 a window at 100,000 peers,
 // fanout 8) made this pass 1.25 ms long; one per tile makes it 3,100.
 constexpr uint32_t kPingRecvItems = 4;
+// The calendar append of one tile, shared by the ping and the flow receipts (every thread of the
+// 256-thread workgroup calls it, once per tile): the tile's entries take consecutive slots behind
+// ONE claim.  w_cnt[4] and s_base are the workgroup's LDS scratch.
+__device__ __forceinline__ void cal_append_tile(const PingArgs& a, const PingCal (&e)[kPingRecvItems],
+                                                const bool (&request)[kPingRecvItems], uint32_t* w_cnt,
+                                                unsigned long long* s_base) {
+  const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+  uint32_t c = 0;
+#pragma unroll
+  for (uint32_t u = 0; u < kPingRecvItems; ++u) c += request[u] ? 1u : 0u;
+  const uint32_t incl = (uint32_t)scan_sum_i32((int32_t)c);
+  const uint32_t w_tot = readlane32(incl, kWave - 1);
+  if (lane == 0) w_cnt[wv] = w_tot;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const uint32_t tot = w_cnt[0] + w_cnt[1] + w_cnt[2] + w_cnt[3];
+    unsigned long long at = 0;
+    if (tot) {
+      at = atomicAdd(&a.ctr[a.cal_cur], (unsigned long long)tot);
+      if (at + tot > a.cal_cap) {  // (the host sizes the calendar for every probe in flight)
+        atomicAdd(&a.ctr[kPcOverflow], (unsigned long long)tot);
+        atomicAdd(&a.ctr[a.cal_cur], 0ull - tot);
+        at = ~0ull;
+      }
+    }
+    *s_base = at;
+  }
+  __syncthreads();
+  if (c && *s_base != ~0ull) {
+    uint64_t pos = *s_base + (incl - c);
+    for (uint32_t w = 0; w < wv; ++w) pos += w_cnt[w];
+#pragma unroll
+    for (uint32_t u = 0; u < kPingRecvItems; ++u)
+      if (request[u]) a.cal[pos++] = e[u];
+  }
+  __syncthreads();  // (w_cnt and s_base are the next tile's)
+}
+
 __global__ __launch_bounds__(256) void k_ping_recv(PingArgs a, const tgsim_delivery* __restrict__ recs,
                                                    const uint64_t* __restrict__ off, uint32_t n_dst, uint64_t n_bound) {
   __shared__ uint32_t hist[kPingMaxBins];
@@ -3124,7 +3162,7 @@ __global__ __launch_bounds__(256) void k_ping_recv(PingArgs a, const tgsim_deliv
   for (uint32_t i = threadIdx.x; i < a.n_bins; i += 256) hist[i] = 0u;
   __syncthreads();
   const uint64_t n = off[n_dst] < n_bound ? off[n_dst] : n_bound;  // (never past the buffer the bound sized)
-  const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+  const uint32_t lane = threadIdx.x & 63u;
   const uint64_t tile = 256 * kPingRecvItems;
   const uint32_t n_req = a.count * a.fanout;  // (count <= 65535, fanout <= 64)
   uint32_t dups = 0, cors = 0;
@@ -3167,35 +3205,7 @@ __global__ __launch_bounds__(256) void k_ping_recv(PingArgs a, const tgsim_deliv
         }
       }
     }
-    uint32_t c = 0;
-#pragma unroll
-    for (uint32_t u = 0; u < kPingRecvItems; ++u) c += request[u] ? 1u : 0u;
-    const uint32_t incl = (uint32_t)scan_sum_i32((int32_t)c);
-    const uint32_t w_tot = readlane32(incl, kWave - 1);
-    if (lane == 0) w_cnt[wv] = w_tot;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      const uint32_t tot = w_cnt[0] + w_cnt[1] + w_cnt[2] + w_cnt[3];
-      unsigned long long at = 0;
-      if (tot) {
-        at = atomicAdd(&a.ctr[a.cal_cur], (unsigned long long)tot);
-        if (at + tot > a.cal_cap) {  // (the host sizes the calendar for every probe in flight)
-          atomicAdd(&a.ctr[kPcOverflow], (unsigned long long)tot);
-          atomicAdd(&a.ctr[a.cal_cur], 0ull - tot);
-          at = ~0ull;
-        }
-      }
-      s_base = at;
-    }
-    __syncthreads();
-    if (c && s_base != ~0ull) {
-      uint64_t pos = s_base + (incl - c);
-      for (uint32_t w = 0; w < wv; ++w) pos += w_cnt[w];
-#pragma unroll
-      for (uint32_t u = 0; u < kPingRecvItems; ++u)
-        if (request[u]) a.cal[pos++] = e[u];
-    }
-    __syncthreads();  // (w_cnt and s_base are the next tile's)
+    cal_append_tile(a, e, request, w_cnt, &s_base);
   }
   const uint64_t td = wave_sum(dups), tc = wave_sum(cors);
   if (lane == 0) {
@@ -3352,13 +3362,15 @@ __device__ __forceinline__ uint64_t wave_min_max_u64(uint64_t v, bool want_max) 
   }
   return v;
 }
-__global__ __launch_bounds__(256) void k_ping_report_init(PingArgs a, unsigned long long* res) {
+// (n_words result words ahead of the histogram, word min_word a minimum: the flow report's too)
+__global__ __launch_bounds__(256) void k_ping_report_init(PingArgs a, unsigned long long* res, uint32_t n_words,
+                                                          uint32_t min_word) {
   const uint32_t i = threadIdx.x;
-  if (i < kPingResWords) res[i] = i == 4 ? ~0ull : 0ull;
+  if (i < n_words) res[i] = i == min_word ? ~0ull : 0ull;
   if (i < a.n_bins) {
     unsigned long long v = 0;
     for (uint32_t r = 0; r < kPingReplicas; ++r) v += a.hist[(uint64_t)r * kPingMaxBins + i];
-    res[kPingResWords + i] = v;
+    res[n_words + i] = v;
   }
 }
 
@@ -3427,6 +3439,267 @@ __global__ __launch_bounds__(256) void k_ping_pairs(PingArgs a, uint64_t i0, uin
   tgsim_ping_pair p = a.pairs[i0 + i];
   p.sent = a.targets[i0 + i] == TGSIM_PING_NONE ? 0u : a.sent;
   out[i] = p;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Flow driver (tgsim_flow_*): windowed transfers with per-segment ACKs and timers.
+// The ACK calendar is the ping driver's: cal_append_tile here, k_ping_count_cal / k_ping_write_cal /
+// k_ping_order in the generation, with f.cal as their arguments.
+__device__ __forceinline__ uint32_t flow_slot(uint32_t seq) { return seq >> 23 & 15u; }
+__device__ __forceinline__ uint32_t flow_seg(uint32_t seq) { return seq & 0x7FFFFFu; }
+
+// Receipt, data leg (the ping request leg): a delivered segment that matches a flow of its source
+// becomes a calendar entry, the ACK its destination offers at the tick after the delivery; clones
+// and corrupted copies of either leg are counted here.
+__global__ __launch_bounds__(256) void k_flow_recv_data(FlowArgs f, const tgsim_delivery* __restrict__ recs,
+                                                        const uint64_t* __restrict__ off, uint32_t n_dst, uint64_t n_bound) {
+  __shared__ uint32_t w_cnt[4];
+  __shared__ unsigned long long s_base;
+  const PingArgs& a = f.cal;
+  const uint64_t n = off[n_dst] < n_bound ? off[n_dst] : n_bound;
+  const uint64_t tile = 256 * kPingRecvItems;
+  uint32_t dups = 0, cors = 0;
+  for (uint64_t base = blockIdx.x * tile; base < n; base += gridDim.x * tile) {  // (uniform in the workgroup)
+    PingCal e[kPingRecvItems];
+    bool request[kPingRecvItems];
+#pragma unroll
+    for (uint32_t u = 0; u < kPingRecvItems; ++u) {
+      const uint64_t i = base + u * 256 + threadIdx.x;
+      request[u] = false;
+      e[u] = PingCal{};
+      if (i >= n) continue;
+      const tgsim_delivery r = recs[i];
+      if (r.flags & TGSIM_FLAG_DUP) {
+        ++dups;
+      } else if (r.flags & TGSIM_FLAG_CORRUPT) {
+        ++cors;
+      } else if (!(r.seq >> 31) && r.src < a.n_peers && flow_slot(r.seq) < f.cnt[r.src]) {
+        const tgsim_flow_spec sp = f.spec[f.first[r.src] + flow_slot(r.seq)];
+        if (sp.dst == r.dst && flow_seg(r.seq) < sp.n_seg) {
+          request[u] = true;
+          e[u].tick = (uint32_t)(r.t_ns / a.tick_ns + 1);
+          e[u].responder = r.dst;
+          e[u].requester = r.src;
+          e[u].seq = r.seq;
+        }
+      }
+    }
+    cal_append_tile(a, e, request, w_cnt, &s_base);
+  }
+  const uint64_t td = wave_sum(dups), tc = wave_sum(cors);
+  if ((threadIdx.x & 63u) == 0) {
+    if (td) atomicAdd(&a.ctr[kPcDup], (unsigned long long)td);
+    if (tc) atomicAdd(&a.ctr[kPcCorrupt], (unsigned long long)tc);
+  }
+}
+
+// Receipt, ACK leg: sequential per flow, so one lane per flow and no atomics on flow state.  The
+// records are grouped by destination and ordered (t_ns, src, seq) inside a group, which is the order
+// the ACKs take effect in: the lane walks its source's range and applies its own slot's ACKs (the
+// lanes of one source's flows are neighbours and read the same records).  Loops: the off[] range, and
+// at most `window` released segments per ACK.  A finished flow's FCT goes to the workgroup's LDS
+// histogram, flushed to replica blockIdx mod kPingReplicas.
+__global__ __launch_bounds__(256) void k_flow_recv_ack(FlowArgs f, const tgsim_delivery* __restrict__ recs,
+                                                       const uint64_t* __restrict__ off, uint64_t n_bound) {
+  __shared__ uint32_t hist[kPingMaxBins];
+  const PingArgs& a = f.cal;
+  for (uint32_t i = threadIdx.x; i < a.n_bins; i += 256) hist[i] = 0u;
+  __syncthreads();
+  const uint64_t fl = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (fl < f.n_flows) {
+    const tgsim_flow_spec sp = f.spec[fl];
+    const uint32_t slot = (uint32_t)(fl - f.first[sp.src]);
+    uint64_t b = off[sp.src], e = off[sp.src + 1];
+    e = e < n_bound ? e : n_bound;  // (never past the buffer the bound sized)
+    tgsim_flow_row row = f.rows[fl];
+    uint64_t bm = f.bitmap[fl];
+    bool touched = false;
+    for (; b < e; ++b) {
+      const tgsim_delivery r = recs[b];
+      if ((r.flags & (TGSIM_FLAG_DUP | TGSIM_FLAG_CORRUPT)) || !(r.seq >> 31) || flow_slot(r.seq) != slot ||
+          r.src != sp.dst)
+        continue;
+      const uint32_t seg = flow_seg(r.seq);
+      if (seg >= sp.n_seg) continue;
+      touched = true;
+      const uint32_t room = sp.n_seg - row.base;  // (base <= n_seg)
+      const uint32_t next = row.base + (room < f.window ? room : f.window);
+      if (row.state != TGSIM_FLOW_ACTIVE || seg < row.base || seg >= next || (bm >> (seg - row.base) & 1ull)) {
+        ++row.stale_acks;
+        continue;
+      }
+      bm |= 1ull << (seg - row.base);  // (seg - base < window <= 64)
+      ++row.acked;
+      if (seg != row.base) continue;
+      const uint32_t sh = ~bm ? (uint32_t)__builtin_ctzll(~bm) : 64u;  // the acknowledged prefix (window 64: all of it)
+      bm = sh < 64u ? bm >> sh : 0ull;
+      row.base += sh;
+      const uint32_t room2 = sp.n_seg - row.base;
+      const uint32_t next2 = row.base + (room2 < f.window ? room2 : f.window);
+      const uint32_t tick = (uint32_t)(r.t_ns / a.tick_ns + 1);
+      for (uint32_t sg = next; sg < next2; ++sg) {  // (at most `window` of them)
+        f.due[fl * f.window + sg % f.window] = tick;
+        f.att[fl * f.window + sg % f.window] = 0;
+      }
+      if (row.base == sp.n_seg) {
+        row.state = TGSIM_FLOW_DONE;
+        row.done_ns = r.t_ns;
+        if (a.n_bins) {
+          const uint64_t fct = r.t_ns - (uint64_t)sp.start_tick * a.tick_ns, bin = fct / a.bin_ns;
+          atomicAdd(&hist[bin < a.n_bins ? (uint32_t)bin : a.n_bins - 1], 1u);
+        }
+      }
+    }
+    if (touched) {
+      f.rows[fl] = row;
+      f.bitmap[fl] = bm;
+    }
+  }
+  __syncthreads();
+  unsigned long long* rep = a.hist + (uint64_t)(blockIdx.x % kPingReplicas) * kPingMaxBins;
+  for (uint32_t i = threadIdx.x; i < a.n_bins; i += 256)
+    if (hist[i]) atomicAdd(&rep[i], (unsigned long long)hist[i]);
+}
+
+// What flow fl offers in the window [win0, win1): the offers' count, the flow's fail tick F (all-ones:
+// none) and its earliest late tick (all-ones: none).  Read-only.
+struct FlowDue {
+  uint32_t n, fail, late;
+};
+__device__ __forceinline__ FlowDue flow_due(const FlowArgs& f, uint64_t fl, const tgsim_flow_spec& sp,
+                                            const tgsim_flow_row& row, uint64_t bm) {
+  FlowDue d{0u, ~0u, ~0u};
+  if (row.state != TGSIM_FLOW_ACTIVE) return d;
+  const uint32_t win0 = (uint32_t)f.cal.win0, win1 = win0 + f.cal.n_ticks;  // (both below 2^31)
+  const uint32_t room = sp.n_seg - row.base, n_fly = room < f.window ? room : f.window;
+  for (uint32_t i = 0; i < n_fly; ++i) {
+    if (bm >> i & 1ull) continue;
+    const uint64_t at = fl * f.window + (row.base + i) % f.window;
+    const uint32_t t = f.due[at];
+    if (t < win0) d.late = t < d.late ? t : d.late;
+    else if (t < win1 && f.att[at] >= f.max_attempts) d.fail = t < d.fail ? t : d.fail;
+  }
+  for (uint32_t i = 0; i < n_fly; ++i) {
+    if (bm >> i & 1ull) continue;
+    const uint32_t t = f.due[fl * f.window + (row.base + i) % f.window];
+    d.n += t >= win0 && t < win1 && t < d.fail;
+  }
+  return d;
+}
+
+// Generation, count pass (read-only: a late window leaves the state as it is): a lane per flow adds
+// its offers to its source's count; the window's total and the earliest late tick per wavefront.
+__global__ __launch_bounds__(256) void k_flow_count(FlowArgs f, uint64_t* counts) {
+  const uint64_t fl = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  FlowDue d{0u, ~0u, ~0u};
+  if (fl < f.n_flows) {
+    const tgsim_flow_spec sp = f.spec[fl];
+    d = flow_due(f, fl, sp, f.rows[fl], f.bitmap[fl]);
+    if (d.n) atomicAdd(reinterpret_cast<unsigned long long*>(&counts[sp.src]), (unsigned long long)d.n);
+  }
+  const uint64_t tot = wave_sum(d.n), late = wave_min_max_u64(d.late == ~0u ? ~0ull : d.late, false);
+  if ((threadIdx.x & 63u) == 0) {
+    if (tot) atomicAdd(&f.cal.ctr[kPcOffers], (unsigned long long)tot);
+    if (late != ~0ull) atomicMin(&f.cal.ctr[kPcLate], (unsigned long long)late);
+  }
+}
+
+// Generation, write pass: the flow's offers take a block of its source's row (one claim on the row
+// cursor; the order pass sorts the row), their timers restart, and a flow whose segment ran out of
+// attempts fails at that tick.  Runs only when nothing is late.
+__global__ __launch_bounds__(256) void k_flow_write(FlowArgs f, const uint64_t* __restrict__ off, uint32_t* cursor, InRec* out) {
+  const uint64_t fl = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (fl >= f.n_flows) return;
+  const tgsim_flow_spec sp = f.spec[fl];
+  tgsim_flow_row row = f.rows[fl];
+  const uint64_t bm = f.bitmap[fl];
+  const FlowDue d = flow_due(f, fl, sp, row, bm);
+  if (!d.n && d.fail == ~0u) return;
+  const uint32_t win0 = (uint32_t)f.cal.win0, win1 = win0 + f.cal.n_ticks;
+  const uint32_t slot = (uint32_t)(fl - f.first[sp.src]);
+  const uint32_t room = sp.n_seg - row.base, n_fly = room < f.window ? room : f.window;
+  uint64_t pos = d.n ? off[sp.src] + atomicAdd(&cursor[sp.src], d.n) : 0;
+  for (uint32_t i = 0; i < n_fly; ++i) {
+    if (bm >> i & 1ull) continue;
+    const uint64_t at = fl * f.window + (row.base + i) % f.window;
+    const uint32_t t = f.due[at], k = f.att[at];
+    if (t < win0 || t >= win1 || t >= d.fail) continue;
+    InRec rec;
+    rec.dst = sp.dst;
+    rec.seq = k << 27 | slot << 23 | (row.base + i);  // (k < max_attempts <= 16)
+    rec.tick = t - win0;
+    rec.len = f.seg_len;
+    out[pos++] = rec;
+    f.due[at] = t + f.rto;  // (t < 2^31, rto < 2^31)
+    f.att[at] = (uint8_t)(k + 1);
+    row.retransmits += k > 0;
+  }
+  row.offered += d.n;
+  if (d.fail != ~0u) {
+    row.state = TGSIM_FLOW_FAILED;
+    row.done_ns = (uint64_t)d.fail * f.cal.tick_ns;
+  }
+  f.rows[fl] = row;
+}
+
+// tgsim_flow_init: every flow's first window of segments due at its start tick; the histogram
+// replicas and the calendar's counters.
+__global__ __launch_bounds__(256) void k_flow_init(FlowArgs f) {
+  const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < f.n_flows) {
+    const tgsim_flow_spec sp = f.spec[i];
+    f.rows[i] = tgsim_flow_row{};
+    f.bitmap[i] = 0ull;
+    for (uint32_t k = 0; k < f.window; ++k) {
+      f.due[i * f.window + k] = sp.start_tick;
+      f.att[i * f.window + k] = 0;
+    }
+  }
+  if (i < kPingReplicas * kPingMaxBins) f.cal.hist[i] = 0ull;
+  if (i < kPingCtrWords) f.cal.ctr[i] = i == kPcLate ? ~0ull : 0ull;
+}
+
+// tgsim_flow_report: one pass over the rows; a workgroup reduces in LDS and ends with one set of
+// atomics (at most 256 workgroups).  res: kFlowResWords words, then the histogram k_ping_report_init folded.
+__global__ __launch_bounds__(256) void k_flow_report(FlowArgs f, unsigned long long* res) {
+  __shared__ unsigned long long acc[kFlowResWords];
+  if (threadIdx.x < kFlowResWords) acc[threadIdx.x] = threadIdx.x == 9 ? ~0ull : 0ull;
+  __syncthreads();
+  uint64_t v[kFlowResWords] = {};
+  v[9] = ~0ull;
+  for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < f.n_flows; i += (uint64_t)gridDim.x * 256) {
+    const tgsim_flow_row r = f.rows[i];
+    ++v[0];
+    v[1] += r.state == TGSIM_FLOW_DONE;
+    v[2] += r.state == TGSIM_FLOW_FAILED;
+    v[3] += r.state == TGSIM_FLOW_ACTIVE;
+    v[4] += r.acked;
+    v[5] += r.offered;
+    v[6] += r.retransmits;
+    v[7] += r.stale_acks;
+    if (r.state == TGSIM_FLOW_DONE) {
+      const uint64_t fct = r.done_ns - (uint64_t)f.spec[i].start_tick * f.cal.tick_ns;
+      v[8] += fct;
+      v[9] = fct < v[9] ? fct : v[9];
+      v[10] = fct > v[10] ? fct : v[10];
+    }
+  }
+#pragma unroll
+  for (uint32_t w = 0; w < kFlowResWords; ++w) {
+    const uint64_t t = w == 9 ? wave_min_max_u64(v[w], false) : w == 10 ? wave_min_max_u64(v[w], true) : wave_sum(v[w]);
+    if ((threadIdx.x & 63u) == 0) {
+      if (w == 9) atomicMin(&acc[w], (unsigned long long)t);
+      else if (w == 10) atomicMax(&acc[w], (unsigned long long)t);
+      else atomicAdd(&acc[w], (unsigned long long)t);
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x < kFlowResWords && acc[0]) {
+    const uint32_t w = threadIdx.x;
+    if (w == 9) atomicMin(&res[w], acc[w]);
+    else if (w == 10) atomicMax(&res[w], acc[w]);
+    else atomicAdd(&res[w], acc[w]);
+  }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -4730,9 +5003,41 @@ void launch_ping_write(const PingArgs& a, const uint64_t* off, uint32_t* cursor,
 }
 
 void launch_ping_report(const PingArgs& a, unsigned long long* res, hipStream_t st) {
-  hipLaunchKernelGGL(k_ping_report_init, dim3(1), dim3(256), 0, st, a, res);
+  hipLaunchKernelGGL(k_ping_report_init, dim3(1), dim3(256), 0, st, a, res, kPingResWords, 4u);
   // (few workgroups: each ends with eight atomics on the same eight words, which serialize)
   hipLaunchKernelGGL(k_ping_report, dim3(std::min(ping_grid((uint64_t)a.n_peers * a.fanout), 256u)), dim3(256), 0, st, a, res);
+}
+
+// Flow driver (tgsim_flow_*).
+void launch_flow_init(const FlowArgs& f, hipStream_t st) {
+  const uint64_t n = std::max<uint64_t>(f.n_flows, (uint64_t)kPingReplicas * kPingMaxBins);
+  hipLaunchKernelGGL(k_flow_init, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, f);
+}
+
+void launch_flow_recv(const FlowArgs& f, const tgsim_delivery* recs, const uint64_t* off, uint32_t n_dst,
+                      uint64_t n_bound, hipStream_t st) {
+  hipLaunchKernelGGL(k_flow_recv_data, dim3(ping_grid(n_bound)), dim3(256), 0, st, f, recs, off, n_dst, n_bound);
+  hipLaunchKernelGGL(k_flow_recv_ack, dim3((uint32_t)((f.n_flows + 255) / 256)), dim3(256), 0, st, f, recs, off, n_bound);
+}
+
+void launch_flow_count(const FlowArgs& f, uint64_t* counts, uint32_t* cursor, uint64_t cal_bound, hipStream_t st) {
+  (void)hipMemsetAsync(counts, 0, sizeof(uint64_t) * f.cal.n_peers, st);
+  (void)hipMemsetAsync(cursor, 0, sizeof(uint32_t) * f.cal.n_peers, st);
+  (void)hipMemsetAsync(f.cal.ctr + kPcOffers, 0, sizeof(unsigned long long), st);
+  hipLaunchKernelGGL(k_flow_count, dim3((uint32_t)((f.n_flows + 255) / 256)), dim3(256), 0, st, f, counts);
+  if (cal_bound) hipLaunchKernelGGL(k_ping_count_cal, dim3(ping_grid(cal_bound)), dim3(256), 0, st, f.cal, counts);
+}
+
+void launch_flow_write(const FlowArgs& f, const uint64_t* off, uint32_t* cursor, InRec* tmp, InRec* out,
+                       uint64_t cal_bound, hipStream_t st) {
+  hipLaunchKernelGGL(k_flow_write, dim3((uint32_t)((f.n_flows + 255) / 256)), dim3(256), 0, st, f, off, cursor, tmp);
+  if (cal_bound) hipLaunchKernelGGL(k_ping_write_cal, dim3(ping_grid(cal_bound)), dim3(256), 0, st, f.cal, off, cursor, tmp);
+  hipLaunchKernelGGL(k_ping_order, dim3((f.cal.n_peers + 3) / 4), dim3(256), 0, st, off, tmp, out, f.cal.n_peers);
+}
+
+void launch_flow_report(const FlowArgs& f, unsigned long long* res, hipStream_t st) {
+  hipLaunchKernelGGL(k_ping_report_init, dim3(1), dim3(256), 0, st, f.cal, res, kFlowResWords, 9u);
+  hipLaunchKernelGGL(k_flow_report, dim3(std::min(ping_grid(f.n_flows), 256u)), dim3(256), 0, st, f, res);
 }
 
 void launch_ping_pairs(const PingArgs& a, uint64_t i0, uint64_t n, tgsim_ping_pair* out, hipStream_t st) {

@@ -84,6 +84,18 @@ void launch_ping_write(const PingArgs& a, const uint64_t* off, uint32_t* cursor,
                        uint64_t cal_bound, hipStream_t st);
 void launch_ping_report(const PingArgs& a, unsigned long long* res, hipStream_t st);
 void launch_ping_pairs(const PingArgs& a, uint64_t i0, uint64_t n, tgsim_ping_pair* out, hipStream_t st);
+// Flow driver (tgsim_flow_*), on the ping driver's calendar (f.cal).  _init: rows, timers, histogram
+// replicas, counters.  _recv: the data leg (calendar entries, ignored records), then the ACK leg (a
+// lane per flow).  _count: clears counts, cursor and kPcOffers, counts the flows' offers per source
+// and the due calendar entries.  _write: offers, due ACKs and the kept calendar entries, then the row
+// order.  _report: res = kFlowResWords summary words + n_bins histogram words.
+void launch_flow_init(const FlowArgs& f, hipStream_t st);
+void launch_flow_recv(const FlowArgs& f, const tgsim_delivery* recs, const uint64_t* off, uint32_t n_dst,
+                      uint64_t n_bound, hipStream_t st);
+void launch_flow_count(const FlowArgs& f, uint64_t* counts, uint32_t* cursor, uint64_t cal_bound, hipStream_t st);
+void launch_flow_write(const FlowArgs& f, const uint64_t* off, uint32_t* cursor, InRec* tmp, InRec* out,
+                       uint64_t cal_bound, hipStream_t st);
+void launch_flow_report(const FlowArgs& f, unsigned long long* res, hipStream_t st);
 // Per-group traffic matrix (tgsim_group_matrix).  _src: words 0..9 from a window's input (off[n_src + 1],
 // in, verdict) behind its simulate kernel; n_in: the window's offered packets (picks the lanes per
 // source).  _dst: words 10..13 from delivery-ordered records, segment sg = off[sg] ..

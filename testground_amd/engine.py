@@ -230,6 +230,48 @@ class CABIEngine:
         self._check(fn(self._h, peer, n, out.ctypes.data, len(out)), "ping_pairs")
         return out.reshape(n, fanout)
 
+    # -- flow driver (tgsim_flow_*) ----------------------------------------------------------------
+    def flow_init(self, flows=None, seg_len: int = 1460, ack_len: int = 64, window: int = 16, rto_ticks: int = 1,
+                  max_attempts: int = 8, bin_ns: int = 0, n_bins: int = 0) -> None:
+        """Arms the device flow driver: `flows` is an abi.FLOW_SPEC_DTYPE table sorted by src
+        (workloads.flow_table_mesh); a fixed window of `window` segments, one ACK per delivered
+        segment, a retransmission timer of rto_ticks per segment, at most max_attempts offers of a
+        segment (include/tgsim.h).  flow_init(None) disarms it."""
+        fn = self._gossip_fn("flow_init")
+        if flows is None:
+            self._check(fn(self._h, None, None, 0), "flow_init")
+            self._n_flows = None
+            return
+        t = np.ascontiguousarray(flows, dtype=abi.FLOW_SPEC_DTYPE)
+        if t.ndim != 1:
+            raise ValueError("flow_init: flows must be a 1-d abi.FLOW_SPEC_DTYPE table")
+        p = abi.Flow(seg_len, ack_len, window, rto_ticks, max_attempts, n_bins, bin_ns)
+        self._check(fn(self._h, C.byref(p), t.ctypes.data, len(t)), "flow_init")
+        self._n_flows = len(t)
+
+    def gen_flow(self, n_ticks: int) -> None:
+        self._check(self._gossip_fn("gen_flow")(self._h, n_ticks), "gen_flow")
+
+    def flow_report(self) -> dict:
+        """The summary over every flow (abi.FLOW_SUMMARY_FIELDS) and `hist` [n_bins] of the flow
+        completion times, reduced on the device (tgsim_flow_report)."""
+        fn = self._gossip_fn("flow_report")
+        s = abi.FlowSummary()
+        hist = np.zeros(abi.PING_MAX_BINS, dtype=np.uint64)
+        n = self._check(fn(self._h, C.byref(s), hist.ctypes.data, len(hist)), "flow_report")
+        out = {k: int(getattr(s, k)) for k in abi.FLOW_SUMMARY_FIELDS}
+        out["hist"] = hist[:n].copy()
+        return out
+
+    def flow_rows(self, first: int = 0, n: Optional[int] = None) -> np.ndarray:
+        """abi.FLOW_ROW_DTYPE rows of flows [first, first + n) of the table (tgsim_flow_rows)."""
+        fn = self._gossip_fn("flow_rows")
+        total = getattr(self, "_n_flows", None) or 0  # (unarmed: the call says so)
+        n = max(total - first, 0) if n is None else n
+        out = np.zeros(n, dtype=abi.FLOW_ROW_DTYPE)
+        self._check(fn(self._h, first, n, out.ctypes.data, len(out)), "flow_rows")
+        return out
+
     # -- per-group traffic matrix (tgsim_groups_init / tgsim_group_matrix) ------------------------
     def groups_init(self, group_of=None, n_groups: Optional[int] = None) -> None:
         """Arms the per-group traffic matrix: group_of[n_peers] names every peer's group (the same

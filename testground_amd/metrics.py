@@ -88,6 +88,33 @@ def ping_lines(report: Dict, bin_ns: int, plan: str, run: str, ts_ns: int) -> Li
     return out
 
 
+FLOW_METRICS = [(f"flow.{k}", k) for k in abi.FLOW_SUMMARY_FIELDS]
+
+
+def flow_lines(report: Dict, bin_ns: int, plan: str, run: str, ts_ns: int) -> List[str]:
+    """The flow report (Engine.flow_report()) in the shape of lines(): one line per summary field (the
+    FCT minimum and maximum only once a flow is DONE) and one per non-zero FCT histogram bin (tag `bin`:
+    the bin's lower edge b * bin_ns in nanoseconds; the last bin holds everything from its edge on).
+
+    `flow.goodput_bps` is bytes_acked * 8 / the mean FCT.  The summary's bytes_acked counts every
+    acknowledged segment, of ACTIVE and FAILED flows too, while the FCT exists for DONE flows only, so
+    the line is written only when every flow is DONE: then it is one flow's own goodput, or the rate
+    the run's flows reached together.  With unfinished or failed flows, take the bytes of the DONE
+    rows from Engine.flow_rows() instead."""
+    tags = f"run={_escape(run)}"
+    out: List[str] = []
+    for name, key in FLOW_METRICS:
+        if key in ("fct_min_ns", "fct_max_ns") and not report["done"]:
+            continue
+        out.append(f"{_escape(f'results.{plan}.{name}')},{tags} value={int(report[key])}i {ts_ns}")
+    if report["done"] and report["done"] == report["flows"] and report["fct_sum_ns"]:
+        goodput = report["bytes_acked"] * 8 * 10**9 * report["done"] // report["fct_sum_ns"]
+        out.append(f"{_escape(f'results.{plan}.flow.goodput_bps')},{tags} value={int(goodput)}i {ts_ns}")
+    meas = _escape(f"results.{plan}.flow.fct_hist")
+    out += [f"{meas},{tags},bin={b * int(bin_ns)} value={int(c)}i {ts_ns}" for b, c in enumerate(report["hist"]) if c]
+    return out
+
+
 def group_lines(m: np.ndarray, names, plan: str, run: str, ts_ns: int) -> List[str]:
     """The per-group traffic matrix (Engine.group_matrix(), or workloads.merge_group_matrices of the
     shards') in the shape of lines(): one line per non-zero word of every cell, measurement

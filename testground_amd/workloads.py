@@ -385,6 +385,247 @@ def ping_run(eng, n_windows: int, window: int, collect: bool = False, probe_at=(
 
 
 # ---------------------------------------------------------------------------------------------
+# Reliable transfers: windowed flows with a selective ACK and a retransmission timer per segment
+# (tgsim_flow_init / tgsim_gen_flow, include/tgsim.h; not TCP).  The HIP engine runs the loop on the
+# device; FlowModel is the same loop driven from the host over any engine-shaped object, in plain
+# Python and numpy: the rules of the header and nothing cleverer.
+def flow_table_mesh(n: int, per_source: int, n_seg, seed: int = SEED, start_tick: int = 0) -> np.ndarray:
+    """The sorted flow table of a mesh: every peer sends `per_source` flows to distinct random peers
+    other than itself; n_seg is one number or an array [n * per_source]."""
+    t = np.zeros(n * per_source, dtype=abi.FLOW_SPEC_DTYPE)
+    t["src"] = np.repeat(np.arange(n, dtype=np.uint32), per_source)
+    t["dst"] = ping_targets_mesh(n, per_source, seed).ravel()
+    t["n_seg"] = n_seg
+    t["start_tick"] = start_tick
+    return t
+
+
+class FlowLate(ValueError):
+    """An ACK's or a released segment's tick precedes the window being generated (the engine's -EINVAL)."""
+
+
+class FlowModel:
+    """The flow loop of include/tgsim.h driven from the host: submit / step / verdicts / drain per
+    window.  `flow` holds Engine.flow_init's keywords (seg_len, ack_len, window, rto_ticks,
+    max_attempts and, optionally, bin_ns, n_bins)."""
+
+    def __init__(self, eng, flow: Dict, flows: np.ndarray):
+        self.eng = eng
+        self.flow = dict(dict(bin_ns=0, n_bins=0), **flow)
+        p = self.flow
+        if not (1 <= p["window"] <= 64 and 1 <= p["max_attempts"] <= 16 and p["rto_ticks"] >= 1):
+            raise ValueError("flow: window 1..64, max_attempts 1..16, rto_ticks >= 1")
+        self.spec = np.ascontiguousarray(flows, dtype=abi.FLOW_SPEC_DTYPE)
+        src = self.spec["src"].astype(np.int64)
+        if (np.diff(src) < 0).any():
+            raise ValueError("flow: the table is not sorted by src")
+        self.n = eng.n_peers
+        self.cnt = np.bincount(src, minlength=self.n)
+        if (self.cnt > abi.FLOW_SLOTS).any():
+            raise ValueError(f"flow: more than {abi.FLOW_SLOTS} flows of source {int(np.argmax(self.cnt))}")
+        self.first = np.concatenate([[0], np.cumsum(self.cnt)[:-1]])
+        self.slot = np.arange(len(src)) - self.first[src]
+        self.now = eng.stats()["now_tick"]
+        self.tick_ns = eng.tick_ns
+        nf, w = len(src), p["window"]
+        self.state = np.zeros(nf, dtype=np.int64)
+        self.base = np.zeros(nf, dtype=np.int64)
+        self.acked_segs = [set() for _ in range(nf)]  # acknowledged segments at or above base
+        self.due = np.repeat(self.spec["start_tick"].astype(np.int64)[:, None], w, axis=1)  # ring: seg % window
+        self.att = np.zeros((nf, w), dtype=np.int64)
+        self.acked = np.zeros(nf, dtype=np.int64)
+        self.offered = np.zeros(nf, dtype=np.int64)
+        self.retransmits = np.zeros(nf, dtype=np.int64)
+        self.stale = np.zeros(nf, dtype=np.int64)
+        self.done_ns = np.zeros(nf, dtype=np.int64)
+        self.cal = np.zeros((0, 4), dtype=np.int64)  # tick, responder, requester, data seq
+        self.hist = np.zeros(p["n_bins"], dtype=np.uint64)
+        self.dup_ignored = self.corrupt_ignored = 0
+        # what the run exercised (the tests' conditions): the largest attempt offered, the longest row,
+        # the most windows ahead a calendar entry has been due, segments released onto a wrapped ring,
+        # sources that offered two packets with equal (tick, seq)
+        # (max_ack_row: the most ACKs one receiver offered in a window)
+        self.max_attempt = self.max_row = self.max_ack_row = self.carried_max = self.ring_wraps = self.ties = 0
+        self.tie_sources: set = set()
+        self.windows = 0
+
+    def _next(self, f: int) -> int:
+        return min(self.base[f] + self.flow["window"], int(self.spec["n_seg"][f]))
+
+    def _unacked(self, f: int):
+        return [i for i in range(int(self.base[f]), self._next(f)) if i not in self.acked_segs[f]]
+
+    def window_packets(self, window: int) -> np.ndarray:
+        """The window's offered packets in (src, tick, seq, dst) order: the segments due in it, and the
+        calendar's ACKs due in it, which leave the calendar."""
+        p, win0, win1 = self.flow, self.now, self.now + window
+        if window > p["rto_ticks"]:
+            raise ValueError(f"flow: a window of {window} ticks is longer than rto_ticks {p['rto_ticks']}")
+        w = p["window"]
+        live = np.nonzero(self.state == abi.FLOW_ACTIVE)[0]
+        late = [int(self.cal[:, 0].min())] if len(self.cal) else []
+        late += [int(self.due[f, i % w]) for f in live for i in self._unacked(f)]
+        if late and min(late) < win0:  # nothing is generated, no state changes
+            raise FlowLate(f"flow: a receipt due at tick {min(late)} precedes the window at tick {win0}")
+        rows = []  # src, dst, seq, tick, len
+        for f in live:
+            segs = self._unacked(f)
+            fail = [int(self.due[f, i % w]) for i in segs if self.due[f, i % w] < win1 and self.att[f, i % w] >= p["max_attempts"]]
+            fail_tick = min(fail) if fail else None
+            for i in segs:
+                t, k = int(self.due[f, i % w]), int(self.att[f, i % w])
+                if t >= win1 or (fail_tick is not None and t >= fail_tick):
+                    continue
+                rows.append((int(self.spec["src"][f]), int(self.spec["dst"][f]),
+                             k << abi.FLOW_ATTEMPT_SHIFT | int(self.slot[f]) << abi.FLOW_SLOT_SHIFT | i, t, p["seg_len"]))
+                self.due[f, i % w] = t + p["rto_ticks"]
+                self.att[f, i % w] = k + 1
+                self.offered[f] += 1
+                self.retransmits[f] += k > 0
+                self.max_attempt = max(self.max_attempt, k)
+            if fail_tick is not None:
+                self.state[f] = abi.FLOW_FAILED
+                self.done_ns[f] = fail_tick * self.tick_ns
+        due = self.cal[:, 0] < win1
+        ack, self.cal = self.cal[due], self.cal[~due]
+        rows += [(int(r), int(q), int(s) | abi.FLOW_ACK, int(t), p["ack_len"]) for t, r, q, s in ack]
+        a = np.array(rows, dtype=np.int64).reshape(-1, 5)
+        a = a[np.lexsort((a[:, 1], a[:, 2], a[:, 3], a[:, 0]))]
+        if len(a):
+            self.max_row = max(self.max_row, int(np.bincount(a[:, 0]).max()))
+            if len(ack):
+                self.max_ack_row = max(self.max_ack_row, int(np.bincount(ack[:, 1]).max()))
+            tie = (a[1:, 0] == a[:-1, 0]) & (a[1:, 3] == a[:-1, 3]) & (a[1:, 2] == a[:-1, 2])
+            self.ties += int(tie.sum())
+            self.tie_sources.update(np.unique(a[1:, 0][tie]).tolist())
+        pk = np.zeros(len(a), dtype=abi.PKT_DTYPE)
+        pk["src"], pk["dst"], pk["seq"], pk["tick"], pk["len"] = a[:, 0], a[:, 1], a[:, 2], a[:, 3] - win0, a[:, 4]
+        return pk
+
+    def _flow_of(self, sender: int, seq: int, peer: int):
+        """The flow of `sender` that seq names, when its dst is `peer` and the segment exists; else None."""
+        slot, seg = seq >> abi.FLOW_SLOT_SHIFT & 15, seq & abi.FLOW_SEG_MASK
+        if sender >= self.n or slot >= self.cnt[sender]:
+            return None
+        f = int(self.first[sender] + slot)
+        if int(self.spec["dst"][f]) != peer or seg >= int(self.spec["n_seg"][f]):
+            return None
+        return f
+
+    def receive(self, d: np.ndarray) -> None:
+        """Folds one window's drained records, in drain order (dst, t_ns, src, seq): data segments into
+        the ACK calendar, ACKs into their flows."""
+        p, w = self.flow, self.flow["window"]
+        new = []
+        for flags, seq, t_ns, src, dst in zip(*(d[k].tolist() for k in ("flags", "seq", "t_ns", "src", "dst"))):
+            if flags & abi.FLAG_DUP:
+                self.dup_ignored += 1
+                continue
+            if flags & abi.FLAG_CORRUPT:
+                self.corrupt_ignored += 1
+                continue
+            tick = t_ns // self.tick_ns + 1
+            if not seq & abi.FLOW_ACK:
+                if self._flow_of(src, seq, dst) is not None:
+                    new.append((tick, dst, src, seq))
+                continue
+            f = self._flow_of(dst, seq, src)
+            if f is None:
+                continue
+            seg, n_seg = seq & abi.FLOW_SEG_MASK, int(self.spec["n_seg"][f])
+            nxt = self._next(f)
+            if self.state[f] != abi.FLOW_ACTIVE or seg < self.base[f] or seg >= nxt or seg in self.acked_segs[f]:
+                self.stale[f] += 1
+                continue
+            self.acked_segs[f].add(seg)
+            self.acked[f] += 1
+            while int(self.base[f]) in self.acked_segs[f]:
+                self.acked_segs[f].discard(int(self.base[f]))
+                self.base[f] += 1
+            for i in range(nxt, self._next(f)):  # the segments that entered the window
+                self.due[f, i % w], self.att[f, i % w] = tick, 0
+                self.ring_wraps += i >= w
+            if self.base[f] == n_seg:
+                self.state[f] = abi.FLOW_DONE
+                self.done_ns[f] = t_ns
+                if p["n_bins"]:
+                    fct = t_ns - int(self.spec["start_tick"][f]) * self.tick_ns
+                    self.hist[min(fct // p["bin_ns"], p["n_bins"] - 1)] += 1
+        self.cal = np.concatenate([self.cal, np.array(new, dtype=np.int64).reshape(-1, 4)])
+
+    def step(self, window: int) -> Tuple[np.ndarray, np.ndarray]:
+        pk = self.window_packets(window)
+        if len(pk):
+            self.eng.submit(pk)
+        self.eng.step(window)
+        self.now += window
+        v, d = self.eng.verdicts(), self.eng.drain()
+        self.receive(d)
+        self.windows += 1
+        if len(self.cal):  # 1: due in the next window; 2 and more: moved to the other calendar buffer first
+            self.carried_max = max(self.carried_max, int((self.cal[:, 0].max() - self.now) // window) + 1)
+        return v, d
+
+    def rows(self) -> np.ndarray:
+        out = np.zeros(len(self.spec), dtype=abi.FLOW_ROW_DTYPE)
+        for key, v in (("state", self.state), ("acked", self.acked), ("offered", self.offered),
+                       ("retransmits", self.retransmits), ("stale_acks", self.stale), ("base", self.base),
+                       ("done_ns", self.done_ns)):
+            out[key] = v
+        return out
+
+    def fct(self) -> np.ndarray:
+        """Flow completion times of the DONE flows, ns."""
+        done = self.state == abi.FLOW_DONE
+        return self.done_ns[done] - self.spec["start_tick"][done].astype(np.int64) * self.tick_ns
+
+    def report(self) -> Dict:
+        fct = self.fct()
+        return {"flows": len(self.spec), "done": int((self.state == abi.FLOW_DONE).sum()),
+                "failed": int((self.state == abi.FLOW_FAILED).sum()), "active": int((self.state == abi.FLOW_ACTIVE).sum()),
+                "segs_acked": int(self.acked.sum()), "bytes_acked": int(self.acked.sum()) * self.flow["seg_len"],
+                "data_offered": int(self.offered.sum()), "retransmits": int(self.retransmits.sum()),
+                "stale_acks": int(self.stale.sum()), "dup_ignored": self.dup_ignored,
+                "corrupt_ignored": self.corrupt_ignored, "pending_acks": len(self.cal),
+                "fct_sum_ns": int(fct.sum()), "fct_min_ns": int(fct.min()) if len(fct) else int(np.iinfo(np.uint64).max),
+                "fct_max_ns": int(fct.max()) if len(fct) else 0, "hist": self.hist.copy()}
+
+
+def flow_reference(eng, flow: Dict, flows: np.ndarray, n_windows: int, window: int, probe_at=(), before=None) -> Dict:
+    """The flow loop driven from the host over `eng` (submit / step / verdicts / drain): per-window
+    (verdicts, deliveries) under "windows", the final "rows" and "summary" (report fields and hist),
+    and under "probes" the (rows, summary) after each window index in probe_at.  before(w) runs ahead
+    of window w (a reshape, a partition).  The model itself is under "model"."""
+    m = FlowModel(eng, flow, flows)
+    out = {"windows": [], "probes": {}, "model": m}
+    for w in range(n_windows):
+        if before is not None:
+            before(w)
+        out["windows"].append(m.step(window))
+        if w in probe_at:
+            out["probes"][w] = (m.rows(), m.report())
+    out["rows"], out["summary"] = m.rows(), m.report()
+    return out
+
+
+def flow_run(eng, n_windows: int, window: int, collect: bool = False, probe_at=(), before=None) -> Dict:
+    """The device loop on an armed engine (Engine.flow_init): n_windows of gen_flow + step.  Nothing
+    reaches the host unless asked for: collect keeps each window's (verdicts, deliveries), probe_at
+    the (rows, report) after those windows."""
+    out = {"windows": [], "probes": {}}
+    for w in range(n_windows):
+        if before is not None:
+            before(w)
+        eng.gen_flow(window)
+        eng.step(window)
+        if collect:
+            out["windows"].append((eng.verdicts(), eng.drain()))
+        if w in probe_at:
+            out["probes"][w] = (eng.flow_rows(), eng.flow_report())
+    return out
+
+
+# ---------------------------------------------------------------------------------------------
 # Per-group traffic matrix (tgsim_groups_init / tgsim_group_matrix, include/tgsim.h): the host model
 # the device's folds are compared with, in numpy: the word definitions and nothing cleverer.
 class GroupMatrix:
