@@ -471,7 +471,8 @@ int64_t tgsim_ping_pairs(void* engine, uint32_t peer, uint32_t n, tgsim_ping_pai
 /* ---- reliable transfers (windowed flows, per-segment ACKs and retransmission timers) --------- */
 /* "Send n_seg segments reliably from a to b" as a closed loop on the device: how
  * long a transfer takes and what goodput it reaches on links with this latency, loss, bandwidth and
- * netem queue limit.  It is NOT TCP: no handshake, no congestion control, no cumulative ACK.  A fixed
+ * netem queue limit.  It is NOT TCP: no handshake, no congestion control (unless
+ * armed with tgsim_flow_init_cc, further down), no cumulative ACK.  A fixed
  * window, a selective ACK per delivered segment, a retransmission timer per segment: the smallest
  * protocol that completes under loss, saturates a link whose bandwidth-delay product the window
  * covers, and is a pure function of the delivered records.
@@ -571,6 +572,78 @@ int64_t tgsim_flow_report(void* engine, tgsim_flow_summary* out, uint64_t* hist,
 /* The rows of flows [first, first + n) of the table; returns the rows written, -EINVAL for a range
  * outside the table, -ENOSPC when cap < n (as tgsim_ping_pairs). */
 int64_t tgsim_flow_rows(void* engine, uint64_t first, uint64_t n, tgsim_flow_row* out, size_t cap);
+
+/* ---- congestion control of the flow driver (opt-in per arming) --------------- */
+/* An AIMD congestion window and a fast retransmit on top of the rules above: how transfers back off
+ * and share a shaped link, what goodput survives loss, what happens when one instance's connections
+ * overrun the netem queue.  Armed with tgsim_flow_init_cc and a non-NULL cc; without it every rule
+ * above holds as written.  With it, `window` is the cap of the congestion window (the receiver
+ * window), and everything above that is not named here stays as written: the seq layout, the ACK
+ * leg, the stale rule, the fail rule by tick, the order, the loop and late rule, and verdicts
+ * teaching the sender nothing.
+ *
+ *   State     per flow, beside the row: cwnd (1..window), ssthresh (2..max(window, 2)), cwnd_cnt, next
+ *             (lowest segment never released; now stored), recover, and the counters loss_events,
+ *             fast_retransmits, timeouts: the 32-B tgsim_flow_cc_row.  Per in-flight segment a FAST
+ *             flag beside its attempt count.
+ *   Invariant base <= next <= min(base + window, n_seg): the timers' ring (segment mod window) and the
+ *             64-bit bitmap hold as before.
+ *   Arming    cwnd = init_cwnd, ssthresh = init_ssthresh ? init_ssthresh : window, next =
+ *             min(init_cwnd, n_seg), recover = 0, cwnd_cnt = 0; the segments [0, next) are due at
+ *             start_tick with attempt 0.
+ *   In flight [base, next), wherever the rules above say [base, min(base + window, n_seg)): the offer
+ *             pass, the late test and the stale test (seg >= next).
+ *   Receipt   of a non-stale ACK of seg delivered at d, tick = floor(d / tick_ns) + 1, in this order:
+ *             1. the segment is marked acknowledged, acked += 1;
+ *             2. base advances over the acknowledged prefix;
+ *             3. growth, only when base >= recover: cwnd += 1 when cwnd < ssthresh; otherwise
+ *                cwnd_cnt += 1, and when cwnd_cnt >= cwnd then cwnd += 1 and cwnd_cnt = 0; then cwnd =
+ *                min(cwnd, window);
+ *             4. fast retransmit, when dupthresh > 0: every unacknowledged segment i of [base, next),
+ *                in ascending order, with at least dupthresh acknowledged segments above it, an attempt
+ *                count of exactly 1, no FAST flag and a due tick > tick, gets due = tick and the FAST
+ *                flag, fast_retransmits += 1; when i >= recover that is a loss event: ssthresh =
+ *                max(cwnd / 2, 2), cwnd = ssthresh, cwnd_cnt = 0, recover = next, loss_events += 1;
+ *             5. release: next2 = max(next, min(base + cwnd, n_seg)); the segments [next, next2) get
+ *                due = tick, attempt 0, no flag; next = next2;
+ *             6. base == n_seg makes the flow DONE, as above.
+ *   Offer     as above.  The retransmission of a FAST segment carries attempt 1 in its seq; its timer
+ *             restarts at its tick + rto_ticks, its attempt count becomes 2 and the flag clears.  An
+ *             offer with attempt k > 0 and no FAST flag is a timeout, timeouts += 1.  When a timeout of
+ *             this generation has seg >= recover (recover as it was before the generation, so the order
+ *             the segments are walked in does not matter), that is one loss event of the flow in this
+ *             generation: ssthresh = max(cwnd / 2, 2), cwnd = 1, cwnd_cnt = 0, recover = next,
+ *             loss_events += 1.  A late window still changes no state, the cc rows included.  A
+ *             FAST segment is due like any other: with max_attempts == 1 it fails the flow at its tick.
+ *   Step      as above, the counters and the windows depend on the step length, the fail tick does not.
+ *   Not here  an RTT estimator, timer backoff, cumulative or delayed ACKs, pacing, and failing at once
+ *             on a BLACKHOLE or PROHIBIT verdict (still the follow-up DESIGN.md §5.8 names). */
+typedef struct {
+    uint32_t init_cwnd;     /* 1..window: segments released at start_tick                  */
+    uint32_t init_ssthresh; /* 0 -> window; else 2..window                                  */
+    uint32_t dupthresh;     /* 0: timer only; 1..63: fast retransmit after this many        */
+                            /* acknowledged segments above a hole                           */
+    uint32_t _pad;
+} tgsim_flow_cc;            /* 16 B */
+typedef struct {            /* one flow; 32 B */
+    uint32_t cwnd, ssthresh, next, recover, cwnd_cnt;
+    uint32_t loss_events, fast_retransmits, timeouts;
+} tgsim_flow_cc_row;
+typedef struct {            /* 64 B */
+    uint64_t loss_events, fast_retransmits, timeouts;
+    uint64_t active, cwnd_sum, cwnd_min /* UINT64_MAX when none */, cwnd_max; /* over ACTIVE flows */
+    uint64_t _pad;
+} tgsim_flow_cc_summary;
+/* tgsim_flow_init with congestion control: every arming, busy and disarm rule of tgsim_flow_init
+ * holds, cc == NULL is tgsim_flow_init itself, and a bad cc field is -EINVAL with a tgsim_last_error
+ * text that names the field and its value. */
+int tgsim_flow_init_cc(void* engine, const tgsim_flow* p, const tgsim_flow_cc* cc,
+                       const tgsim_flow_spec* flows, uint64_t n_flows);
+/* The cc rows of flows [first, first + n), and the cc summary reduced on the device.  -EINVAL
+ * ("congestion control is not armed") when flows are armed without cc or not at all; otherwise they
+ * synchronize, and fail, like tgsim_flow_rows and tgsim_flow_report. */
+int64_t tgsim_flow_cc_rows(void* engine, uint64_t first, uint64_t n, tgsim_flow_cc_row* out, size_t cap);
+int     tgsim_flow_cc_report(void* engine, tgsim_flow_cc_summary* out);
 
 /* ---- per-group traffic matrix (who offered what to whom, and what became of it) -------------- */
 /* Every peer belongs to one group (a region, a composition group); the engine folds each window's

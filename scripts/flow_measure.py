@@ -7,6 +7,13 @@
            rocprofv3 --kernel-trace --output-format csv -d DIR -o run -- python scripts/flow_measure.py run
   trace  per-kernel device time of the k_flow_* and shared k_ping_* kernels in such a trace (max_us: the
          busy windows, see below), beside the HBM floor of a busy window
+  steady the device loop alone: wall time per window and the median over the steady windows (the A/B
+         figure: run it with TGSIM_LIB naming another build of the library)
+  curve  goodput per flow against link loss, with and without congestion control (the README's table)
+
+`--cc` arms run, steady and trace with congestion control (init_cwnd 2, dupthresh 3,
+the cap `window` as without) and `--loss PCT` puts that loss on every link; with either the run takes
+CC_WINDOWS windows, since the windows open from 2 segments and lost ones wait for a timer.
 
 Every link 5 ms, lossless, unlimited, reorder off; 800,000 flows of 64 segments of 1,000 bytes, window
 8, ACKs of 64 bytes, a timer of 20 ms that never fires; windows of 5,000 ticks.  Every flow starts at
@@ -33,24 +40,30 @@ FLOW = dict(seg_len=1000, ack_len=64, window=8, rto_ticks=20_000, max_attempts=4
 WINDOWS, STEADY = 18, range(2, 14)  # 8 round trips of two windows each, the last ACKs in window 15
 HOST_WINDOWS, HOST_STEADY = 4, range(2, 4)
 HBM_BPS = 6.3e12  # the measured rate DESIGN.md §5.5 uses
+CC = dict(init_cwnd=2, init_ssthresh=0, dupthresh=3)
+CC_WINDOWS, CC_STEADY = 44, range(8, 24)  # from 2 segments: 2, 4, then 8 a round trip; every flow ACTIVE in these windows
+# curve: 10,000 peers, 8 flows each of 64 segments over links of 5 ms and 10 Mbit/s (a source's 8 flows share
+# the link: 12.5 KB of bandwidth-delay product against 64 KB of fixed windows), a timer of 60 ms
+CURVE = dict(n=10_000, rate_bps=10_000_000, rto_ticks=60_000, max_windows=1200, losses=(0.0, 0.5, 1.0, 2.0, 4.0))
 OFFSETS = np.array([1, 17, 263, 4099, 9973, 31337, 54321, 77777])
 
 
-def flow_table():
-    t = wl.flow_table_mesh(N, PER_SOURCE, N_SEG, seed=9)
-    t["dst"] = (t["src"].astype(np.int64) + np.tile(OFFSETS, N)) % N
+def flow_table(n=N):
+    t = wl.flow_table_mesh(n, PER_SOURCE, N_SEG, seed=9)
+    t["dst"] = (t["src"].astype(np.int64) + np.tile(OFFSETS % n, n)) % n
     return t
 
 
-def engine(flags):
-    eng = Engine(N, lookahead_ns=LAT, flags=flags)
-    eng.configure_batch(np.arange(N), nw.configs_array(np.full(N, LAT)))
+def engine(flags, loss=0.0, n=N, rate_bps=0):
+    eng = Engine(n, lookahead_ns=LAT, flags=flags)
+    eng.configure_batch(np.arange(n), nw.configs_array(np.full(n, LAT), loss=np.full(n, loss, dtype=np.float32),
+                                                       bandwidth_bps=np.full(n, rate_bps)))
     return eng
 
 
-def device_loop(windows=WINDOWS):
-    eng, t = engine(abi.OPT_DISCARD_DELIVERIES), []
-    eng.flow_init(flow_table(), **FLOW)
+def device_loop(windows=WINDOWS, cc=None, loss=0.0):
+    eng, t = engine(abi.OPT_DISCARD_DELIVERIES, loss), []
+    eng.flow_init(flow_table(), cc=cc, **FLOW)
     for w in range(windows):
         eng.sync()
         t0 = time.perf_counter()
@@ -58,7 +71,34 @@ def device_loop(windows=WINDOWS):
         eng.step(WIN)
         eng.sync()
         t.append(time.perf_counter() - t0)
-    return eng.flow_report(), t
+    rep = eng.flow_report()
+    if cc is not None:
+        rep["cc"] = eng.flow_cc_report()
+    return rep, t
+
+
+def curve_point(loss, cc):
+    """One run of the curve's table to the end (or max_windows): the mean over the DONE flows of their own
+    goodput, bytes * 8 / FCT."""
+    n = CURVE["n"]
+    eng = engine(abi.OPT_DISCARD_DELIVERIES, loss, n, CURVE["rate_bps"])
+    eng.flow_init(flow_table(n), cc=cc, **dict(FLOW, rto_ticks=CURVE["rto_ticks"], max_attempts=16, n_bins=0, bin_ns=0))
+    windows = 0
+    while windows < CURVE["max_windows"]:
+        wl.flow_run(eng, 40, WIN)
+        windows += 40
+        if eng.flow_report()["active"] == 0:
+            break
+    rows, rep = eng.flow_rows(), eng.flow_report()
+    done = rows[rows["state"] == abi.FLOW_DONE]
+    goodput = N_SEG * FLOW["seg_len"] * 8e9 / done["done_ns"].astype(np.float64) if len(done) else np.zeros(1)
+    out = {"loss_pct": loss, "cc": cc is not None, "windows": windows, "done": int(rep["done"]), "failed": int(rep["failed"]),
+           "active": int(rep["active"]), "goodput_bps_per_flow_mean": round(float(goodput.mean())),
+           "fct_ms_mean": round(float(done["done_ns"].mean()) / 1e6, 2) if len(done) else None,
+           "retransmits_per_segment": round(rep["retransmits"] / max(rep["segs_acked"], 1), 4)}
+    if cc is not None:
+        out["cc"] = eng.flow_cc_report()
+    return out
 
 
 def host_loop(windows=HOST_WINDOWS):
@@ -73,8 +113,23 @@ def host_loop(windows=HOST_WINDOWS):
 
 def main():
     mode = sys.argv[1]
+    cc = CC if "--cc" in sys.argv else None
+    loss = float(sys.argv[sys.argv.index("--loss") + 1]) if "--loss" in sys.argv else 0.0
+    windows, steady = (CC_WINDOWS, CC_STEADY) if cc is not None or loss else (WINDOWS, STEADY)
     if mode == "run":
-        print(json.dumps({k: int(v) for k, v in device_loop()[0].items() if k != "hist"}))
+        print(json.dumps({k: v for k, v in device_loop(windows, cc, loss)[0].items() if k != "hist"}))
+    elif mode == "steady":
+        rep, td = device_loop(windows, cc, loss)
+        print(json.dumps({"cc": cc, "loss_pct": loss, "windows": windows, "steady": [steady[0], steady[-1]],
+                          "report": {k: v for k, v in rep.items() if k != "hist"},
+                          "device_ms_per_window": [round(1e3 * x, 3) for x in td],
+                          "device_steady_ms": round(1e3 * statistics.median(td[w] for w in steady), 3),
+                          "device_steady_min_max_ms": [round(1e3 * min(td[w] for w in steady), 3),
+                                                       round(1e3 * max(td[w] for w in steady), 3)]}))
+    elif mode == "curve":
+        for loss_pct in CURVE["losses"]:
+            for c in (None, CC):
+                print(json.dumps(curve_point(loss_pct, c)), flush=True)
     elif mode == "wall":
         dev, td = device_loop()
         short, _ = device_loop(HOST_WINDOWS)
@@ -92,15 +147,17 @@ def main():
     elif mode == "trace":
         per = {}
         for r in csv.DictReader(open(sys.argv[2])):
-            name = r["Kernel_Name"].split("(")[0].split("::")[-1]
+            name = r["Kernel_Name"].split("(")[0].split("::")[-1].split()[-1].split("<")[0]  # (void k_flow_write<true>(...))
             if name.startswith(("k_flow_", "k_ping_")) or name in ("k_sim_sparse", "k_sim", "k_sim_list", "k_sim_multi"):
                 per.setdefault(name, []).append((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3)
         flows, w = N * PER_SOURCE, FLOW["window"]
         seg = flows * w  # the windows alternate: a busy window carries 6.4 M segments or their 6.4 M ACKs
-        state = flows * (16 + 32 + 8 + w * 5)  # spec, row, bitmap, timers
+        ccb = 32 if cc is not None else 0  # the cc row beside the flow row
+        state = flows * (16 + 32 + ccb + 8 + w * 5)  # spec, row, bitmap, timers
         floors = {"k_flow_recv_data": seg * 24 + seg * 16,          # a window of segments read, an entry each written
-                  "k_flow_recv_ack": seg * 24 + flows * (16 + 2 * 32 + 2 * 8) + seg * 5,  # ACKs once, state in and out, timers
-                  "k_flow_count": state, "k_flow_write": state + seg * 16 + seg * 5 + flows * 32,
+                  "k_flow_recv_ack": seg * 24 + flows * (16 + 2 * (32 + ccb) + 2 * 8) + seg * 5,  # ACKs once, state in and out, timers
+                  "k_flow_count": state, "k_flow_write": state + seg * 16 + seg * 5 + flows * (32 + ccb),
+                  "k_flow_cc_report": flows * (32 + 32),  # the cc row, and the flow row for its state
                   "k_ping_count_cal": seg * 16, "k_ping_write_cal": seg * 16 + seg * 16, "k_ping_order": seg * 16 * 2}
         out = {}
         for name, us in sorted(per.items()):

@@ -156,6 +156,20 @@ class FlowSummary(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in FLOW_SUMMARY_FIELDS]
 
 
+# Congestion control of the flow driver (tgsim_flow_init_cc); bit 7 of a segment's attempt byte is its FAST flag.
+class FlowCC(C.Structure):
+    _fields_ = [("init_cwnd", C.c_uint32), ("init_ssthresh", C.c_uint32), ("dupthresh", C.c_uint32), ("_pad", C.c_uint32)]
+
+
+FLOW_CC_ROW_DTYPE = np.dtype([("cwnd", "<u4"), ("ssthresh", "<u4"), ("next", "<u4"), ("recover", "<u4"), ("cwnd_cnt", "<u4"),
+                              ("loss_events", "<u4"), ("fast_retransmits", "<u4"), ("timeouts", "<u4")])
+FLOW_CC_SUMMARY_FIELDS = ("loss_events", "fast_retransmits", "timeouts", "active", "cwnd_sum", "cwnd_min", "cwnd_max")
+
+
+class FlowCCSummary(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in FLOW_CC_SUMMARY_FIELDS + ("_pad",)]
+
+
 # Per-group traffic matrix (tgsim_groups_init / tgsim_group_matrix): the words of a cell.
 GROUP_MAX = 64
 GROUP_WORDS = 14
@@ -188,6 +202,7 @@ assert C.sizeof(GossipFlood) == 24 and GOSSIP_FLOOD_DTYPE.itemsize == 24
 assert C.sizeof(Ping) == 40 and PING_PAIR_DTYPE.itemsize == 32 and C.sizeof(PingSummary) == 88
 assert C.sizeof(Flow) == 32 and FLOW_SPEC_DTYPE.itemsize == 16 and FLOW_ROW_DTYPE.itemsize == 32
 assert C.sizeof(FlowSummary) == 120
+assert C.sizeof(FlowCC) == 16 and FLOW_CC_ROW_DTYPE.itemsize == 32 and C.sizeof(FlowCCSummary) == 64
 assert C.sizeof(CommInfo) == 72 and C.sizeof(Gossip) == 24 and C.sizeof(Opts) == 56 and C.sizeof(Shape) == 56 and C.sizeof(Config) == 104
 
 # Every symbol include/tgsim.h declares (checked by tests/test_abi.py).
@@ -205,6 +220,7 @@ EXPORTS = [
     "tgsim_gossip_times", "tgsim_metrics",
     "tgsim_ping_init", "tgsim_gen_ping", "tgsim_ping_report", "tgsim_ping_pairs",
     "tgsim_flow_init", "tgsim_gen_flow", "tgsim_flow_report", "tgsim_flow_rows",
+    "tgsim_flow_init_cc", "tgsim_flow_cc_rows", "tgsim_flow_cc_report",
     "tgsim_groups_init", "tgsim_group_matrix",
     "tgsim_comm_id", "tgsim_comm_init", "tgsim_comm_step", "tgsim_comm_launch", "tgsim_comm_finish", "tgsim_comm_run", "tgsim_comm_barrier", "tgsim_comm_info",
     "tgsim_bridge_create", "tgsim_bridge_destroy", "tgsim_bridge_send", "tgsim_bridge_step",
@@ -284,6 +300,9 @@ def declare(lib: C.CDLL, prefix: str) -> None:
     f("gen_flow", C.c_int, vp, C.c_uint32)
     f("flow_report", C.c_int64, vp, C.POINTER(FlowSummary), C.c_void_p, C.c_size_t)
     f("flow_rows", C.c_int64, vp, C.c_uint64, C.c_uint64, C.c_void_p, C.c_size_t)
+    f("flow_init_cc", C.c_int, vp, C.POINTER(Flow), C.POINTER(FlowCC), C.c_void_p, C.c_uint64)
+    f("flow_cc_rows", C.c_int64, vp, C.c_uint64, C.c_uint64, C.c_void_p, C.c_size_t)
+    f("flow_cc_report", C.c_int, vp, C.POINTER(FlowCCSummary))
     f("groups_init", C.c_int, vp, C.c_void_p, C.c_uint32)
     f("group_matrix", C.c_int64, vp, C.c_void_p, C.c_size_t, C.c_int)
     f("offered", C.c_int64, vp, C.c_void_p, C.c_size_t)

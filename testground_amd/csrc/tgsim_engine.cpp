@@ -481,6 +481,9 @@ struct tgsim_engine_s {
   DevBuf<uint64_t> d_fbits;
   DevBuf<uint32_t> d_fdue, d_ffirst, d_fcnt;
   DevBuf<uint8_t> d_fatt;
+  bool flow_cc_on = false;       // armed by tgsim_flow_init_cc with a cc
+  tgsim_flow_cc flow_cc{};
+  DevBuf<tgsim_flow_cc_row> d_fcc;
   hipEvent_t ev_flow = nullptr;  // after the last k_flow_recv_ack (delivery stream)
 
   // per-group traffic matrix (tgsim_groups_init / tgsim_group_matrix)
@@ -1526,8 +1529,9 @@ int ping_recv(Eng* E, const tgsim_delivery* recs, const uint64_t* off, uint32_t 
 void flow_release(Eng* E) {
   ping_release(E);
   E->d_fspec.release(); E->d_frow.release(); E->d_fbits.release(); E->d_fdue.release(); E->d_ffirst.release();
-  E->d_fcnt.release(); E->d_fatt.release();
+  E->d_fcnt.release(); E->d_fatt.release(); E->d_fcc.release();
   E->flow_on = false;
+  E->flow_cc_on = false;
   E->flow_late = false;
 }
 
@@ -1559,6 +1563,10 @@ FlowArgs flow_args(Eng* E, uint64_t win0, uint32_t n_ticks) {
   f.window = E->flow.window;
   f.rto = E->flow.rto_ticks;
   f.max_attempts = E->flow.max_attempts;
+  f.cc = E->flow_cc_on ? E->d_fcc.p : nullptr;
+  f.init_cwnd = E->flow_cc.init_cwnd;
+  f.init_ssthresh = E->flow_cc.init_ssthresh;
+  f.dupthresh = E->flow_cc.dupthresh;
   return f;
 }
 
@@ -2896,6 +2904,11 @@ int64_t tgsim_ping_pairs(void* e, uint32_t peer, uint32_t n, tgsim_ping_pair* ou
 
 // Flow driver (include/tgsim.h).
 int tgsim_flow_init(void* e, const tgsim_flow* p, const tgsim_flow_spec* flows, uint64_t n_flows) {
+  return tgsim_flow_init_cc(e, p, nullptr, flows, n_flows);
+}
+
+int tgsim_flow_init_cc(void* e, const tgsim_flow* p, const tgsim_flow_cc* cc, const tgsim_flow_spec* flows,
+                       uint64_t n_flows) {
   Eng* E = as_eng(e);
   if (!E) return -EINVAL;
   HIPCHK(hipSetDevice(E->dev));
@@ -2917,6 +2930,13 @@ int tgsim_flow_init(void* e, const tgsim_flow* p, const tgsim_flow_spec* flows, 
   if (p->max_attempts == 0 || p->max_attempts > 16) return E->fail(-EINVAL, "flow: max_attempts %u outside 1..16", p->max_attempts);
   if (p->n_bins > kPingMaxBins) return E->fail(-EINVAL, "flow: n_bins %u above %u", p->n_bins, kPingMaxBins);
   if (p->n_bins && p->bin_ns == 0) return E->fail(-EINVAL, "flow: bin_ns 0 with %u bins", p->n_bins);
+  if (cc) {
+    if (cc->init_cwnd == 0 || cc->init_cwnd > p->window)
+      return E->fail(-EINVAL, "flow: init_cwnd %u outside 1..window (%u)", cc->init_cwnd, p->window);
+    if (cc->init_ssthresh && (cc->init_ssthresh < 2 || cc->init_ssthresh > p->window))
+      return E->fail(-EINVAL, "flow: init_ssthresh %u neither 0 nor in 2..window (%u)", cc->init_ssthresh, p->window);
+    if (cc->dupthresh > 63) return E->fail(-EINVAL, "flow: dupthresh %u outside 0..63", cc->dupthresh);
+  }
   if (n_flows > static_cast<uint64_t>(E->N) * TGSIM_FLOW_SLOTS)
     return E->fail(-EINVAL, "flow: %llu flows for %u peers (at most %u per source)", static_cast<unsigned long long>(n_flows), E->N,
                    TGSIM_FLOW_SLOTS);
@@ -2959,6 +2979,9 @@ int tgsim_flow_init(void* e, const tgsim_flow* p, const tgsim_flow_spec* flows, 
   E->flow = *p;
   E->n_flows = n_flows;
   E->flow_offered = 0;
+  E->flow_cc_on = cc != nullptr;
+  E->flow_cc = cc ? *cc : tgsim_flow_cc{};
+  if (cc) HIPCHK(E->d_fcc.ensure_exact(n_flows));
   E->ping_cur = 0;
   E->ping_kept = 0;
   E->ping_appended = 0;
@@ -3112,6 +3135,48 @@ int64_t tgsim_flow_rows(void* e, uint64_t first, uint64_t n, tgsim_flow_row* out
   HIPCHK(hipMemcpyAsync(out, E->d_frow.p + first, sizeof(tgsim_flow_row) * n, hipMemcpyDeviceToHost, E->st));
   HIPCHK(hipStreamSynchronize(E->st));
   return static_cast<int64_t>(n);
+}
+
+int64_t tgsim_flow_cc_rows(void* e, uint64_t first, uint64_t n, tgsim_flow_cc_row* out, size_t cap) {
+  Eng* E = as_eng(e);
+  if (!E) return -EINVAL;
+  if (!E->flow_on || !E->flow_cc_on) return E->fail(-EINVAL, "flow_cc_rows: congestion control is not armed (tgsim_flow_init_cc)");
+  if (first > E->n_flows || n > E->n_flows - first)
+    return E->fail(-EINVAL, "flow_cc_rows: flows [%llu, %llu) outside [0, %llu)", static_cast<unsigned long long>(first),
+                   static_cast<unsigned long long>(first + n), static_cast<unsigned long long>(E->n_flows));
+  if (cap < n) return E->fail(-ENOSPC, "flow_cc_rows: %zu rows for %llu", cap, static_cast<unsigned long long>(n));
+  if (n && !out) return E->fail(-EINVAL, "flow_cc_rows: no output buffer");
+  HIPCHK(hipSetDevice(E->dev));
+  int rc = sync_stream(E);
+  if (rc) return rc;
+  if (!n) return 0;
+  HIPCHK(hipMemcpyAsync(out, E->d_fcc.p + first, sizeof(tgsim_flow_cc_row) * n, hipMemcpyDeviceToHost, E->st));
+  HIPCHK(hipStreamSynchronize(E->st));
+  return static_cast<int64_t>(n);
+}
+
+int tgsim_flow_cc_report(void* e, tgsim_flow_cc_summary* out) {
+  Eng* E = as_eng(e);
+  if (!E) return -EINVAL;
+  if (!E->flow_on || !E->flow_cc_on) return E->fail(-EINVAL, "flow_cc_report: congestion control is not armed (tgsim_flow_init_cc)");
+  if (!out) return E->fail(-EINVAL, "flow_cc_report: no summary buffer");
+  HIPCHK(hipSetDevice(E->dev));
+  int rc = sync_stream(E);  // the receipts of the last delivery are folded on the delivery stream
+  if (rc) return rc;
+  launch_flow_cc_report(flow_args(E, 0, 0), E->d_pres.p, E->st);
+  HIPCHK(hipGetLastError());
+  unsigned long long res[kFlowCcResWords];
+  HIPCHK(hipMemcpyAsync(res, E->d_pres.p, sizeof res, hipMemcpyDeviceToHost, E->st));
+  HIPCHK(hipStreamSynchronize(E->st));
+  *out = tgsim_flow_cc_summary{};
+  out->loss_events = res[0];
+  out->fast_retransmits = res[1];
+  out->timeouts = res[2];
+  out->active = res[3];
+  out->cwnd_sum = res[4];
+  out->cwnd_min = res[5];
+  out->cwnd_max = res[6];
+  return 0;
 }
 
 // Per-group traffic matrix (include/tgsim.h).

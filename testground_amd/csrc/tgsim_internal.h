@@ -370,7 +370,11 @@ struct FlowArgs {
   const uint32_t* cnt;          // [n_peers] its flows (<= TGSIM_FLOW_SLOTS)
   uint64_t n_flows;
   uint32_t seg_len, window, rto, max_attempts;
+  // congestion control (tgsim_flow_init_cc); cc == nullptr: armed without it
+  tgsim_flow_cc_row* cc;        // [n_flows]
+  uint32_t init_cwnd, init_ssthresh, dupthresh;
 };
+constexpr uint32_t kFlowCcResWords = 7;  // loss_events fast_retransmits timeouts active cwnd_sum cwnd_min cwnd_max
 
 // Per-group traffic matrix (tgsim_groups_init / tgsim_group_matrix).
 constexpr uint32_t kGroupWords = TGSIM_GROUP_WORDS, kGroupMax = TGSIM_GROUP_MAX;

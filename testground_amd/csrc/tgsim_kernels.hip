@@ -3493,12 +3493,29 @@ __global__ __launch_bounds__(256) void k_flow_recv_data(FlowArgs f, const tgsim_
   }
 }
 
+// Congestion control (tgsim_flow_init_cc).  The kernels below are templates on CC:
+// the CC = false instantiation is the fixed-window driver as it was, the CC = true one loads and
+// stores the flow's 32-B cc row beside its 32-B flow row, in the same lane.  An attempt byte keeps
+// the attempt count in its low five bits (0..16) and the FAST flag in bit 7.
+constexpr uint32_t kFlowAttMask = 31u, kFlowFast = 128u;
+
+// The fast-retransmit candidates of a bitmap (bit i: segment base + i acknowledged): the clear bits
+// below the position of the dupthresh-th highest set bit, or none with fewer set bits.  The loop
+// clears dupthresh - 1 set bits, fewer than `window` of them.
+__device__ __forceinline__ uint64_t flow_fast_mask(uint64_t bm, uint32_t dupthresh) {
+  if ((uint32_t)__popcll(bm) < dupthresh) return 0ull;
+  uint64_t m = bm;
+  for (uint32_t k = 1; k < dupthresh; ++k) m &= ~(1ull << (63 - __builtin_clzll(m)));
+  return ~bm & ((1ull << (63 - __builtin_clzll(m))) - 1ull);
+}
+
 // Receipt, ACK leg: sequential per flow, so one lane per flow and no atomics on flow state.  The
 // records are grouped by destination and ordered (t_ns, src, seq) inside a group, which is the order
 // the ACKs take effect in: the lane walks its source's range and applies its own slot's ACKs (the
 // lanes of one source's flows are neighbours and read the same records).  Loops: the off[] range, and
-// at most `window` released segments per ACK.  A finished flow's FCT goes to the workgroup's LDS
-// histogram, flushed to replica blockIdx mod kPingReplicas.
+// at most `window` released (CC: and marked) segments per ACK.  A finished flow's FCT goes to the
+// workgroup's LDS histogram, flushed to replica blockIdx mod kPingReplicas.
+template <bool CC>
 __global__ __launch_bounds__(256) void k_flow_recv_ack(FlowArgs f, const tgsim_delivery* __restrict__ recs,
                                                        const uint64_t* __restrict__ off, uint64_t n_bound) {
   __shared__ uint32_t hist[kPingMaxBins];
@@ -3512,6 +3529,8 @@ __global__ __launch_bounds__(256) void k_flow_recv_ack(FlowArgs f, const tgsim_d
     uint64_t b = off[sp.src], e = off[sp.src + 1];
     e = e < n_bound ? e : n_bound;  // (never past the buffer the bound sized)
     tgsim_flow_row row = f.rows[fl];
+    [[maybe_unused]] tgsim_flow_cc_row c{};
+    if constexpr (CC) c = f.cc[fl];
     uint64_t bm = f.bitmap[fl];
     bool touched = false;
     for (; b < e; ++b) {
@@ -3522,24 +3541,73 @@ __global__ __launch_bounds__(256) void k_flow_recv_ack(FlowArgs f, const tgsim_d
       const uint32_t seg = flow_seg(r.seq);
       if (seg >= sp.n_seg) continue;
       touched = true;
-      const uint32_t room = sp.n_seg - row.base;  // (base <= n_seg)
-      const uint32_t next = row.base + (room < f.window ? room : f.window);
+      uint32_t next;
+      if constexpr (CC) {
+        next = c.next;
+      } else {
+        const uint32_t room = sp.n_seg - row.base;  // (base <= n_seg)
+        next = row.base + (room < f.window ? room : f.window);
+      }
       if (row.state != TGSIM_FLOW_ACTIVE || seg < row.base || seg >= next || (bm >> (seg - row.base) & 1ull)) {
         ++row.stale_acks;
         continue;
       }
       bm |= 1ull << (seg - row.base);  // (seg - base < window <= 64)
       ++row.acked;
-      if (seg != row.base) continue;
-      const uint32_t sh = ~bm ? (uint32_t)__builtin_ctzll(~bm) : 64u;  // the acknowledged prefix (window 64: all of it)
-      bm = sh < 64u ? bm >> sh : 0ull;
-      row.base += sh;
-      const uint32_t room2 = sp.n_seg - row.base;
-      const uint32_t next2 = row.base + (room2 < f.window ? room2 : f.window);
-      const uint32_t tick = (uint32_t)(r.t_ns / a.tick_ns + 1);
-      for (uint32_t sg = next; sg < next2; ++sg) {  // (at most `window` of them)
-        f.due[fl * f.window + sg % f.window] = tick;
-        f.att[fl * f.window + sg % f.window] = 0;
+      if constexpr (CC) {
+        if (seg == row.base) {
+          const uint32_t sh = ~bm ? (uint32_t)__builtin_ctzll(~bm) : 64u;
+          bm = sh < 64u ? bm >> sh : 0ull;
+          row.base += sh;
+        }
+        const uint32_t tick = (uint32_t)(r.t_ns / a.tick_ns + 1);
+        if (row.base >= c.recover) {  // growth: by one per ACK below ssthresh, by one per window above
+          if (c.cwnd < c.ssthresh) {
+            ++c.cwnd;
+          } else if (++c.cwnd_cnt >= c.cwnd) {
+            ++c.cwnd;
+            c.cwnd_cnt = 0;
+          }
+          c.cwnd = c.cwnd < f.window ? c.cwnd : f.window;
+        }
+        if (f.dupthresh) {  // fast retransmit: the holes with dupthresh acknowledged segments above them
+          uint64_t cand = flow_fast_mask(bm, f.dupthresh);
+          while (cand) {  // (ascending; at most `window` bits)
+            const uint32_t i = (uint32_t)__builtin_ctzll(cand);
+            cand &= cand - 1;
+            const uint64_t at = fl * f.window + (row.base + i) % f.window;
+            if (f.att[at] != 1 || f.due[at] <= tick) continue;  // (attempt 1, no FAST flag)
+            f.due[at] = tick;
+            f.att[at] = (uint8_t)(1u | kFlowFast);
+            ++c.fast_retransmits;
+            if (row.base + i >= c.recover) {  // a loss event: halve, once per window of data
+              c.ssthresh = c.cwnd / 2 > 2u ? c.cwnd / 2 : 2u;
+              c.cwnd = c.ssthresh;
+              c.cwnd_cnt = 0;
+              c.recover = c.next;
+              ++c.loss_events;
+            }
+          }
+        }
+        const uint32_t room2 = sp.n_seg - row.base, adm = row.base + (room2 < c.cwnd ? room2 : c.cwnd);
+        const uint32_t next2 = adm > c.next ? adm : c.next;
+        for (uint32_t sg = c.next; sg < next2; ++sg) {  // (at most `window` of them: cwnd <= window)
+          f.due[fl * f.window + sg % f.window] = tick;
+          f.att[fl * f.window + sg % f.window] = 0;
+        }
+        c.next = next2;
+      } else {
+        if (seg != row.base) continue;
+        const uint32_t sh = ~bm ? (uint32_t)__builtin_ctzll(~bm) : 64u;  // the acknowledged prefix (window 64: all of it)
+        bm = sh < 64u ? bm >> sh : 0ull;
+        row.base += sh;
+        const uint32_t room2 = sp.n_seg - row.base;
+        const uint32_t next2 = row.base + (room2 < f.window ? room2 : f.window);
+        const uint32_t tick = (uint32_t)(r.t_ns / a.tick_ns + 1);
+        for (uint32_t sg = next; sg < next2; ++sg) {  // (at most `window` of them)
+          f.due[fl * f.window + sg % f.window] = tick;
+          f.att[fl * f.window + sg % f.window] = 0;
+        }
       }
       if (row.base == sp.n_seg) {
         row.state = TGSIM_FLOW_DONE;
@@ -3553,6 +3621,7 @@ __global__ __launch_bounds__(256) void k_flow_recv_ack(FlowArgs f, const tgsim_d
     if (touched) {
       f.rows[fl] = row;
       f.bitmap[fl] = bm;
+      if constexpr (CC) f.cc[fl] = c;
     }
   }
   __syncthreads();
@@ -3562,22 +3631,23 @@ __global__ __launch_bounds__(256) void k_flow_recv_ack(FlowArgs f, const tgsim_d
 }
 
 // What flow fl offers in the window [win0, win1): the offers' count, the flow's fail tick F (all-ones:
-// none) and its earliest late tick (all-ones: none).  Read-only.
+// none) and its earliest late tick (all-ones: none).  Read-only.  n_fly: the segments in flight,
+// min(window, n_seg - base), or with congestion control next - base.
 struct FlowDue {
   uint32_t n, fail, late;
 };
-__device__ __forceinline__ FlowDue flow_due(const FlowArgs& f, uint64_t fl, const tgsim_flow_spec& sp,
-                                            const tgsim_flow_row& row, uint64_t bm) {
+template <bool CC>
+__device__ __forceinline__ FlowDue flow_due(const FlowArgs& f, uint64_t fl, const tgsim_flow_row& row, uint64_t bm,
+                                            uint32_t n_fly) {
   FlowDue d{0u, ~0u, ~0u};
   if (row.state != TGSIM_FLOW_ACTIVE) return d;
   const uint32_t win0 = (uint32_t)f.cal.win0, win1 = win0 + f.cal.n_ticks;  // (both below 2^31)
-  const uint32_t room = sp.n_seg - row.base, n_fly = room < f.window ? room : f.window;
   for (uint32_t i = 0; i < n_fly; ++i) {
     if (bm >> i & 1ull) continue;
     const uint64_t at = fl * f.window + (row.base + i) % f.window;
     const uint32_t t = f.due[at];
     if (t < win0) d.late = t < d.late ? t : d.late;
-    else if (t < win1 && f.att[at] >= f.max_attempts) d.fail = t < d.fail ? t : d.fail;
+    else if (t < win1 && (CC ? f.att[at] & kFlowAttMask : f.att[at]) >= f.max_attempts) d.fail = t < d.fail ? t : d.fail;
   }
   for (uint32_t i = 0; i < n_fly; ++i) {
     if (bm >> i & 1ull) continue;
@@ -3586,15 +3656,24 @@ __device__ __forceinline__ FlowDue flow_due(const FlowArgs& f, uint64_t fl, cons
   }
   return d;
 }
+template <bool CC>
+__device__ __forceinline__ uint32_t flow_n_fly(const FlowArgs& f, uint64_t fl, const tgsim_flow_spec& sp,
+                                               const tgsim_flow_row& row) {
+  if constexpr (CC) return f.cc[fl].next - row.base;  // (base <= next <= min(base + window, n_seg))
+  const uint32_t room = sp.n_seg - row.base;
+  return room < f.window ? room : f.window;
+}
 
 // Generation, count pass (read-only: a late window leaves the state as it is): a lane per flow adds
 // its offers to its source's count; the window's total and the earliest late tick per wavefront.
+template <bool CC>
 __global__ __launch_bounds__(256) void k_flow_count(FlowArgs f, uint64_t* counts) {
   const uint64_t fl = (uint64_t)blockIdx.x * 256 + threadIdx.x;
   FlowDue d{0u, ~0u, ~0u};
   if (fl < f.n_flows) {
     const tgsim_flow_spec sp = f.spec[fl];
-    d = flow_due(f, fl, sp, f.rows[fl], f.bitmap[fl]);
+    const tgsim_flow_row row = f.rows[fl];
+    d = flow_due<CC>(f, fl, row, f.bitmap[fl], flow_n_fly<CC>(f, fl, sp, row));
     if (d.n) atomicAdd(reinterpret_cast<unsigned long long*>(&counts[sp.src]), (unsigned long long)d.n);
   }
   const uint64_t tot = wave_sum(d.n), late = wave_min_max_u64(d.late == ~0u ? ~0ull : d.late, false);
@@ -3606,23 +3685,34 @@ __global__ __launch_bounds__(256) void k_flow_count(FlowArgs f, uint64_t* counts
 
 // Generation, write pass: the flow's offers take a block of its source's row (one claim on the row
 // cursor; the order pass sorts the row), their timers restart, and a flow whose segment ran out of
-// attempts fails at that tick.  Runs only when nothing is late.
+// attempts fails at that tick.  Runs only when nothing is late.  CC: an offer with attempt > 0 and no
+// FAST flag is a timeout; timeouts at or above `recover` (read once, ahead of the walk) make one loss
+// event of the flow in this generation.
+template <bool CC>
 __global__ __launch_bounds__(256) void k_flow_write(FlowArgs f, const uint64_t* __restrict__ off, uint32_t* cursor, InRec* out) {
   const uint64_t fl = (uint64_t)blockIdx.x * 256 + threadIdx.x;
   if (fl >= f.n_flows) return;
   const tgsim_flow_spec sp = f.spec[fl];
   tgsim_flow_row row = f.rows[fl];
   const uint64_t bm = f.bitmap[fl];
-  const FlowDue d = flow_due(f, fl, sp, row, bm);
+  [[maybe_unused]] tgsim_flow_cc_row c{};
+  uint32_t n_fly;
+  if constexpr (CC) {
+    c = f.cc[fl];
+    n_fly = c.next - row.base;
+  } else {
+    n_fly = flow_n_fly<false>(f, fl, sp, row);
+  }
+  const FlowDue d = flow_due<CC>(f, fl, row, bm, n_fly);
   if (!d.n && d.fail == ~0u) return;
   const uint32_t win0 = (uint32_t)f.cal.win0, win1 = win0 + f.cal.n_ticks;
   const uint32_t slot = (uint32_t)(fl - f.first[sp.src]);
-  const uint32_t room = sp.n_seg - row.base, n_fly = room < f.window ? room : f.window;
   uint64_t pos = d.n ? off[sp.src] + atomicAdd(&cursor[sp.src], d.n) : 0;
+  [[maybe_unused]] bool loss = false;
   for (uint32_t i = 0; i < n_fly; ++i) {
     if (bm >> i & 1ull) continue;
     const uint64_t at = fl * f.window + (row.base + i) % f.window;
-    const uint32_t t = f.due[at], k = f.att[at];
+    const uint32_t t = f.due[at], k = CC ? f.att[at] & kFlowAttMask : f.att[at];
     if (t < win0 || t >= win1 || t >= d.fail) continue;
     InRec rec;
     rec.dst = sp.dst;
@@ -3631,7 +3721,13 @@ __global__ __launch_bounds__(256) void k_flow_write(FlowArgs f, const uint64_t* 
     rec.len = f.seg_len;
     out[pos++] = rec;
     f.due[at] = t + f.rto;  // (t < 2^31, rto < 2^31)
-    f.att[at] = (uint8_t)(k + 1);
+    if constexpr (CC) {
+      if (k > 0 && !(f.att[at] & kFlowFast)) {
+        ++c.timeouts;
+        loss |= row.base + i >= c.recover;  // (recover changes after the walk only)
+      }
+    }
+    f.att[at] = (uint8_t)(k + 1);  // (the FAST flag clears)
     row.retransmits += k > 0;
   }
   row.offered += d.n;
@@ -3640,10 +3736,21 @@ __global__ __launch_bounds__(256) void k_flow_write(FlowArgs f, const uint64_t* 
     row.done_ns = (uint64_t)d.fail * f.cal.tick_ns;
   }
   f.rows[fl] = row;
+  if constexpr (CC) {
+    if (loss) {
+      c.ssthresh = c.cwnd / 2 > 2u ? c.cwnd / 2 : 2u;
+      c.cwnd = 1;
+      c.cwnd_cnt = 0;
+      c.recover = c.next;
+      ++c.loss_events;
+    }
+    f.cc[fl] = c;
+  }
 }
 
 // tgsim_flow_init: every flow's first window of segments due at its start tick; the histogram
-// replicas and the calendar's counters.
+// replicas and the calendar's counters.  CC: the cc row, with the first init_cwnd segments released.
+template <bool CC>
 __global__ __launch_bounds__(256) void k_flow_init(FlowArgs f) {
   const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
   if (i < f.n_flows) {
@@ -3654,9 +3761,54 @@ __global__ __launch_bounds__(256) void k_flow_init(FlowArgs f) {
       f.due[i * f.window + k] = sp.start_tick;
       f.att[i * f.window + k] = 0;
     }
+    if constexpr (CC) {
+      tgsim_flow_cc_row c{};
+      c.cwnd = f.init_cwnd;
+      c.ssthresh = f.init_ssthresh ? f.init_ssthresh : f.window;
+      c.next = f.init_cwnd < sp.n_seg ? f.init_cwnd : sp.n_seg;
+      f.cc[i] = c;
+    }
   }
   if (i < kPingReplicas * kPingMaxBins) f.cal.hist[i] = 0ull;
   if (i < kPingCtrWords) f.cal.ctr[i] = i == kPcLate ? ~0ull : 0ull;
+}
+
+// tgsim_flow_cc_report, as k_flow_report below: loss_events, fast_retransmits, timeouts over every
+// flow; the count, sum, minimum and maximum of cwnd over the ACTIVE ones.
+__global__ __launch_bounds__(256) void k_flow_cc_report(FlowArgs f, unsigned long long* res) {
+  __shared__ unsigned long long acc[kFlowCcResWords];
+  if (threadIdx.x < kFlowCcResWords) acc[threadIdx.x] = threadIdx.x == 5 ? ~0ull : 0ull;
+  __syncthreads();
+  uint64_t v[kFlowCcResWords] = {};
+  v[5] = ~0ull;
+  for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < f.n_flows; i += (uint64_t)gridDim.x * 256) {
+    const tgsim_flow_cc_row c = f.cc[i];
+    v[0] += c.loss_events;
+    v[1] += c.fast_retransmits;
+    v[2] += c.timeouts;
+    if (f.rows[i].state == TGSIM_FLOW_ACTIVE) {
+      ++v[3];
+      v[4] += c.cwnd;
+      v[5] = c.cwnd < v[5] ? c.cwnd : v[5];
+      v[6] = c.cwnd > v[6] ? c.cwnd : v[6];
+    }
+  }
+#pragma unroll
+  for (uint32_t w = 0; w < kFlowCcResWords; ++w) {
+    const uint64_t t = w == 5 ? wave_min_max_u64(v[w], false) : w == 6 ? wave_min_max_u64(v[w], true) : wave_sum(v[w]);
+    if ((threadIdx.x & 63u) == 0) {
+      if (w == 5) atomicMin(&acc[w], (unsigned long long)t);
+      else if (w == 6) atomicMax(&acc[w], (unsigned long long)t);
+      else atomicAdd(&acc[w], (unsigned long long)t);
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x < kFlowCcResWords) {
+    const uint32_t w = threadIdx.x;
+    if (w == 5) atomicMin(&res[w], acc[w]);
+    else if (w == 6) atomicMax(&res[w], acc[w]);
+    else atomicAdd(&res[w], acc[w]);
+  }
 }
 
 // tgsim_flow_report: one pass over the rows; a workgroup reduces in LDS and ends with one set of
@@ -5011,26 +5163,34 @@ void launch_ping_report(const PingArgs& a, unsigned long long* res, hipStream_t 
 // Flow driver (tgsim_flow_*).
 void launch_flow_init(const FlowArgs& f, hipStream_t st) {
   const uint64_t n = std::max<uint64_t>(f.n_flows, (uint64_t)kPingReplicas * kPingMaxBins);
-  hipLaunchKernelGGL(k_flow_init, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, f);
+  const dim3 grid((uint32_t)((n + 255) / 256));
+  if (f.cc) hipLaunchKernelGGL(k_flow_init<true>, grid, dim3(256), 0, st, f);
+  else hipLaunchKernelGGL(k_flow_init<false>, grid, dim3(256), 0, st, f);
 }
 
 void launch_flow_recv(const FlowArgs& f, const tgsim_delivery* recs, const uint64_t* off, uint32_t n_dst,
                       uint64_t n_bound, hipStream_t st) {
   hipLaunchKernelGGL(k_flow_recv_data, dim3(ping_grid(n_bound)), dim3(256), 0, st, f, recs, off, n_dst, n_bound);
-  hipLaunchKernelGGL(k_flow_recv_ack, dim3((uint32_t)((f.n_flows + 255) / 256)), dim3(256), 0, st, f, recs, off, n_bound);
+  const dim3 grid((uint32_t)((f.n_flows + 255) / 256));
+  if (f.cc) hipLaunchKernelGGL(k_flow_recv_ack<true>, grid, dim3(256), 0, st, f, recs, off, n_bound);
+  else hipLaunchKernelGGL(k_flow_recv_ack<false>, grid, dim3(256), 0, st, f, recs, off, n_bound);
 }
 
 void launch_flow_count(const FlowArgs& f, uint64_t* counts, uint32_t* cursor, uint64_t cal_bound, hipStream_t st) {
   (void)hipMemsetAsync(counts, 0, sizeof(uint64_t) * f.cal.n_peers, st);
   (void)hipMemsetAsync(cursor, 0, sizeof(uint32_t) * f.cal.n_peers, st);
   (void)hipMemsetAsync(f.cal.ctr + kPcOffers, 0, sizeof(unsigned long long), st);
-  hipLaunchKernelGGL(k_flow_count, dim3((uint32_t)((f.n_flows + 255) / 256)), dim3(256), 0, st, f, counts);
+  const dim3 grid((uint32_t)((f.n_flows + 255) / 256));
+  if (f.cc) hipLaunchKernelGGL(k_flow_count<true>, grid, dim3(256), 0, st, f, counts);
+  else hipLaunchKernelGGL(k_flow_count<false>, grid, dim3(256), 0, st, f, counts);
   if (cal_bound) hipLaunchKernelGGL(k_ping_count_cal, dim3(ping_grid(cal_bound)), dim3(256), 0, st, f.cal, counts);
 }
 
 void launch_flow_write(const FlowArgs& f, const uint64_t* off, uint32_t* cursor, InRec* tmp, InRec* out,
                        uint64_t cal_bound, hipStream_t st) {
-  hipLaunchKernelGGL(k_flow_write, dim3((uint32_t)((f.n_flows + 255) / 256)), dim3(256), 0, st, f, off, cursor, tmp);
+  const dim3 grid((uint32_t)((f.n_flows + 255) / 256));
+  if (f.cc) hipLaunchKernelGGL(k_flow_write<true>, grid, dim3(256), 0, st, f, off, cursor, tmp);
+  else hipLaunchKernelGGL(k_flow_write<false>, grid, dim3(256), 0, st, f, off, cursor, tmp);
   if (cal_bound) hipLaunchKernelGGL(k_ping_write_cal, dim3(ping_grid(cal_bound)), dim3(256), 0, st, f.cal, off, cursor, tmp);
   hipLaunchKernelGGL(k_ping_order, dim3((f.cal.n_peers + 3) / 4), dim3(256), 0, st, off, tmp, out, f.cal.n_peers);
 }
@@ -5038,6 +5198,13 @@ void launch_flow_write(const FlowArgs& f, const uint64_t* off, uint32_t* cursor,
 void launch_flow_report(const FlowArgs& f, unsigned long long* res, hipStream_t st) {
   hipLaunchKernelGGL(k_ping_report_init, dim3(1), dim3(256), 0, st, f.cal, res, kFlowResWords, 9u);
   hipLaunchKernelGGL(k_flow_report, dim3(std::min(ping_grid(f.n_flows), 256u)), dim3(256), 0, st, f, res);
+}
+
+void launch_flow_cc_report(const FlowArgs& f, unsigned long long* res, hipStream_t st) {
+  PingArgs words_only = f.cal;  // (no histogram to fold)
+  words_only.n_bins = 0;
+  hipLaunchKernelGGL(k_ping_report_init, dim3(1), dim3(256), 0, st, words_only, res, kFlowCcResWords, 5u);
+  hipLaunchKernelGGL(k_flow_cc_report, dim3(std::min(ping_grid(f.n_flows), 256u)), dim3(256), 0, st, f, res);
 }
 
 void launch_ping_pairs(const PingArgs& a, uint64_t i0, uint64_t n, tgsim_ping_pair* out, hipStream_t st) {

@@ -96,6 +96,9 @@ void launch_flow_count(const FlowArgs& f, uint64_t* counts, uint32_t* cursor, ui
 void launch_flow_write(const FlowArgs& f, const uint64_t* off, uint32_t* cursor, InRec* tmp, InRec* out,
                        uint64_t cal_bound, hipStream_t st);
 void launch_flow_report(const FlowArgs& f, unsigned long long* res, hipStream_t st);
+// With f.cc set the launchers above run the kernels' congestion-control instantiations.  _cc_report:
+// res = kFlowCcResWords words.
+void launch_flow_cc_report(const FlowArgs& f, unsigned long long* res, hipStream_t st);
 // Per-group traffic matrix (tgsim_group_matrix).  _src: words 0..9 from a window's input (off[n_src + 1],
 // in, verdict) behind its simulate kernel; n_in: the window's offered packets (picks the lanes per
 // source).  _dst: words 10..13 from delivery-ordered records, segment sg = off[sg] ..

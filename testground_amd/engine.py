@@ -232,12 +232,15 @@ class CABIEngine:
 
     # -- flow driver (tgsim_flow_*) ----------------------------------------------------------------
     def flow_init(self, flows=None, seg_len: int = 1460, ack_len: int = 64, window: int = 16, rto_ticks: int = 1,
-                  max_attempts: int = 8, bin_ns: int = 0, n_bins: int = 0) -> None:
+                  max_attempts: int = 8, bin_ns: int = 0, n_bins: int = 0, cc: Optional[dict] = None) -> None:
         """Arms the device flow driver: `flows` is an abi.FLOW_SPEC_DTYPE table sorted by src
         (workloads.flow_table_mesh); a fixed window of `window` segments, one ACK per delivered
         segment, a retransmission timer of rto_ticks per segment, at most max_attempts offers of a
-        segment (include/tgsim.h).  flow_init(None) disarms it."""
-        fn = self._gossip_fn("flow_init")
+        segment (include/tgsim.h).  flow_init(None) disarms it.  `cc` (a dict of init_cwnd,
+        init_ssthresh and dupthresh; missing keys as workloads.FLOW_CC_DEFAULT) arms it with the
+        congestion window and fast retransmit of tgsim_flow_init_cc: `window` is then the cap."""
+        fn = self._gossip_fn("flow_init" if cc is None or flows is None else "flow_init_cc")
+        self.flow_cc_armed = False
         if flows is None:
             self._check(fn(self._h, None, None, 0), "flow_init")
             self._n_flows = None
@@ -246,8 +249,29 @@ class CABIEngine:
         if t.ndim != 1:
             raise ValueError("flow_init: flows must be a 1-d abi.FLOW_SPEC_DTYPE table")
         p = abi.Flow(seg_len, ack_len, window, rto_ticks, max_attempts, n_bins, bin_ns)
-        self._check(fn(self._h, C.byref(p), t.ctypes.data, len(t)), "flow_init")
+        if cc is None:
+            self._check(fn(self._h, C.byref(p), t.ctypes.data, len(t)), "flow_init")
+        else:
+            c = abi.FlowCC(cc.get("init_cwnd", 1), cc.get("init_ssthresh", 0), cc.get("dupthresh", 3), 0)
+            self._check(fn(self._h, C.byref(p), C.byref(c), t.ctypes.data, len(t)), "flow_init_cc")
+            self.flow_cc_armed = True
         self._n_flows = len(t)
+
+    def flow_cc_rows(self, first: int = 0, n: Optional[int] = None) -> np.ndarray:
+        """abi.FLOW_CC_ROW_DTYPE rows of flows [first, first + n) (tgsim_flow_cc_rows)."""
+        fn = self._gossip_fn("flow_cc_rows")
+        total = getattr(self, "_n_flows", None) or 0  # (unarmed: the call says so)
+        n = max(total - first, 0) if n is None else n
+        out = np.zeros(n, dtype=abi.FLOW_CC_ROW_DTYPE)
+        self._check(fn(self._h, first, n, out.ctypes.data, len(out)), "flow_cc_rows")
+        return out
+
+    def flow_cc_report(self) -> dict:
+        """The congestion summary over every flow (abi.FLOW_CC_SUMMARY_FIELDS), reduced on the device
+        (tgsim_flow_cc_report); the cwnd fields are over the ACTIVE flows."""
+        s = abi.FlowCCSummary()
+        self._check(self._gossip_fn("flow_cc_report")(self._h, C.byref(s)), "flow_cc_report")
+        return {k: int(getattr(s, k)) for k in abi.FLOW_CC_SUMMARY_FIELDS}
 
     def gen_flow(self, n_ticks: int) -> None:
         self._check(self._gossip_fn("gen_flow")(self._h, n_ticks), "gen_flow")

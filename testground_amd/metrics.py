@@ -100,7 +100,11 @@ def flow_lines(report: Dict, bin_ns: int, plan: str, run: str, ts_ns: int) -> Li
     acknowledged segment, of ACTIVE and FAILED flows too, while the FCT exists for DONE flows only, so
     the line is written only when every flow is DONE: then it is one flow's own goodput, or the rate
     the run's flows reached together.  With unfinished or failed flows, take the bytes of the DONE
-    rows from Engine.flow_rows() instead."""
+    rows from Engine.flow_rows() instead.
+
+    A report that carries the congestion summary under "cc" (dict(eng.flow_report(),
+    cc=eng.flow_cc_report()), flows armed with cc) adds one `flow.cc.<field>` line per field of it,
+    the cwnd minimum and maximum only while a flow is ACTIVE."""
     tags = f"run={_escape(run)}"
     out: List[str] = []
     for name, key in FLOW_METRICS:
@@ -110,6 +114,11 @@ def flow_lines(report: Dict, bin_ns: int, plan: str, run: str, ts_ns: int) -> Li
     if report["done"] and report["done"] == report["flows"] and report["fct_sum_ns"]:
         goodput = report["bytes_acked"] * 8 * 10**9 * report["done"] // report["fct_sum_ns"]
         out.append(f"{_escape(f'results.{plan}.flow.goodput_bps')},{tags} value={int(goodput)}i {ts_ns}")
+    cc = report.get("cc")
+    for key in abi.FLOW_CC_SUMMARY_FIELDS if cc else ():
+        if key in ("cwnd_min", "cwnd_max") and not cc["active"]:
+            continue
+        out.append(f"{_escape(f'results.{plan}.flow.cc.{key}')},{tags} value={int(cc[key])}i {ts_ns}")
     meas = _escape(f"results.{plan}.flow.fct_hist")
     out += [f"{meas},{tags},bin={b * int(bin_ns)} value={int(c)}i {ts_ns}" for b, c in enumerate(report["hist"]) if c]
     return out

@@ -591,28 +591,227 @@ class FlowModel:
                 "fct_max_ns": int(fct.max()) if len(fct) else 0, "hist": self.hist.copy()}
 
 
-def flow_reference(eng, flow: Dict, flows: np.ndarray, n_windows: int, window: int, probe_at=(), before=None) -> Dict:
+FLOW_CC_DEFAULT = dict(init_cwnd=1, init_ssthresh=0, dupthresh=3)
+
+
+class FlowCCModel(FlowModel):
+    """FlowModel with the congestion window of tgsim_flow_init_cc (include/tgsim.h, "Congestion
+    control"): `cc` holds init_cwnd, init_ssthresh and dupthresh.  `window` is the cap of cwnd; what is
+    in flight is [base, next) with `next` stored; an ACK grows cwnd, marks segments below `dupthresh`
+    acknowledged ones for a fast retransmission and releases what the window admits; a timer that runs
+    out shrinks cwnd to 1."""
+
+    def __init__(self, eng, flow: Dict, flows: np.ndarray, cc: Dict):
+        super().__init__(eng, flow, flows)
+        self.cc = dict(FLOW_CC_DEFAULT, **cc)
+        c, w = self.cc, self.flow["window"]
+        if not 1 <= c["init_cwnd"] <= w:
+            raise ValueError(f"flow: init_cwnd {c['init_cwnd']} outside 1..window {w}")
+        if c["init_ssthresh"] and not 2 <= c["init_ssthresh"] <= w:
+            raise ValueError(f"flow: init_ssthresh {c['init_ssthresh']} neither 0 nor in 2..window {w}")
+        if not 0 <= c["dupthresh"] <= 63:
+            raise ValueError(f"flow: dupthresh {c['dupthresh']} outside 0..63")
+        nf = len(self.spec)
+        self.cwnd = np.full(nf, c["init_cwnd"], dtype=np.int64)
+        self.ssthresh = np.full(nf, c["init_ssthresh"] or w, dtype=np.int64)
+        self.next = np.minimum(c["init_cwnd"], self.spec["n_seg"].astype(np.int64))
+        self.recover = np.zeros(nf, dtype=np.int64)
+        self.cwnd_cnt = np.zeros(nf, dtype=np.int64)
+        self.loss_events = np.zeros(nf, dtype=np.int64)
+        self.fast_retransmits = np.zeros(nf, dtype=np.int64)
+        self.timeouts = np.zeros(nf, dtype=np.int64)
+        self.fast = np.zeros((nf, w), dtype=bool)  # ring, beside att
+        # what the run exercised: loss events by cause, loss signals `recover` suppressed, growth by
+        # regime, cwnd grown to the cap, a reduced window draining (next - base > cwnd), fast-marked
+        # segments acknowledged before their re-offer, fast retransmissions recovered by their timer
+        self.loss_fast = self.loss_timeout = self.suppressed = self.grow_ss = self.grow_ca = 0
+        self.cwnd_at_cap = self.draining = self.fast_acked_early = self.fast_lost = 0
+        self._was_fast = [set() for _ in range(nf)]
+
+    def _next(self, f: int) -> int:
+        return int(self.next[f])
+
+    def window_packets(self, window: int) -> np.ndarray:
+        p, win0, win1 = self.flow, self.now, self.now + window
+        if window > p["rto_ticks"]:
+            raise ValueError(f"flow: a window of {window} ticks is longer than rto_ticks {p['rto_ticks']}")
+        w = p["window"]
+        live = np.nonzero(self.state == abi.FLOW_ACTIVE)[0]
+        late = [int(self.cal[:, 0].min())] if len(self.cal) else []
+        late += [int(self.due[f, i % w]) for f in live for i in self._unacked(f)]
+        if late and min(late) < win0:  # nothing is generated, no state changes, the cc rows included
+            raise FlowLate(f"flow: a receipt due at tick {min(late)} precedes the window at tick {win0}")
+        rows = []  # src, dst, seq, tick, len
+        for f in live:
+            segs = self._unacked(f)
+            fail = [int(self.due[f, i % w]) for i in segs if self.due[f, i % w] < win1 and self.att[f, i % w] >= p["max_attempts"]]
+            fail_tick = min(fail) if fail else None
+            recover, timed_out, loss = int(self.recover[f]), False, False  # (recover: read once, before the pass)
+            self.draining += self.next[f] - self.base[f] > self.cwnd[f]
+            for i in segs:
+                t, k = int(self.due[f, i % w]), int(self.att[f, i % w])
+                if t >= win1 or (fail_tick is not None and t >= fail_tick):
+                    continue
+                rows.append((int(self.spec["src"][f]), int(self.spec["dst"][f]),
+                             k << abi.FLOW_ATTEMPT_SHIFT | int(self.slot[f]) << abi.FLOW_SLOT_SHIFT | i, t, p["seg_len"]))
+                self.due[f, i % w] = t + p["rto_ticks"]
+                self.att[f, i % w] = k + 1
+                self.offered[f] += 1
+                self.retransmits[f] += k > 0
+                self.max_attempt = max(self.max_attempt, k)
+                if self.fast[f, i % w]:  # the fast retransmission: attempt 1 in its seq
+                    self.fast[f, i % w] = False
+                    self._was_fast[f].add(i)
+                elif k > 0:
+                    self.timeouts[f] += 1
+                    timed_out = True
+                    loss |= i >= recover
+                    self.fast_lost += k >= 2 and i in self._was_fast[f]
+            if loss:  # one loss event per flow per generation
+                self.ssthresh[f] = max(self.cwnd[f] // 2, 2)
+                self.cwnd[f], self.cwnd_cnt[f], self.recover[f] = 1, 0, self.next[f]
+                self.loss_events[f] += 1
+                self.loss_timeout += 1
+            elif timed_out:
+                self.suppressed += 1
+            if fail_tick is not None:
+                self.state[f] = abi.FLOW_FAILED
+                self.done_ns[f] = fail_tick * self.tick_ns
+        due = self.cal[:, 0] < win1
+        ack, self.cal = self.cal[due], self.cal[~due]
+        rows += [(int(r), int(q), int(s) | abi.FLOW_ACK, int(t), p["ack_len"]) for t, r, q, s in ack]
+        a = np.array(rows, dtype=np.int64).reshape(-1, 5)
+        a = a[np.lexsort((a[:, 1], a[:, 2], a[:, 3], a[:, 0]))]
+        if len(a):
+            self.max_row = max(self.max_row, int(np.bincount(a[:, 0]).max()))
+            if len(ack):
+                self.max_ack_row = max(self.max_ack_row, int(np.bincount(ack[:, 1]).max()))
+            tie = (a[1:, 0] == a[:-1, 0]) & (a[1:, 3] == a[:-1, 3]) & (a[1:, 2] == a[:-1, 2])
+            self.ties += int(tie.sum())
+            self.tie_sources.update(np.unique(a[1:, 0][tie]).tolist())
+        pk = np.zeros(len(a), dtype=abi.PKT_DTYPE)
+        pk["src"], pk["dst"], pk["seq"], pk["tick"], pk["len"] = a[:, 0], a[:, 1], a[:, 2], a[:, 3] - win0, a[:, 4]
+        return pk
+
+    def receive(self, d: np.ndarray) -> None:
+        p, w, dup = self.flow, self.flow["window"], self.cc["dupthresh"]
+        new = []
+        for flags, seq, t_ns, src, dst in zip(*(d[k].tolist() for k in ("flags", "seq", "t_ns", "src", "dst"))):
+            if flags & abi.FLAG_DUP:
+                self.dup_ignored += 1
+                continue
+            if flags & abi.FLAG_CORRUPT:
+                self.corrupt_ignored += 1
+                continue
+            tick = t_ns // self.tick_ns + 1
+            if not seq & abi.FLOW_ACK:
+                if self._flow_of(src, seq, dst) is not None:
+                    new.append((tick, dst, src, seq))
+                continue
+            f = self._flow_of(dst, seq, src)
+            if f is None:
+                continue
+            seg, n_seg = seq & abi.FLOW_SEG_MASK, int(self.spec["n_seg"][f])
+            if self.state[f] != abi.FLOW_ACTIVE or seg < self.base[f] or seg >= self.next[f] or seg in self.acked_segs[f]:
+                self.stale[f] += 1
+                continue
+            # 1, 2: mark, advance base
+            self.acked_segs[f].add(seg)
+            self.acked[f] += 1
+            self.fast_acked_early += bool(self.fast[f, seg % w])
+            while int(self.base[f]) in self.acked_segs[f]:
+                self.acked_segs[f].discard(int(self.base[f]))
+                self.base[f] += 1
+            # 3: growth
+            if self.base[f] >= self.recover[f]:
+                before = int(self.cwnd[f])
+                if self.cwnd[f] < self.ssthresh[f]:
+                    self.cwnd[f] += 1
+                    self.grow_ss += self.cwnd[f] <= w
+                else:
+                    self.cwnd_cnt[f] += 1
+                    if self.cwnd_cnt[f] >= self.cwnd[f]:
+                        self.cwnd[f] += 1
+                        self.cwnd_cnt[f] = 0
+                        self.grow_ca += self.cwnd[f] <= w
+                self.cwnd[f] = min(self.cwnd[f], w)
+                self.cwnd_at_cap += before < w == self.cwnd[f]
+            # 4: fast retransmit
+            if dup:
+                for i in range(int(self.base[f]), int(self.next[f])):
+                    if i in self.acked_segs[f] or sum(1 for s in self.acked_segs[f] if s > i) < dup:
+                        continue
+                    if self.att[f, i % w] != 1 or self.fast[f, i % w] or self.due[f, i % w] <= tick:
+                        continue
+                    self.due[f, i % w], self.fast[f, i % w] = tick, True
+                    self.fast_retransmits[f] += 1
+                    if i >= self.recover[f]:
+                        self.ssthresh[f] = max(self.cwnd[f] // 2, 2)
+                        self.cwnd[f], self.cwnd_cnt[f], self.recover[f] = self.ssthresh[f], 0, self.next[f]
+                        self.loss_events[f] += 1
+                        self.loss_fast += 1
+                    else:
+                        self.suppressed += 1
+            # 5: release
+            next2 = max(int(self.next[f]), min(int(self.base[f] + self.cwnd[f]), n_seg))
+            for i in range(int(self.next[f]), next2):
+                self.due[f, i % w], self.att[f, i % w], self.fast[f, i % w] = tick, 0, False
+                self.ring_wraps += i >= w
+            self.next[f] = next2
+            # 6: done
+            if self.base[f] == n_seg:
+                self.state[f] = abi.FLOW_DONE
+                self.done_ns[f] = t_ns
+                if p["n_bins"]:
+                    fct = t_ns - int(self.spec["start_tick"][f]) * self.tick_ns
+                    self.hist[min(fct // p["bin_ns"], p["n_bins"] - 1)] += 1
+        self.cal = np.concatenate([self.cal, np.array(new, dtype=np.int64).reshape(-1, 4)])
+
+    def cc_rows(self) -> np.ndarray:
+        out = np.zeros(len(self.spec), dtype=abi.FLOW_CC_ROW_DTYPE)
+        for key, v in (("cwnd", self.cwnd), ("ssthresh", self.ssthresh), ("next", self.next), ("recover", self.recover),
+                       ("cwnd_cnt", self.cwnd_cnt), ("loss_events", self.loss_events),
+                       ("fast_retransmits", self.fast_retransmits), ("timeouts", self.timeouts)):
+            out[key] = v
+        return out
+
+    def cc_report(self) -> Dict:
+        cw = self.cwnd[self.state == abi.FLOW_ACTIVE]
+        return {"loss_events": int(self.loss_events.sum()), "fast_retransmits": int(self.fast_retransmits.sum()),
+                "timeouts": int(self.timeouts.sum()), "active": len(cw), "cwnd_sum": int(cw.sum()),
+                "cwnd_min": int(cw.min()) if len(cw) else int(np.iinfo(np.uint64).max),
+                "cwnd_max": int(cw.max()) if len(cw) else 0}
+
+
+def flow_reference(eng, flow: Dict, flows: np.ndarray, n_windows: int, window: int, probe_at=(), before=None,
+                   cc=None) -> Dict:
     """The flow loop driven from the host over `eng` (submit / step / verdicts / drain): per-window
     (verdicts, deliveries) under "windows", the final "rows" and "summary" (report fields and hist),
     and under "probes" the (rows, summary) after each window index in probe_at.  before(w) runs ahead
-    of window w (a reshape, a partition).  The model itself is under "model"."""
-    m = FlowModel(eng, flow, flows)
+    of window w (a reshape, a partition).  The model itself is under "model".  With `cc` (the dict of
+    Engine.flow_init) the model is FlowCCModel, the result has "cc_rows" and "cc_summary" too, and a
+    probe is (rows, summary, cc_rows, cc_summary)."""
+    m = FlowModel(eng, flow, flows) if cc is None else FlowCCModel(eng, flow, flows, cc)
     out = {"windows": [], "probes": {}, "model": m}
     for w in range(n_windows):
         if before is not None:
             before(w)
         out["windows"].append(m.step(window))
         if w in probe_at:
-            out["probes"][w] = (m.rows(), m.report())
+            out["probes"][w] = (m.rows(), m.report()) + (() if cc is None else (m.cc_rows(), m.cc_report()))
     out["rows"], out["summary"] = m.rows(), m.report()
+    if cc is not None:
+        out["cc_rows"], out["cc_summary"] = m.cc_rows(), m.cc_report()
     return out
 
 
 def flow_run(eng, n_windows: int, window: int, collect: bool = False, probe_at=(), before=None) -> Dict:
     """The device loop on an armed engine (Engine.flow_init): n_windows of gen_flow + step.  Nothing
     reaches the host unless asked for: collect keeps each window's (verdicts, deliveries), probe_at
-    the (rows, report) after those windows."""
+    the (rows, report) after those windows, and the (cc rows, cc report) beside them when the engine
+    is armed with congestion control."""
     out = {"windows": [], "probes": {}}
+    cc = getattr(eng, "flow_cc_armed", False)
     for w in range(n_windows):
         if before is not None:
             before(w)
@@ -621,7 +820,7 @@ def flow_run(eng, n_windows: int, window: int, collect: bool = False, probe_at=(
         if collect:
             out["windows"].append((eng.verdicts(), eng.drain()))
         if w in probe_at:
-            out["probes"][w] = (eng.flow_rows(), eng.flow_report())
+            out["probes"][w] = (eng.flow_rows(), eng.flow_report()) + ((eng.flow_cc_rows(), eng.flow_cc_report()) if cc else ())
     return out
 
 
