@@ -616,8 +616,9 @@ int64_t tgsim_flow_rows(void* engine, uint64_t first, uint64_t n, tgsim_flow_row
  *             loss_events += 1.  A late window still changes no state, the cc rows included.  A
  *             FAST segment is due like any other: with max_attempts == 1 it fails the flow at its tick.
  *   Step      as above, the counters and the windows depend on the step length, the fail tick does not.
- *   Not here  an RTT estimator, timer backoff, cumulative or delayed ACKs, pacing, and failing at once
- *             on a BLACKHOLE or PROHIBIT verdict (still the follow-up DESIGN.md §5.8 names). */
+ *   Not here  cumulative or delayed ACKs, pacing, and failing at once on a BLACKHOLE or PROHIBIT
+ *             verdict (still the follow-up DESIGN.md §5.8 names); an RTT estimator and timer backoff
+ *             are opt-in further down (tgsim_flow_init_rto). */
 typedef struct {
     uint32_t init_cwnd;     /* 1..window: segments released at start_tick                  */
     uint32_t init_ssthresh; /* 0 -> window; else 2..window                                  */
@@ -644,6 +645,74 @@ int tgsim_flow_init_cc(void* engine, const tgsim_flow* p, const tgsim_flow_cc* c
  * synchronize, and fail, like tgsim_flow_rows and tgsim_flow_report. */
 int64_t tgsim_flow_cc_rows(void* engine, uint64_t first, uint64_t n, tgsim_flow_cc_row* out, size_t cap);
 int     tgsim_flow_cc_report(void* engine, tgsim_flow_cc_summary* out);
+
+/* ---- RTT estimator and timer backoff of the flow driver (opt-in per arming) -- */
+/* A retransmission timer per flow that follows the flow's measured round trip (RFC 6298 in integer
+ * ticks) and, optionally, doubles per earlier offer of a segment: what a run over links of unequal
+ * latency needs, where no one rto_ticks is right.  Armed with tgsim_flow_init_rto and a non-NULL rto,
+ * with or without cc (the two are independent); without it every rule above holds as written.  With
+ * it, everything above that is not named here stays as written.
+ *
+ *   State     per flow, the 32-B tgsim_flow_rto_row: srtt8 (smoothed RTT x 8), rttvar4 (variation x 4),
+ *             rto (the flow's current timer), samples, rtt_min, rtt_max, rtt_last, all in ticks.  Per
+ *             in-flight segment a `sent` tick beside its due tick and attempt count, on the same ring
+ *             (segment mod window).
+ *   Arming    rto = p->rto_ticks (the initial timer), srtt8 = rttvar4 = samples = rtt_max = rtt_last =
+ *             0, rtt_min = 0xFFFFFFFF.
+ *   Offer     a segment offered at tick t with attempt count k before the offer: its timer restarts at
+ *             t + timer, timer = backoff ? min((uint64)rto << k, max_rto_ticks) : rto, with rto the
+ *             flow's value as the generation finds it (a generation changes no rto row, so the order
+ *             the segments are walked in does not matter).  k counts every earlier offer of the
+ *             segment, a fast retransmission included.  When k == 0, sent = t.  The fail rule stays by
+ *             tick and by max_attempts: with backoff a flow that never gets an ACK fails at start_tick
+ *             + the sum over k < max_attempts of min(rto << k, max_rto_ticks).
+ *   Sample    a non-stale ACK whose attempt field (seq bits 27..30) is 0 and whose segment has been
+ *             offered (attempt count >= 1), delivered at d, tick = floor(d / tick_ns) + 1, gives m =
+ *             min(tick - sent, max_rto_ticks).  The ACK echoes the attempt it answers, so the sample
+ *             is unambiguous however often the segment was retransmitted since: no Karn exclusion, and
+ *             a flow whose initial timer is below its round trip still gets its first sample.
+ *   Update    before anything else uses the ACK (ahead of step 1 of the cc receipt).  First sample:
+ *             srtt8 = 8 m, rttvar4 = 2 m.  Later: err = m - (srtt8 >> 3), signed; rttvar4 = rttvar4 -
+ *             (rttvar4 >> 2) + |err|; srtt8 += err.  Then rto = clamp((srtt8 >> 3) + max(rttvar4, 1),
+ *             min_rto_ticks, max_rto_ticks); samples += 1; rtt_min, rtt_max and rtt_last follow m.
+ *             max_rto_ticks <= 2^27 keeps every field inside 32 bits.
+ *   Window    while armed with rto, tgsim_gen_flow(n) is -EINVAL when n > min_rto_ticks (the text names
+ *             min_rto_ticks), in place of the rto_ticks test: a segment is still offered at most once
+ *             per window.
+ *   Late      a late window changes no state, the rto rows and `sent` included.
+ *   Step      as above, the counters and the samples depend on the step length, the fail tick does not.
+ *   Not here  cumulative or delayed ACKs, pacing, and failing at once on a BLACKHOLE or PROHIBIT
+ *             verdict (still the follow-up DESIGN.md §5.8 names). */
+typedef struct {
+    uint32_t min_rto_ticks; /* >= 1; also the longest window tgsim_gen_flow accepts while armed */
+    uint32_t max_rto_ticks; /* min_rto_ticks .. 2^27                                            */
+    uint32_t backoff;       /* 0: a segment's timer is the flow's rto; 1: doubled per earlier   */
+                            /* offer of the segment                                             */
+    uint32_t _pad;
+} tgsim_flow_rto;           /* 16 B */
+typedef struct {            /* one flow; 32 B */
+    uint32_t srtt8;         /* smoothed RTT x 8, ticks; 0 with no sample                        */
+    uint32_t rttvar4;       /* RTT variation x 4                                                */
+    uint32_t rto;           /* the flow's current timer, ticks                                  */
+    uint32_t samples;
+    uint32_t rtt_min /* 0xFFFFFFFF when none */, rtt_max, rtt_last, _pad;
+} tgsim_flow_rto_row;
+typedef struct {            /* 64 B; every field but samples is over the flows with samples > 0 */
+    uint64_t samples, sampled_flows;
+    uint64_t srtt_sum, srtt_min /* UINT64_MAX when none */, srtt_max;   /* srtt8 >> 3 */
+    uint64_t rto_sum, rto_min /* UINT64_MAX when none */, rto_max;
+} tgsim_flow_rto_summary;
+/* tgsim_flow_init_cc with the estimator: every arming, busy and disarm rule of tgsim_flow_init holds,
+ * rto == NULL is tgsim_flow_init_cc itself, cc may be NULL or not, and a bad rto field is -EINVAL with
+ * a tgsim_last_error text that names the field and its value: min_rto_ticks == 0, max_rto_ticks below
+ * min_rto_ticks or above 2^27, backoff > 1, p->rto_ticks outside [min_rto_ticks, max_rto_ticks]. */
+int tgsim_flow_init_rto(void* engine, const tgsim_flow* p, const tgsim_flow_cc* cc, const tgsim_flow_rto* rto,
+                        const tgsim_flow_spec* flows, uint64_t n_flows);
+/* The rto rows of flows [first, first + n), and the rto summary reduced on the device.  -EINVAL ("the
+ * RTT estimator is not armed") when flows are armed without rto or not at all; otherwise they
+ * synchronize, and fail, like tgsim_flow_cc_rows and tgsim_flow_cc_report. */
+int64_t tgsim_flow_rto_rows(void* engine, uint64_t first, uint64_t n, tgsim_flow_rto_row* out, size_t cap);
+int     tgsim_flow_rto_report(void* engine, tgsim_flow_rto_summary* out);
 
 /* ---- per-group traffic matrix (who offered what to whom, and what became of it) -------------- */
 /* Every peer belongs to one group (a region, a composition group); the engine folds each window's

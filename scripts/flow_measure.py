@@ -10,10 +10,14 @@
   steady the device loop alone: wall time per window and the median over the steady windows (the A/B
          figure: run it with TGSIM_LIB naming another build of the library)
   curve  goodput per flow against link loss, with and without congestion control (the README's table)
+  hetero 10,000 peers with latencies U[1,100] ms: a fixed timer of 60 ms, one above the largest round
+         trip, and the RTT estimator from that same timer (the README's table)
 
 `--cc` arms run, steady and trace with congestion control (init_cwnd 2, dupthresh 3,
 the cap `window` as without) and `--loss PCT` puts that loss on every link; with either the run takes
-CC_WINDOWS windows, since the windows open from 2 segments and lost ones wait for a timer.
+CC_WINDOWS windows, since the windows open from 2 segments and lost ones wait for a timer.  `--rto`
+arms them with the RTT estimator as well (from the timer of 20 ms, a floor of one
+window, backoff on), with or without `--cc`.
 
 Every link 5 ms, lossless, unlimited, reorder off; 800,000 flows of 64 segments of 1,000 bytes, window
 8, ACKs of 64 bytes, a timer of 20 ms that never fires; windows of 5,000 ticks.  Every flow starts at
@@ -46,6 +50,11 @@ CC_WINDOWS, CC_STEADY = 44, range(8, 24)  # from 2 segments: 2, 4, then 8 a roun
 # the link: 12.5 KB of bandwidth-delay product against 64 KB of fixed windows), a timer of 60 ms
 CURVE = dict(n=10_000, rate_bps=10_000_000, rto_ticks=60_000, max_windows=1200, losses=(0.0, 0.5, 1.0, 2.0, 4.0))
 OFFSETS = np.array([1, 17, 263, 4099, 9973, 31337, 54321, 77777])
+RTO = dict(min_rto_ticks=WIN, max_rto_ticks=2_000_000, backoff=1)
+# hetero: per-peer latency U[1,100] ms (round trips of 2 to 200 ms), jitter U[0.1,0.5] ms on every peer, 1 %
+# loss; the minimum netem delay is 0.5 ms, which is the lookahead and the window.  Unlimited links.
+HETERO = dict(n=10_000, win=500, lookahead_ns=nw.Millisecond // 2, loss=1.0, above_ticks=210_000, max_windows=16_000,
+              bin_ns=20 * nw.Millisecond, n_bins=256, seed=11)
 
 
 def flow_table(n=N):
@@ -61,9 +70,9 @@ def engine(flags, loss=0.0, n=N, rate_bps=0):
     return eng
 
 
-def device_loop(windows=WINDOWS, cc=None, loss=0.0):
+def device_loop(windows=WINDOWS, cc=None, loss=0.0, rto=None):
     eng, t = engine(abi.OPT_DISCARD_DELIVERIES, loss), []
-    eng.flow_init(flow_table(), cc=cc, **FLOW)
+    eng.flow_init(flow_table(), cc=cc, rto=rto, **FLOW)
     for w in range(windows):
         eng.sync()
         t0 = time.perf_counter()
@@ -74,7 +83,45 @@ def device_loop(windows=WINDOWS, cc=None, loss=0.0):
     rep = eng.flow_report()
     if cc is not None:
         rep["cc"] = eng.flow_cc_report()
+    if rto is not None:
+        rep["rto"] = eng.flow_rto_report()
     return rep, t
+
+
+def hist_quantile_ms(hist, q, bin_ns):
+    """The upper edge (ms) of the histogram bin that holds the q-quantile of the DONE flows."""
+    c = np.cumsum(hist)
+    return None if not c[-1] else round(float((np.searchsorted(c, q * c[-1]) + 1) * bin_ns) / 1e6, 1)
+
+
+def hetero_point(name, rto_ticks, rto):
+    """One row of the hetero table: run to the end (or max_windows)."""
+    h = HETERO
+    n, rng = h["n"], np.random.default_rng(h["seed"])
+    lat = rng.integers(nw.Millisecond, 100 * nw.Millisecond + 1, n)
+    jit = rng.integers(nw.Millisecond // 10, nw.Millisecond // 2 + 1, n)
+    eng = Engine(n, lookahead_ns=h["lookahead_ns"], flags=abi.OPT_DISCARD_DELIVERIES)
+    eng.configure_batch(np.arange(n), nw.configs_array(lat, jitter_ns=jit, loss=np.full(n, h["loss"], dtype=np.float32)))
+    eng.flow_init(flow_table(n), cc=CC, rto=rto,
+                  **dict(FLOW, rto_ticks=rto_ticks, max_attempts=16, n_bins=h["n_bins"], bin_ns=h["bin_ns"]))
+    windows, t0 = 0, time.perf_counter()
+    while windows < h["max_windows"]:
+        wl.flow_run(eng, 500, h["win"])
+        windows += 500
+        if eng.flow_report()["active"] == 0:
+            break
+    eng.sync()
+    wall = time.perf_counter() - t0
+    rep, cc = eng.flow_report(), eng.flow_cc_report()
+    out = {"row": name, "rto_ticks": rto_ticks, "rto": rto, "windows": windows, "wall_s": round(wall, 2),
+           "done": rep["done"], "failed": rep["failed"], "active": rep["active"],
+           "fct_ms_mean": round(rep["fct_sum_ns"] / rep["done"] / 1e6, 1) if rep["done"] else None,
+           "fct_ms_p99_bin_edge": hist_quantile_ms(rep["hist"], 0.99, h["bin_ns"]),
+           "retransmits": rep["retransmits"], "stale_acks": rep["stale_acks"], "timeouts": cc["timeouts"],
+           "fast_retransmits": cc["fast_retransmits"], "loss_events": cc["loss_events"], "segs_acked": rep["segs_acked"]}
+    if rto is not None:
+        out["rto_report"] = eng.flow_rto_report()
+    return out
 
 
 def curve_point(loss, cc):
@@ -114,13 +161,14 @@ def host_loop(windows=HOST_WINDOWS):
 def main():
     mode = sys.argv[1]
     cc = CC if "--cc" in sys.argv else None
+    rto = RTO if "--rto" in sys.argv else None
     loss = float(sys.argv[sys.argv.index("--loss") + 1]) if "--loss" in sys.argv else 0.0
     windows, steady = (CC_WINDOWS, CC_STEADY) if cc is not None or loss else (WINDOWS, STEADY)
     if mode == "run":
-        print(json.dumps({k: v for k, v in device_loop(windows, cc, loss)[0].items() if k != "hist"}))
+        print(json.dumps({k: v for k, v in device_loop(windows, cc, loss, rto)[0].items() if k != "hist"}))
     elif mode == "steady":
-        rep, td = device_loop(windows, cc, loss)
-        print(json.dumps({"cc": cc, "loss_pct": loss, "windows": windows, "steady": [steady[0], steady[-1]],
+        rep, td = device_loop(windows, cc, loss, rto)
+        print(json.dumps({"cc": cc, "rto": rto, "loss_pct": loss, "windows": windows, "steady": [steady[0], steady[-1]],
                           "report": {k: v for k, v in rep.items() if k != "hist"},
                           "device_ms_per_window": [round(1e3 * x, 3) for x in td],
                           "device_steady_ms": round(1e3 * statistics.median(td[w] for w in steady), 3),
@@ -130,6 +178,11 @@ def main():
         for loss_pct in CURVE["losses"]:
             for c in (None, CC):
                 print(json.dumps(curve_point(loss_pct, c)), flush=True)
+    elif mode == "hetero":
+        h = HETERO
+        for row in (("fixed 60 ms", 60_000, None), ("fixed above the largest round trip", h["above_ticks"], None),
+                    ("adaptive", h["above_ticks"], dict(min_rto_ticks=h["win"], max_rto_ticks=RTO["max_rto_ticks"], backoff=1))):
+            print(json.dumps(hetero_point(*row)), flush=True)
     elif mode == "wall":
         dev, td = device_loop()
         short, _ = device_loop(HOST_WINDOWS)
@@ -147,16 +200,20 @@ def main():
     elif mode == "trace":
         per = {}
         for r in csv.DictReader(open(sys.argv[2])):
-            name = r["Kernel_Name"].split("(")[0].split("::")[-1].split()[-1].split("<")[0]  # (void k_flow_write<true>(...))
+            name = r["Kernel_Name"].split("(")[0].split("<")[0].split("::")[-1].split()[-1]  # (void k_flow_write<true, false>(...))
             if name.startswith(("k_flow_", "k_ping_")) or name in ("k_sim_sparse", "k_sim", "k_sim_list", "k_sim_multi"):
                 per.setdefault(name, []).append((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3)
         flows, w = N * PER_SOURCE, FLOW["window"]
         seg = flows * w  # the windows alternate: a busy window carries 6.4 M segments or their 6.4 M ACKs
         ccb = 32 if cc is not None else 0  # the cc row beside the flow row
+        rtb, snt = (32, 4) if rto is not None else (0, 0)  # the rto row; a `sent` tick per ring slot
         state = flows * (16 + 32 + ccb + 8 + w * 5)  # spec, row, bitmap, timers
         floors = {"k_flow_recv_data": seg * 24 + seg * 16,          # a window of segments read, an entry each written
-                  "k_flow_recv_ack": seg * 24 + flows * (16 + 2 * (32 + ccb) + 2 * 8) + seg * 5,  # ACKs once, state in and out, timers
-                  "k_flow_count": state, "k_flow_write": state + seg * 16 + seg * 5 + flows * (32 + ccb),
+                  # ACKs once, state in and out, timers (rto: a `sent` tick read per ACK)
+                  "k_flow_recv_ack": seg * 24 + flows * (16 + 2 * (32 + ccb + rtb) + 2 * 8) + seg * (5 + snt),
+                  # (rto: the row's timer read, a `sent` tick written per first offer)
+                  "k_flow_count": state, "k_flow_write": state + seg * 16 + seg * (5 + snt) + flows * (32 + ccb + rtb),
+                  "k_flow_rto_report": flows * 32,
                   "k_flow_cc_report": flows * (32 + 32),  # the cc row, and the flow row for its state
                   "k_ping_count_cal": seg * 16, "k_ping_write_cal": seg * 16 + seg * 16, "k_ping_order": seg * 16 * 2}
         out = {}

@@ -170,6 +170,23 @@ class FlowCCSummary(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in FLOW_CC_SUMMARY_FIELDS + ("_pad",)]
 
 
+# RTT estimator and timer backoff of the flow driver (tgsim_flow_init_rto).
+FLOW_MAX_RTO = 1 << 27
+
+
+class FlowRto(C.Structure):
+    _fields_ = [("min_rto_ticks", C.c_uint32), ("max_rto_ticks", C.c_uint32), ("backoff", C.c_uint32), ("_pad", C.c_uint32)]
+
+
+FLOW_RTO_ROW_DTYPE = np.dtype([("srtt8", "<u4"), ("rttvar4", "<u4"), ("rto", "<u4"), ("samples", "<u4"), ("rtt_min", "<u4"),
+                               ("rtt_max", "<u4"), ("rtt_last", "<u4"), ("_pad", "<u4")])
+FLOW_RTO_SUMMARY_FIELDS = ("samples", "sampled_flows", "srtt_sum", "srtt_min", "srtt_max", "rto_sum", "rto_min", "rto_max")
+
+
+class FlowRtoSummary(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in FLOW_RTO_SUMMARY_FIELDS]
+
+
 # Per-group traffic matrix (tgsim_groups_init / tgsim_group_matrix): the words of a cell.
 GROUP_MAX = 64
 GROUP_WORDS = 14
@@ -203,6 +220,7 @@ assert C.sizeof(Ping) == 40 and PING_PAIR_DTYPE.itemsize == 32 and C.sizeof(Ping
 assert C.sizeof(Flow) == 32 and FLOW_SPEC_DTYPE.itemsize == 16 and FLOW_ROW_DTYPE.itemsize == 32
 assert C.sizeof(FlowSummary) == 120
 assert C.sizeof(FlowCC) == 16 and FLOW_CC_ROW_DTYPE.itemsize == 32 and C.sizeof(FlowCCSummary) == 64
+assert C.sizeof(FlowRto) == 16 and FLOW_RTO_ROW_DTYPE.itemsize == 32 and C.sizeof(FlowRtoSummary) == 64
 assert C.sizeof(CommInfo) == 72 and C.sizeof(Gossip) == 24 and C.sizeof(Opts) == 56 and C.sizeof(Shape) == 56 and C.sizeof(Config) == 104
 
 # Every symbol include/tgsim.h declares (checked by tests/test_abi.py).
@@ -221,6 +239,7 @@ EXPORTS = [
     "tgsim_ping_init", "tgsim_gen_ping", "tgsim_ping_report", "tgsim_ping_pairs",
     "tgsim_flow_init", "tgsim_gen_flow", "tgsim_flow_report", "tgsim_flow_rows",
     "tgsim_flow_init_cc", "tgsim_flow_cc_rows", "tgsim_flow_cc_report",
+    "tgsim_flow_init_rto", "tgsim_flow_rto_rows", "tgsim_flow_rto_report",
     "tgsim_groups_init", "tgsim_group_matrix",
     "tgsim_comm_id", "tgsim_comm_init", "tgsim_comm_step", "tgsim_comm_launch", "tgsim_comm_finish", "tgsim_comm_run", "tgsim_comm_barrier", "tgsim_comm_info",
     "tgsim_bridge_create", "tgsim_bridge_destroy", "tgsim_bridge_send", "tgsim_bridge_step",
@@ -303,6 +322,9 @@ def declare(lib: C.CDLL, prefix: str) -> None:
     f("flow_init_cc", C.c_int, vp, C.POINTER(Flow), C.POINTER(FlowCC), C.c_void_p, C.c_uint64)
     f("flow_cc_rows", C.c_int64, vp, C.c_uint64, C.c_uint64, C.c_void_p, C.c_size_t)
     f("flow_cc_report", C.c_int, vp, C.POINTER(FlowCCSummary))
+    f("flow_init_rto", C.c_int, vp, C.POINTER(Flow), C.POINTER(FlowCC), C.POINTER(FlowRto), C.c_void_p, C.c_uint64)
+    f("flow_rto_rows", C.c_int64, vp, C.c_uint64, C.c_uint64, C.c_void_p, C.c_size_t)
+    f("flow_rto_report", C.c_int, vp, C.POINTER(FlowRtoSummary))
     f("groups_init", C.c_int, vp, C.c_void_p, C.c_uint32)
     f("group_matrix", C.c_int64, vp, C.c_void_p, C.c_size_t, C.c_int)
     f("offered", C.c_int64, vp, C.c_void_p, C.c_size_t)

@@ -484,6 +484,10 @@ struct tgsim_engine_s {
   bool flow_cc_on = false;       // armed by tgsim_flow_init_cc with a cc
   tgsim_flow_cc flow_cc{};
   DevBuf<tgsim_flow_cc_row> d_fcc;
+  bool flow_rto_on = false;      // armed by tgsim_flow_init_rto with an rto
+  tgsim_flow_rto flow_rto{};
+  DevBuf<tgsim_flow_rto_row> d_frt;
+  DevBuf<uint32_t> d_fsent;
   hipEvent_t ev_flow = nullptr;  // after the last k_flow_recv_ack (delivery stream)
 
   // per-group traffic matrix (tgsim_groups_init / tgsim_group_matrix)
@@ -1529,9 +1533,10 @@ int ping_recv(Eng* E, const tgsim_delivery* recs, const uint64_t* off, uint32_t 
 void flow_release(Eng* E) {
   ping_release(E);
   E->d_fspec.release(); E->d_frow.release(); E->d_fbits.release(); E->d_fdue.release(); E->d_ffirst.release();
-  E->d_fcnt.release(); E->d_fatt.release(); E->d_fcc.release();
+  E->d_fcnt.release(); E->d_fatt.release(); E->d_fcc.release(); E->d_frt.release(); E->d_fsent.release();
   E->flow_on = false;
   E->flow_cc_on = false;
+  E->flow_rto_on = false;
   E->flow_late = false;
 }
 
@@ -1567,6 +1572,11 @@ FlowArgs flow_args(Eng* E, uint64_t win0, uint32_t n_ticks) {
   f.init_cwnd = E->flow_cc.init_cwnd;
   f.init_ssthresh = E->flow_cc.init_ssthresh;
   f.dupthresh = E->flow_cc.dupthresh;
+  f.rt = E->flow_rto_on ? E->d_frt.p : nullptr;
+  f.sent = E->flow_rto_on ? E->d_fsent.p : nullptr;
+  f.min_rto = E->flow_rto.min_rto_ticks;
+  f.max_rto = E->flow_rto.max_rto_ticks;
+  f.backoff = E->flow_rto.backoff;
   return f;
 }
 
@@ -2909,6 +2919,11 @@ int tgsim_flow_init(void* e, const tgsim_flow* p, const tgsim_flow_spec* flows, 
 
 int tgsim_flow_init_cc(void* e, const tgsim_flow* p, const tgsim_flow_cc* cc, const tgsim_flow_spec* flows,
                        uint64_t n_flows) {
+  return tgsim_flow_init_rto(e, p, cc, nullptr, flows, n_flows);
+}
+
+int tgsim_flow_init_rto(void* e, const tgsim_flow* p, const tgsim_flow_cc* cc, const tgsim_flow_rto* rto,
+                        const tgsim_flow_spec* flows, uint64_t n_flows) {
   Eng* E = as_eng(e);
   if (!E) return -EINVAL;
   HIPCHK(hipSetDevice(E->dev));
@@ -2936,6 +2951,15 @@ int tgsim_flow_init_cc(void* e, const tgsim_flow* p, const tgsim_flow_cc* cc, co
     if (cc->init_ssthresh && (cc->init_ssthresh < 2 || cc->init_ssthresh > p->window))
       return E->fail(-EINVAL, "flow: init_ssthresh %u neither 0 nor in 2..window (%u)", cc->init_ssthresh, p->window);
     if (cc->dupthresh > 63) return E->fail(-EINVAL, "flow: dupthresh %u outside 0..63", cc->dupthresh);
+  }
+  if (rto) {
+    if (rto->min_rto_ticks == 0) return E->fail(-EINVAL, "flow: min_rto_ticks %u below 1", rto->min_rto_ticks);
+    if (rto->max_rto_ticks < rto->min_rto_ticks || rto->max_rto_ticks > (1u << 27))
+      return E->fail(-EINVAL, "flow: max_rto_ticks %u outside min_rto_ticks (%u)..2^27", rto->max_rto_ticks, rto->min_rto_ticks);
+    if (rto->backoff > 1) return E->fail(-EINVAL, "flow: backoff %u outside 0..1", rto->backoff);
+    if (p->rto_ticks < rto->min_rto_ticks || p->rto_ticks > rto->max_rto_ticks)
+      return E->fail(-EINVAL, "flow: rto_ticks %u outside min_rto_ticks..max_rto_ticks (%u..%u): it is the initial timer",
+                     p->rto_ticks, rto->min_rto_ticks, rto->max_rto_ticks);
   }
   if (n_flows > static_cast<uint64_t>(E->N) * TGSIM_FLOW_SLOTS)
     return E->fail(-EINVAL, "flow: %llu flows for %u peers (at most %u per source)", static_cast<unsigned long long>(n_flows), E->N,
@@ -2982,6 +3006,12 @@ int tgsim_flow_init_cc(void* e, const tgsim_flow* p, const tgsim_flow_cc* cc, co
   E->flow_cc_on = cc != nullptr;
   E->flow_cc = cc ? *cc : tgsim_flow_cc{};
   if (cc) HIPCHK(E->d_fcc.ensure_exact(n_flows));
+  E->flow_rto_on = rto != nullptr;
+  E->flow_rto = rto ? *rto : tgsim_flow_rto{};
+  if (rto) {
+    HIPCHK(E->d_frt.ensure_exact(n_flows));
+    HIPCHK(E->d_fsent.ensure_exact(n_flows * p->window));
+  }
   E->ping_cur = 0;
   E->ping_kept = 0;
   E->ping_appended = 0;
@@ -3014,7 +3044,10 @@ int tgsim_gen_flow(void* e, uint32_t n_ticks) {
   Eng* E = as_eng(e);
   if (!E || n_ticks == 0 || n_ticks > 65536) return -EINVAL;
   if (!E->flow_on) return E->fail(-EINVAL, "flow: the driver is not armed (tgsim_flow_init)");
-  if (n_ticks > E->flow.rto_ticks)
+  if (E->flow_rto_on && n_ticks > E->flow_rto.min_rto_ticks)
+    return E->fail(-EINVAL, "flow: a window of %u ticks is longer than min_rto_ticks %u (a segment is offered at most once per window)",
+                   n_ticks, E->flow_rto.min_rto_ticks);
+  if (!E->flow_rto_on && n_ticks > E->flow.rto_ticks)
     return E->fail(-EINVAL, "flow: a window of %u ticks is longer than rto_ticks %u (a segment is offered at most once per window)",
                    n_ticks, E->flow.rto_ticks);
   if (!E->staged.empty()) return E->fail(-EBUSY, "host packets already pending for the next step");
@@ -3176,6 +3209,48 @@ int tgsim_flow_cc_report(void* e, tgsim_flow_cc_summary* out) {
   out->cwnd_sum = res[4];
   out->cwnd_min = res[5];
   out->cwnd_max = res[6];
+  return 0;
+}
+
+int64_t tgsim_flow_rto_rows(void* e, uint64_t first, uint64_t n, tgsim_flow_rto_row* out, size_t cap) {
+  Eng* E = as_eng(e);
+  if (!E) return -EINVAL;
+  if (!E->flow_on || !E->flow_rto_on) return E->fail(-EINVAL, "flow_rto_rows: the RTT estimator is not armed (tgsim_flow_init_rto)");
+  if (first > E->n_flows || n > E->n_flows - first)
+    return E->fail(-EINVAL, "flow_rto_rows: flows [%llu, %llu) outside [0, %llu)", static_cast<unsigned long long>(first),
+                   static_cast<unsigned long long>(first + n), static_cast<unsigned long long>(E->n_flows));
+  if (cap < n) return E->fail(-ENOSPC, "flow_rto_rows: %zu rows for %llu", cap, static_cast<unsigned long long>(n));
+  if (n && !out) return E->fail(-EINVAL, "flow_rto_rows: no output buffer");
+  HIPCHK(hipSetDevice(E->dev));
+  int rc = sync_stream(E);
+  if (rc) return rc;
+  if (!n) return 0;
+  HIPCHK(hipMemcpyAsync(out, E->d_frt.p + first, sizeof(tgsim_flow_rto_row) * n, hipMemcpyDeviceToHost, E->st));
+  HIPCHK(hipStreamSynchronize(E->st));
+  return static_cast<int64_t>(n);
+}
+
+int tgsim_flow_rto_report(void* e, tgsim_flow_rto_summary* out) {
+  Eng* E = as_eng(e);
+  if (!E) return -EINVAL;
+  if (!E->flow_on || !E->flow_rto_on) return E->fail(-EINVAL, "flow_rto_report: the RTT estimator is not armed (tgsim_flow_init_rto)");
+  if (!out) return E->fail(-EINVAL, "flow_rto_report: no summary buffer");
+  HIPCHK(hipSetDevice(E->dev));
+  int rc = sync_stream(E);  // the receipts of the last delivery are folded on the delivery stream
+  if (rc) return rc;
+  launch_flow_rto_report(flow_args(E, 0, 0), E->d_pres.p, E->st);
+  HIPCHK(hipGetLastError());
+  unsigned long long res[kFlowRtoResWords];
+  HIPCHK(hipMemcpyAsync(res, E->d_pres.p, sizeof res, hipMemcpyDeviceToHost, E->st));
+  HIPCHK(hipStreamSynchronize(E->st));
+  out->samples = res[0];
+  out->sampled_flows = res[1];
+  out->srtt_sum = res[2];
+  out->srtt_min = ~res[3];  // (the minima are reduced complemented)
+  out->srtt_max = res[4];
+  out->rto_sum = res[5];
+  out->rto_min = ~res[6];
+  out->rto_max = res[7];
   return 0;
 }
 

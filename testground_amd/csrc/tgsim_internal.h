@@ -373,8 +373,15 @@ struct FlowArgs {
   // congestion control (tgsim_flow_init_cc); cc == nullptr: armed without it
   tgsim_flow_cc_row* cc;        // [n_flows]
   uint32_t init_cwnd, init_ssthresh, dupthresh;
+  // RTT estimator and timer backoff (tgsim_flow_init_rto); rt == nullptr: armed
+  // without it, and `rto` above is every segment's timer.  With it `rto` is the initial timer.
+  uint32_t backoff;
+  tgsim_flow_rto_row* rt;       // [n_flows]
+  uint32_t* sent;               // [n_flows][window] ring beside due and att: the tick of attempt 0
+  uint32_t min_rto, max_rto;
 };
 constexpr uint32_t kFlowCcResWords = 7;  // loss_events fast_retransmits timeouts active cwnd_sum cwnd_min cwnd_max
+constexpr uint32_t kFlowRtoResWords = 8;  // samples sampled_flows srtt_sum srtt_min srtt_max rto_sum rto_min rto_max
 
 // Per-group traffic matrix (tgsim_groups_init / tgsim_group_matrix).
 constexpr uint32_t kGroupWords = TGSIM_GROUP_WORDS, kGroupMax = TGSIM_GROUP_MAX;

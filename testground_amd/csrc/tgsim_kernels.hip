@@ -3509,13 +3509,37 @@ __device__ __forceinline__ uint64_t flow_fast_mask(uint64_t bm, uint32_t dupthre
   return ~bm & ((1ull << (63 - __builtin_clzll(m))) - 1ull);
 }
 
+// RTT estimator (tgsim_flow_init_rto).  The kernels below are templates on RTO as
+// they are on CC: the RTO = false instantiations are the code as it was; with RTO the owning lane
+// loads and stores the flow's 32-B rto row beside its flow row in k_flow_recv_ack, k_flow_write reads
+// the row's timer, and a `sent` tick rides the ring beside due and att.
+// One sample m (ticks, <= max_rto <= 2^27) into a row, RFC 6298 in integers: srtt8 <= 8 max_rto and
+// rttvar4 <= 4 max_rto, so nothing leaves 32 bits.
+__device__ __forceinline__ void flow_rto_sample(tgsim_flow_rto_row& q, uint32_t m, uint32_t min_rto, uint32_t max_rto) {
+  if (!q.samples) {
+    q.srtt8 = 8u * m;
+    q.rttvar4 = 2u * m;
+  } else {
+    const int32_t err = (int32_t)m - (int32_t)(q.srtt8 >> 3);
+    q.rttvar4 = q.rttvar4 - (q.rttvar4 >> 2) + (uint32_t)(err < 0 ? -err : err);
+    q.srtt8 += (uint32_t)err;
+  }
+  const uint32_t v = (q.srtt8 >> 3) + (q.rttvar4 > 1u ? q.rttvar4 : 1u);
+  q.rto = v < min_rto ? min_rto : v > max_rto ? max_rto : v;
+  ++q.samples;
+  q.rtt_min = m < q.rtt_min ? m : q.rtt_min;
+  q.rtt_max = m > q.rtt_max ? m : q.rtt_max;
+  q.rtt_last = m;
+}
+
 // Receipt, ACK leg: sequential per flow, so one lane per flow and no atomics on flow state.  The
 // records are grouped by destination and ordered (t_ns, src, seq) inside a group, which is the order
 // the ACKs take effect in: the lane walks its source's range and applies its own slot's ACKs (the
 // lanes of one source's flows are neighbours and read the same records).  Loops: the off[] range, and
 // at most `window` released (CC: and marked) segments per ACK.  A finished flow's FCT goes to the
-// workgroup's LDS histogram, flushed to replica blockIdx mod kPingReplicas.
-template <bool CC>
+// workgroup's LDS histogram, flushed to replica blockIdx mod kPingReplicas.  RTO: a non-stale ACK of
+// attempt 0 is a sample, taken before anything else uses the ACK.
+template <bool CC, bool RTO>
 __global__ __launch_bounds__(256) void k_flow_recv_ack(FlowArgs f, const tgsim_delivery* __restrict__ recs,
                                                        const uint64_t* __restrict__ off, uint64_t n_bound) {
   __shared__ uint32_t hist[kPingMaxBins];
@@ -3531,6 +3555,8 @@ __global__ __launch_bounds__(256) void k_flow_recv_ack(FlowArgs f, const tgsim_d
     tgsim_flow_row row = f.rows[fl];
     [[maybe_unused]] tgsim_flow_cc_row c{};
     if constexpr (CC) c = f.cc[fl];
+    [[maybe_unused]] tgsim_flow_rto_row q{};
+    if constexpr (RTO) q = f.rt[fl];
     uint64_t bm = f.bitmap[fl];
     bool touched = false;
     for (; b < e; ++b) {
@@ -3551,6 +3577,13 @@ __global__ __launch_bounds__(256) void k_flow_recv_ack(FlowArgs f, const tgsim_d
       if (row.state != TGSIM_FLOW_ACTIVE || seg < row.base || seg >= next || (bm >> (seg - row.base) & 1ull)) {
         ++row.stale_acks;
         continue;
+      }
+      if constexpr (RTO) {
+        const uint64_t at = fl * f.window + seg % f.window;
+        if (!(r.seq >> 27 & 15u) && (CC ? f.att[at] & kFlowAttMask : f.att[at]) >= 1u) {
+          const uint32_t m = (uint32_t)(r.t_ns / a.tick_ns + 1) - f.sent[at];
+          flow_rto_sample(q, m < f.max_rto ? m : f.max_rto, f.min_rto, f.max_rto);
+        }
       }
       bm |= 1ull << (seg - row.base);  // (seg - base < window <= 64)
       ++row.acked;
@@ -3622,6 +3655,7 @@ __global__ __launch_bounds__(256) void k_flow_recv_ack(FlowArgs f, const tgsim_d
       f.rows[fl] = row;
       f.bitmap[fl] = bm;
       if constexpr (CC) f.cc[fl] = c;
+      if constexpr (RTO) f.rt[fl] = q;
     }
   }
   __syncthreads();
@@ -3687,8 +3721,9 @@ __global__ __launch_bounds__(256) void k_flow_count(FlowArgs f, uint64_t* counts
 // cursor; the order pass sorts the row), their timers restart, and a flow whose segment ran out of
 // attempts fails at that tick.  Runs only when nothing is late.  CC: an offer with attempt > 0 and no
 // FAST flag is a timeout; timeouts at or above `recover` (read once, ahead of the walk) make one loss
-// event of the flow in this generation.
-template <bool CC>
+// event of the flow in this generation.  RTO: the timer is the flow's own (read once: this pass
+// changes no rto row), shifted by the attempt count with backoff; attempt 0 stamps `sent`.
+template <bool CC, bool RTO>
 __global__ __launch_bounds__(256) void k_flow_write(FlowArgs f, const uint64_t* __restrict__ off, uint32_t* cursor, InRec* out) {
   const uint64_t fl = (uint64_t)blockIdx.x * 256 + threadIdx.x;
   if (fl >= f.n_flows) return;
@@ -3709,6 +3744,8 @@ __global__ __launch_bounds__(256) void k_flow_write(FlowArgs f, const uint64_t* 
   const uint32_t slot = (uint32_t)(fl - f.first[sp.src]);
   uint64_t pos = d.n ? off[sp.src] + atomicAdd(&cursor[sp.src], d.n) : 0;
   [[maybe_unused]] bool loss = false;
+  uint32_t rto = f.rto;
+  if constexpr (RTO) rto = f.rt[fl].rto;
   for (uint32_t i = 0; i < n_fly; ++i) {
     if (bm >> i & 1ull) continue;
     const uint64_t at = fl * f.window + (row.base + i) % f.window;
@@ -3720,7 +3757,15 @@ __global__ __launch_bounds__(256) void k_flow_write(FlowArgs f, const uint64_t* 
     rec.tick = t - win0;
     rec.len = f.seg_len;
     out[pos++] = rec;
-    f.due[at] = t + f.rto;  // (t < 2^31, rto < 2^31)
+    uint32_t timer = rto;
+    if constexpr (RTO) {
+      if (f.backoff) {  // (k <= 15, rto <= 2^27)
+        const uint64_t sh = (uint64_t)rto << k;
+        timer = sh < f.max_rto ? (uint32_t)sh : f.max_rto;
+      }
+      if (k == 0) f.sent[at] = t;
+    }
+    f.due[at] = t + timer;  // (t < 2^31, rto < 2^31)
     if constexpr (CC) {
       if (k > 0 && !(f.att[at] & kFlowFast)) {
         ++c.timeouts;
@@ -3750,7 +3795,8 @@ __global__ __launch_bounds__(256) void k_flow_write(FlowArgs f, const uint64_t* 
 
 // tgsim_flow_init: every flow's first window of segments due at its start tick; the histogram
 // replicas and the calendar's counters.  CC: the cc row, with the first init_cwnd segments released.
-template <bool CC>
+// RTO: the rto row, with the initial timer.
+template <bool CC, bool RTO>
 __global__ __launch_bounds__(256) void k_flow_init(FlowArgs f) {
   const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
   if (i < f.n_flows) {
@@ -3760,6 +3806,13 @@ __global__ __launch_bounds__(256) void k_flow_init(FlowArgs f) {
     for (uint32_t k = 0; k < f.window; ++k) {
       f.due[i * f.window + k] = sp.start_tick;
       f.att[i * f.window + k] = 0;
+      if constexpr (RTO) f.sent[i * f.window + k] = 0u;
+    }
+    if constexpr (RTO) {
+      tgsim_flow_rto_row q{};
+      q.rto = f.rto;
+      q.rtt_min = ~0u;
+      f.rt[i] = q;
     }
     if constexpr (CC) {
       tgsim_flow_cc_row c{};
@@ -3807,6 +3860,44 @@ __global__ __launch_bounds__(256) void k_flow_cc_report(FlowArgs f, unsigned lon
     const uint32_t w = threadIdx.x;
     if (w == 5) atomicMin(&res[w], acc[w]);
     else if (w == 6) atomicMax(&res[w], acc[w]);
+    else atomicAdd(&res[w], acc[w]);
+  }
+}
+
+// tgsim_flow_rto_report, as k_flow_cc_report: samples over every flow; the count, and the sum, minimum
+// and maximum of srtt8 >> 3 and of rto, over the flows with a sample.  The two minima travel
+// complemented (words 3 and 6 hold the maximum of ~x), so res starts as zeros.
+__global__ __launch_bounds__(256) void k_flow_rto_report(FlowArgs f, unsigned long long* res) {
+  __shared__ unsigned long long acc[kFlowRtoResWords];
+  if (threadIdx.x < kFlowRtoResWords) acc[threadIdx.x] = 0ull;
+  __syncthreads();
+  uint64_t v[kFlowRtoResWords] = {};
+  for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < f.n_flows; i += (uint64_t)gridDim.x * 256) {
+    const tgsim_flow_rto_row q = f.rt[i];
+    if (!q.samples) continue;
+    const uint64_t srtt = q.srtt8 >> 3, nsrtt = ~srtt, nrto = ~(uint64_t)q.rto;
+    v[0] += q.samples;
+    ++v[1];
+    v[2] += srtt;
+    v[3] = nsrtt > v[3] ? nsrtt : v[3];
+    v[4] = srtt > v[4] ? srtt : v[4];
+    v[5] += q.rto;
+    v[6] = nrto > v[6] ? nrto : v[6];
+    v[7] = q.rto > v[7] ? q.rto : v[7];
+  }
+#pragma unroll
+  for (uint32_t w = 0; w < kFlowRtoResWords; ++w) {
+    const bool is_max = w == 3 || w == 4 || w == 6 || w == 7;
+    const uint64_t t = is_max ? wave_min_max_u64(v[w], true) : wave_sum(v[w]);
+    if ((threadIdx.x & 63u) == 0) {
+      if (is_max) atomicMax(&acc[w], (unsigned long long)t);
+      else atomicAdd(&acc[w], (unsigned long long)t);
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x < kFlowRtoResWords && acc[1]) {
+    const uint32_t w = threadIdx.x;
+    if (w == 3 || w == 4 || w == 6 || w == 7) atomicMax(&res[w], acc[w]);
     else atomicAdd(&res[w], acc[w]);
   }
 }
@@ -5164,16 +5255,20 @@ void launch_ping_report(const PingArgs& a, unsigned long long* res, hipStream_t 
 void launch_flow_init(const FlowArgs& f, hipStream_t st) {
   const uint64_t n = std::max<uint64_t>(f.n_flows, (uint64_t)kPingReplicas * kPingMaxBins);
   const dim3 grid((uint32_t)((n + 255) / 256));
-  if (f.cc) hipLaunchKernelGGL(k_flow_init<true>, grid, dim3(256), 0, st, f);
-  else hipLaunchKernelGGL(k_flow_init<false>, grid, dim3(256), 0, st, f);
+  if (f.cc && f.rt) hipLaunchKernelGGL((k_flow_init<true, true>), grid, dim3(256), 0, st, f);
+  else if (f.cc) hipLaunchKernelGGL((k_flow_init<true, false>), grid, dim3(256), 0, st, f);
+  else if (f.rt) hipLaunchKernelGGL((k_flow_init<false, true>), grid, dim3(256), 0, st, f);
+  else hipLaunchKernelGGL((k_flow_init<false, false>), grid, dim3(256), 0, st, f);
 }
 
 void launch_flow_recv(const FlowArgs& f, const tgsim_delivery* recs, const uint64_t* off, uint32_t n_dst,
                       uint64_t n_bound, hipStream_t st) {
   hipLaunchKernelGGL(k_flow_recv_data, dim3(ping_grid(n_bound)), dim3(256), 0, st, f, recs, off, n_dst, n_bound);
   const dim3 grid((uint32_t)((f.n_flows + 255) / 256));
-  if (f.cc) hipLaunchKernelGGL(k_flow_recv_ack<true>, grid, dim3(256), 0, st, f, recs, off, n_bound);
-  else hipLaunchKernelGGL(k_flow_recv_ack<false>, grid, dim3(256), 0, st, f, recs, off, n_bound);
+  if (f.cc && f.rt) hipLaunchKernelGGL((k_flow_recv_ack<true, true>), grid, dim3(256), 0, st, f, recs, off, n_bound);
+  else if (f.cc) hipLaunchKernelGGL((k_flow_recv_ack<true, false>), grid, dim3(256), 0, st, f, recs, off, n_bound);
+  else if (f.rt) hipLaunchKernelGGL((k_flow_recv_ack<false, true>), grid, dim3(256), 0, st, f, recs, off, n_bound);
+  else hipLaunchKernelGGL((k_flow_recv_ack<false, false>), grid, dim3(256), 0, st, f, recs, off, n_bound);
 }
 
 void launch_flow_count(const FlowArgs& f, uint64_t* counts, uint32_t* cursor, uint64_t cal_bound, hipStream_t st) {
@@ -5189,8 +5284,10 @@ void launch_flow_count(const FlowArgs& f, uint64_t* counts, uint32_t* cursor, ui
 void launch_flow_write(const FlowArgs& f, const uint64_t* off, uint32_t* cursor, InRec* tmp, InRec* out,
                        uint64_t cal_bound, hipStream_t st) {
   const dim3 grid((uint32_t)((f.n_flows + 255) / 256));
-  if (f.cc) hipLaunchKernelGGL(k_flow_write<true>, grid, dim3(256), 0, st, f, off, cursor, tmp);
-  else hipLaunchKernelGGL(k_flow_write<false>, grid, dim3(256), 0, st, f, off, cursor, tmp);
+  if (f.cc && f.rt) hipLaunchKernelGGL((k_flow_write<true, true>), grid, dim3(256), 0, st, f, off, cursor, tmp);
+  else if (f.cc) hipLaunchKernelGGL((k_flow_write<true, false>), grid, dim3(256), 0, st, f, off, cursor, tmp);
+  else if (f.rt) hipLaunchKernelGGL((k_flow_write<false, true>), grid, dim3(256), 0, st, f, off, cursor, tmp);
+  else hipLaunchKernelGGL((k_flow_write<false, false>), grid, dim3(256), 0, st, f, off, cursor, tmp);
   if (cal_bound) hipLaunchKernelGGL(k_ping_write_cal, dim3(ping_grid(cal_bound)), dim3(256), 0, st, f.cal, off, cursor, tmp);
   hipLaunchKernelGGL(k_ping_order, dim3((f.cal.n_peers + 3) / 4), dim3(256), 0, st, off, tmp, out, f.cal.n_peers);
 }
@@ -5205,6 +5302,11 @@ void launch_flow_cc_report(const FlowArgs& f, unsigned long long* res, hipStream
   words_only.n_bins = 0;
   hipLaunchKernelGGL(k_ping_report_init, dim3(1), dim3(256), 0, st, words_only, res, kFlowCcResWords, 5u);
   hipLaunchKernelGGL(k_flow_cc_report, dim3(std::min(ping_grid(f.n_flows), 256u)), dim3(256), 0, st, f, res);
+}
+
+void launch_flow_rto_report(const FlowArgs& f, unsigned long long* res, hipStream_t st) {
+  (void)hipMemsetAsync(res, 0, sizeof(unsigned long long) * kFlowRtoResWords, st);
+  hipLaunchKernelGGL(k_flow_rto_report, dim3(std::min(ping_grid(f.n_flows), 256u)), dim3(256), 0, st, f, res);
 }
 
 void launch_ping_pairs(const PingArgs& a, uint64_t i0, uint64_t n, tgsim_ping_pair* out, hipStream_t st) {

@@ -99,6 +99,9 @@ void launch_flow_report(const FlowArgs& f, unsigned long long* res, hipStream_t 
 // With f.cc set the launchers above run the kernels' congestion-control instantiations.  _cc_report:
 // res = kFlowCcResWords words.
 void launch_flow_cc_report(const FlowArgs& f, unsigned long long* res, hipStream_t st);
+// With f.rt set they run the RTT-estimator instantiations (either way with f.cc).  _rto_report: res =
+// kFlowRtoResWords words, the two minima complemented (words 3 and 6 hold the maximum of ~x).
+void launch_flow_rto_report(const FlowArgs& f, unsigned long long* res, hipStream_t st);
 // Per-group traffic matrix (tgsim_group_matrix).  _src: words 0..9 from a window's input (off[n_src + 1],
 // in, verdict) behind its simulate kernel; n_in: the window's offered packets (picks the lanes per
 // source).  _dst: words 10..13 from delivery-ordered records, segment sg = off[sg] ..

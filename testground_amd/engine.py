@@ -232,15 +232,21 @@ class CABIEngine:
 
     # -- flow driver (tgsim_flow_*) ----------------------------------------------------------------
     def flow_init(self, flows=None, seg_len: int = 1460, ack_len: int = 64, window: int = 16, rto_ticks: int = 1,
-                  max_attempts: int = 8, bin_ns: int = 0, n_bins: int = 0, cc: Optional[dict] = None) -> None:
+                  max_attempts: int = 8, bin_ns: int = 0, n_bins: int = 0, cc: Optional[dict] = None,
+                  rto: Optional[dict] = None) -> None:
         """Arms the device flow driver: `flows` is an abi.FLOW_SPEC_DTYPE table sorted by src
         (workloads.flow_table_mesh); a fixed window of `window` segments, one ACK per delivered
         segment, a retransmission timer of rto_ticks per segment, at most max_attempts offers of a
         segment (include/tgsim.h).  flow_init(None) disarms it.  `cc` (a dict of init_cwnd,
         init_ssthresh and dupthresh; missing keys as workloads.FLOW_CC_DEFAULT) arms it with the
-        congestion window and fast retransmit of tgsim_flow_init_cc: `window` is then the cap."""
+        congestion window and fast retransmit of tgsim_flow_init_cc: `window` is then the cap.  `rto`
+        (a dict of min_rto_ticks, max_rto_ticks and backoff; missing keys as
+        workloads.FLOW_RTO_DEFAULT) arms it through tgsim_flow_init_rto with the RTT estimator:
+        rto_ticks is then each flow's initial timer, and min_rto_ticks the longest window."""
+        if rto is not None and flows is not None:
+            return self._flow_init_rto(flows, abi.Flow(seg_len, ack_len, window, rto_ticks, max_attempts, n_bins, bin_ns), cc, rto)
         fn = self._gossip_fn("flow_init" if cc is None or flows is None else "flow_init_cc")
-        self.flow_cc_armed = False
+        self.flow_cc_armed = self.flow_rto_armed = False
         if flows is None:
             self._check(fn(self._h, None, None, 0), "flow_init")
             self._n_flows = None
@@ -256,6 +262,34 @@ class CABIEngine:
             self._check(fn(self._h, C.byref(p), C.byref(c), t.ctypes.data, len(t)), "flow_init_cc")
             self.flow_cc_armed = True
         self._n_flows = len(t)
+
+    def _flow_init_rto(self, flows, p, cc: Optional[dict], rto: dict) -> None:
+        fn = self._gossip_fn("flow_init_rto")
+        self.flow_cc_armed = self.flow_rto_armed = False
+        t = np.ascontiguousarray(flows, dtype=abi.FLOW_SPEC_DTYPE)
+        if t.ndim != 1:
+            raise ValueError("flow_init: flows must be a 1-d abi.FLOW_SPEC_DTYPE table")
+        c = None if cc is None else C.byref(abi.FlowCC(cc.get("init_cwnd", 1), cc.get("init_ssthresh", 0), cc.get("dupthresh", 3), 0))
+        r = abi.FlowRto(rto.get("min_rto_ticks", 1), rto.get("max_rto_ticks", abi.FLOW_MAX_RTO), rto.get("backoff", 1), 0)
+        self._check(fn(self._h, C.byref(p), c, C.byref(r), t.ctypes.data, len(t)), "flow_init_rto")
+        self.flow_cc_armed, self.flow_rto_armed = cc is not None, True
+        self._n_flows = len(t)
+
+    def flow_rto_rows(self, first: int = 0, n: Optional[int] = None) -> np.ndarray:
+        """abi.FLOW_RTO_ROW_DTYPE rows of flows [first, first + n) (tgsim_flow_rto_rows)."""
+        fn = self._gossip_fn("flow_rto_rows")
+        total = getattr(self, "_n_flows", None) or 0  # (unarmed: the call says so)
+        n = max(total - first, 0) if n is None else n
+        out = np.zeros(n, dtype=abi.FLOW_RTO_ROW_DTYPE)
+        self._check(fn(self._h, first, n, out.ctypes.data, len(out)), "flow_rto_rows")
+        return out
+
+    def flow_rto_report(self) -> dict:
+        """The estimator's summary (abi.FLOW_RTO_SUMMARY_FIELDS), reduced on the device
+        (tgsim_flow_rto_report); every field but samples is over the flows with a sample."""
+        s = abi.FlowRtoSummary()
+        self._check(self._gossip_fn("flow_rto_report")(self._h, C.byref(s)), "flow_rto_report")
+        return {k: int(getattr(s, k)) for k in abi.FLOW_RTO_SUMMARY_FIELDS}
 
     def flow_cc_rows(self, first: int = 0, n: Optional[int] = None) -> np.ndarray:
         """abi.FLOW_CC_ROW_DTYPE rows of flows [first, first + n) (tgsim_flow_cc_rows)."""

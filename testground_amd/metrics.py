@@ -104,7 +104,9 @@ def flow_lines(report: Dict, bin_ns: int, plan: str, run: str, ts_ns: int) -> Li
 
     A report that carries the congestion summary under "cc" (dict(eng.flow_report(),
     cc=eng.flow_cc_report()), flows armed with cc) adds one `flow.cc.<field>` line per field of it,
-    the cwnd minimum and maximum only while a flow is ACTIVE."""
+    the cwnd minimum and maximum only while a flow is ACTIVE.  One that carries the estimator's summary
+    under "rto" (eng.flow_rto_report(), flows armed with rto) adds one `flow.rto.<field>` line per
+    field of it, the minima and maxima only once a flow has a sample."""
     tags = f"run={_escape(run)}"
     out: List[str] = []
     for name, key in FLOW_METRICS:
@@ -119,6 +121,11 @@ def flow_lines(report: Dict, bin_ns: int, plan: str, run: str, ts_ns: int) -> Li
         if key in ("cwnd_min", "cwnd_max") and not cc["active"]:
             continue
         out.append(f"{_escape(f'results.{plan}.flow.cc.{key}')},{tags} value={int(cc[key])}i {ts_ns}")
+    rto = report.get("rto")
+    for key in abi.FLOW_RTO_SUMMARY_FIELDS if rto else ():
+        if key.endswith(("_min", "_max")) and not rto["sampled_flows"]:
+            continue
+        out.append(f"{_escape(f'results.{plan}.flow.rto.{key}')},{tags} value={int(rto[key])}i {ts_ns}")
     meas = _escape(f"results.{plan}.flow.fct_hist")
     out += [f"{meas},{tags},bin={b * int(bin_ns)} value={int(c)}i {ts_ns}" for b, c in enumerate(report["hist"]) if c]
     return out

@@ -455,12 +455,24 @@ class FlowModel:
     def _unacked(self, f: int):
         return [i for i in range(int(self.base[f]), self._next(f)) if i not in self.acked_segs[f]]
 
+    # The three places the RTT estimator (FlowRtoMixin) changes: the longest window, a segment's timer
+    # when it is offered at tick t with attempt count k, and a non-stale ACK ahead of anything else.
+    def _window_limit(self) -> Tuple[str, int]:
+        return "rto_ticks", self.flow["rto_ticks"]
+
+    def _timer(self, f: int, i: int, k: int, t: int) -> int:
+        return self.flow["rto_ticks"]
+
+    def _non_stale_ack(self, f: int, seg: int, seq: int, tick: int) -> None:
+        pass
+
     def window_packets(self, window: int) -> np.ndarray:
         """The window's offered packets in (src, tick, seq, dst) order: the segments due in it, and the
         calendar's ACKs due in it, which leave the calendar."""
         p, win0, win1 = self.flow, self.now, self.now + window
-        if window > p["rto_ticks"]:
-            raise ValueError(f"flow: a window of {window} ticks is longer than rto_ticks {p['rto_ticks']}")
+        name, longest = self._window_limit()
+        if window > longest:
+            raise ValueError(f"flow: a window of {window} ticks is longer than {name} {longest}")
         w = p["window"]
         live = np.nonzero(self.state == abi.FLOW_ACTIVE)[0]
         late = [int(self.cal[:, 0].min())] if len(self.cal) else []
@@ -478,7 +490,7 @@ class FlowModel:
                     continue
                 rows.append((int(self.spec["src"][f]), int(self.spec["dst"][f]),
                              k << abi.FLOW_ATTEMPT_SHIFT | int(self.slot[f]) << abi.FLOW_SLOT_SHIFT | i, t, p["seg_len"]))
-                self.due[f, i % w] = t + p["rto_ticks"]
+                self.due[f, i % w] = t + self._timer(f, i, k, t)
                 self.att[f, i % w] = k + 1
                 self.offered[f] += 1
                 self.retransmits[f] += k > 0
@@ -537,6 +549,7 @@ class FlowModel:
             if self.state[f] != abi.FLOW_ACTIVE or seg < self.base[f] or seg >= nxt or seg in self.acked_segs[f]:
                 self.stale[f] += 1
                 continue
+            self._non_stale_ack(f, seg, seq, tick)
             self.acked_segs[f].add(seg)
             self.acked[f] += 1
             while int(self.base[f]) in self.acked_segs[f]:
@@ -633,8 +646,9 @@ class FlowCCModel(FlowModel):
 
     def window_packets(self, window: int) -> np.ndarray:
         p, win0, win1 = self.flow, self.now, self.now + window
-        if window > p["rto_ticks"]:
-            raise ValueError(f"flow: a window of {window} ticks is longer than rto_ticks {p['rto_ticks']}")
+        name, longest = self._window_limit()
+        if window > longest:
+            raise ValueError(f"flow: a window of {window} ticks is longer than {name} {longest}")
         w = p["window"]
         live = np.nonzero(self.state == abi.FLOW_ACTIVE)[0]
         late = [int(self.cal[:, 0].min())] if len(self.cal) else []
@@ -654,7 +668,7 @@ class FlowCCModel(FlowModel):
                     continue
                 rows.append((int(self.spec["src"][f]), int(self.spec["dst"][f]),
                              k << abi.FLOW_ATTEMPT_SHIFT | int(self.slot[f]) << abi.FLOW_SLOT_SHIFT | i, t, p["seg_len"]))
-                self.due[f, i % w] = t + p["rto_ticks"]
+                self.due[f, i % w] = t + self._timer(f, i, k, t)
                 self.att[f, i % w] = k + 1
                 self.offered[f] += 1
                 self.retransmits[f] += k > 0
@@ -715,6 +729,7 @@ class FlowCCModel(FlowModel):
             if self.state[f] != abi.FLOW_ACTIVE or seg < self.base[f] or seg >= self.next[f] or seg in self.acked_segs[f]:
                 self.stale[f] += 1
                 continue
+            self._non_stale_ack(f, seg, seq, tick)
             # 1, 2: mark, advance base
             self.acked_segs[f].add(seg)
             self.acked[f] += 1
@@ -783,25 +798,130 @@ class FlowCCModel(FlowModel):
                 "cwnd_max": int(cw.max()) if len(cw) else 0}
 
 
+FLOW_RTO_DEFAULT = dict(min_rto_ticks=1, max_rto_ticks=abi.FLOW_MAX_RTO, backoff=1)
+
+
+class FlowRtoMixin:
+    """The RTT estimator and timer backoff of tgsim_flow_init_rto (include/tgsim.h) over FlowModel or
+    FlowCCModel: `rto` holds min_rto_ticks, max_rto_ticks and backoff; flow["rto_ticks"] is every
+    flow's initial timer.  An ACK of attempt 0 is a sample (RFC 6298 in integer ticks), a segment's
+    timer is the flow's rto, doubled per earlier offer with backoff and capped at max_rto_ticks."""
+
+    def __init__(self, eng, flow: Dict, flows: np.ndarray, *cc, rto: Dict):
+        super().__init__(eng, flow, flows, *cc)
+        self.rto_p = dict(FLOW_RTO_DEFAULT, **rto)
+        r, t0 = self.rto_p, self.flow["rto_ticks"]
+        if r["min_rto_ticks"] < 1:
+            raise ValueError(f"flow: min_rto_ticks {r['min_rto_ticks']} below 1")
+        if not r["min_rto_ticks"] <= r["max_rto_ticks"] <= abi.FLOW_MAX_RTO:
+            raise ValueError(f"flow: max_rto_ticks {r['max_rto_ticks']} outside min_rto_ticks ({r['min_rto_ticks']})..2^27")
+        if r["backoff"] not in (0, 1):
+            raise ValueError(f"flow: backoff {r['backoff']} outside 0..1")
+        if not r["min_rto_ticks"] <= t0 <= r["max_rto_ticks"]:
+            raise ValueError(f"flow: rto_ticks {t0} outside min_rto_ticks..max_rto_ticks")
+        nf, w = len(self.spec), self.flow["window"]
+        self.srtt8 = np.zeros(nf, dtype=np.int64)
+        self.rttvar4 = np.zeros(nf, dtype=np.int64)
+        self.rto = np.full(nf, t0, dtype=np.int64)
+        self.samples = np.zeros(nf, dtype=np.int64)
+        self.rtt_min = np.full(nf, 0xFFFFFFFF, dtype=np.int64)
+        self.rtt_max = np.zeros(nf, dtype=np.int64)
+        self.rtt_last = np.zeros(nf, dtype=np.int64)
+        self.sent = np.zeros((nf, w), dtype=np.int64)  # ring, beside due and att
+        self.sample_log = [[] for _ in range(nf)]  # per flow, the samples in the order taken
+        # what the run exercised: samples from a segment retransmitted since, rto clamped at either end,
+        # timers shifted by two or more, shifted timers capped, ACKs of a later attempt (no sample)
+        self.sampled_after_retransmit = self.clamped_min = self.clamped_max = 0
+        self.shifted_twice = self.shift_capped = self.unsampled_attempts = 0
+
+    def _window_limit(self) -> Tuple[str, int]:
+        return "min_rto_ticks", self.rto_p["min_rto_ticks"]
+
+    def _timer(self, f: int, i: int, k: int, t: int) -> int:
+        r, rto = self.rto_p, int(self.rto[f])
+        if k == 0:
+            self.sent[f, i % self.flow["window"]] = t
+        if not r["backoff"]:
+            return rto
+        self.shifted_twice += k >= 2
+        self.shift_capped += k >= 1 and rto << k > r["max_rto_ticks"]
+        return min(rto << k, r["max_rto_ticks"])
+
+    def _non_stale_ack(self, f: int, seg: int, seq: int, tick: int) -> None:
+        r, at = self.rto_p, seg % self.flow["window"]
+        if seq >> abi.FLOW_ATTEMPT_SHIFT & 15:
+            self.unsampled_attempts += 1
+            return
+        if self.att[f, at] < 1:
+            return
+        m = min(tick - int(self.sent[f, at]), r["max_rto_ticks"])
+        if self.samples[f] == 0:
+            self.srtt8[f], self.rttvar4[f] = 8 * m, 2 * m
+        else:
+            err = m - (int(self.srtt8[f]) >> 3)
+            self.rttvar4[f] = self.rttvar4[f] - (int(self.rttvar4[f]) >> 2) + abs(err)
+            self.srtt8[f] += err
+        v = (int(self.srtt8[f]) >> 3) + max(int(self.rttvar4[f]), 1)
+        self.rto[f] = min(max(v, r["min_rto_ticks"]), r["max_rto_ticks"])
+        self.clamped_min += v < r["min_rto_ticks"]
+        self.clamped_max += v > r["max_rto_ticks"]
+        self.sampled_after_retransmit += self.att[f, at] >= 2
+        self.samples[f] += 1
+        self.rtt_min[f], self.rtt_max[f], self.rtt_last[f] = min(self.rtt_min[f], m), max(self.rtt_max[f], m), m
+        self.sample_log[f].append(m)
+
+    def rto_rows(self) -> np.ndarray:
+        out = np.zeros(len(self.spec), dtype=abi.FLOW_RTO_ROW_DTYPE)
+        for key, v in (("srtt8", self.srtt8), ("rttvar4", self.rttvar4), ("rto", self.rto), ("samples", self.samples),
+                       ("rtt_min", self.rtt_min), ("rtt_max", self.rtt_max), ("rtt_last", self.rtt_last)):
+            out[key] = v
+        return out
+
+    def rto_report(self) -> Dict:
+        on = self.samples > 0
+        srtt, rto, none = self.srtt8[on] >> 3, self.rto[on], int(np.iinfo(np.uint64).max)
+        return {"samples": int(self.samples.sum()), "sampled_flows": int(on.sum()),
+                "srtt_sum": int(srtt.sum()), "srtt_min": int(srtt.min()) if on.any() else none,
+                "srtt_max": int(srtt.max()) if on.any() else 0,
+                "rto_sum": int(rto.sum()), "rto_min": int(rto.min()) if on.any() else none,
+                "rto_max": int(rto.max()) if on.any() else 0}
+
+
+class FlowRtoModel(FlowRtoMixin, FlowModel):
+    """FlowModel armed with `rto`: FlowRtoModel(eng, flow, flows, rto=dict(...))."""
+
+
+class FlowCCRtoModel(FlowRtoMixin, FlowCCModel):
+    """FlowCCModel armed with `rto`: FlowCCRtoModel(eng, flow, flows, cc, rto=dict(...))."""
+
+
 def flow_reference(eng, flow: Dict, flows: np.ndarray, n_windows: int, window: int, probe_at=(), before=None,
-                   cc=None) -> Dict:
+                   cc=None, rto=None) -> Dict:
     """The flow loop driven from the host over `eng` (submit / step / verdicts / drain): per-window
     (verdicts, deliveries) under "windows", the final "rows" and "summary" (report fields and hist),
     and under "probes" the (rows, summary) after each window index in probe_at.  before(w) runs ahead
     of window w (a reshape, a partition).  The model itself is under "model".  With `cc` (the dict of
     Engine.flow_init) the model is FlowCCModel, the result has "cc_rows" and "cc_summary" too, and a
-    probe is (rows, summary, cc_rows, cc_summary)."""
-    m = FlowModel(eng, flow, flows) if cc is None else FlowCCModel(eng, flow, flows, cc)
+    probe is (rows, summary, cc_rows, cc_summary).  With `rto` (the dict of Engine.flow_init) the model
+    is FlowRtoModel or FlowCCRtoModel, the result has "rto_rows" and "rto_summary" too, and a probe ends
+    with (rto_rows, rto_summary)."""
+    if rto is None:
+        m = FlowModel(eng, flow, flows) if cc is None else FlowCCModel(eng, flow, flows, cc)
+    else:
+        m = FlowRtoModel(eng, flow, flows, rto=rto) if cc is None else FlowCCRtoModel(eng, flow, flows, cc, rto=rto)
     out = {"windows": [], "probes": {}, "model": m}
     for w in range(n_windows):
         if before is not None:
             before(w)
         out["windows"].append(m.step(window))
         if w in probe_at:
-            out["probes"][w] = (m.rows(), m.report()) + (() if cc is None else (m.cc_rows(), m.cc_report()))
+            out["probes"][w] = ((m.rows(), m.report()) + (() if cc is None else (m.cc_rows(), m.cc_report()))
+                                + (() if rto is None else (m.rto_rows(), m.rto_report())))
     out["rows"], out["summary"] = m.rows(), m.report()
     if cc is not None:
         out["cc_rows"], out["cc_summary"] = m.cc_rows(), m.cc_report()
+    if rto is not None:
+        out["rto_rows"], out["rto_summary"] = m.rto_rows(), m.rto_report()
     return out
 
 
@@ -809,9 +929,10 @@ def flow_run(eng, n_windows: int, window: int, collect: bool = False, probe_at=(
     """The device loop on an armed engine (Engine.flow_init): n_windows of gen_flow + step.  Nothing
     reaches the host unless asked for: collect keeps each window's (verdicts, deliveries), probe_at
     the (rows, report) after those windows, and the (cc rows, cc report) beside them when the engine
-    is armed with congestion control."""
+    is armed with congestion control, and the (rto rows, rto report) last when it is armed with the RTT
+    estimator."""
     out = {"windows": [], "probes": {}}
-    cc = getattr(eng, "flow_cc_armed", False)
+    cc, rto = getattr(eng, "flow_cc_armed", False), getattr(eng, "flow_rto_armed", False)
     for w in range(n_windows):
         if before is not None:
             before(w)
@@ -820,7 +941,8 @@ def flow_run(eng, n_windows: int, window: int, collect: bool = False, probe_at=(
         if collect:
             out["windows"].append((eng.verdicts(), eng.drain()))
         if w in probe_at:
-            out["probes"][w] = (eng.flow_rows(), eng.flow_report()) + ((eng.flow_cc_rows(), eng.flow_cc_report()) if cc else ())
+            out["probes"][w] = ((eng.flow_rows(), eng.flow_report()) + ((eng.flow_cc_rows(), eng.flow_cc_report()) if cc else ())
+                                + ((eng.flow_rto_rows(), eng.flow_rto_report()) if rto else ()))
     return out
 
 
