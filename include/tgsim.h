@@ -178,7 +178,10 @@ typedef struct {
  * Flood f (0 <= f < n_floods) starts at tick start_tick + f * start_gap_ticks at its origin peer;
  * every peer forwards a flood once, on its first receipt, to its `degree` out-neighbours
  * (a fixed hash of (seed, peer, k)), one msg_len-byte packet each, seq = f * degree + k, offered
- * at the tick after the receipt's delivery time.  Corrupted deliveries are not receipts. */
+ * at the tick after the receipt's delivery time.  Corrupted deliveries are not receipts.
+ * Flood starts and receipts are 32-bit ticks: tgsim_gossip_init returns -EINVAL when the last flood's
+ * start tick, start_tick + (n_floods - 1) * start_gap_ticks, exceeds 0xFFFFFFFE, and tgsim_gen_gossip
+ * -EOVERFLOW when its window ends beyond tick 0xFFFFFFFE (a receipt later than that saturates there). */
 typedef struct {
     uint32_t n_floods;         /* 1..64                                                      */
     uint32_t degree;           /* out-neighbours per peer, 1..64                             */
@@ -220,7 +223,11 @@ int tgsim_gen_storm(void* engine, double lambda, uint32_t n_ticks);
  * On an engine that owns every peer the step is asynchronous on the engine's stream (with
  * TGSIM_OPT_DISCARD_DELIVERIES and no gossip driver it returns without a host round trip); every
  * call that reads results (drain, verdicts, stats, gossip_reached, sim_kernel_ms) synchronizes
- * first.  A simulated-time overflow (-EOVERFLOW) is then reported by the next step or reader. */
+ * first.  A simulated-time overflow (-EOVERFLOW) is then reported by the next step or reader.
+ * Simulated-time overflow: any eligibility time (offer time + netem delay) or departure time (HTB's,
+ * the t_ns of the delivery record) at or beyond 2^46 ns (19.5 simulated hours), whatever tick_ns is;
+ * the window's results are not handed out and the error is sticky: from the reader of that window
+ * on, every step and every reader (drain, verdicts, stats, sync, the reports) returns -EOVERFLOW.  A window may end beyond 2^46 ns as long as no packet's times do. */
 int tgsim_step(void* engine, uint32_t n_ticks);
 /* n_steps consecutive tgsim_step(engine, n_ticks) calls, with identical results (verdicts then
  * refer to the last window).  Windows of generated traffic (tgsim_gen_storm) on an engine that owns

@@ -1085,6 +1085,9 @@ int tgo_gossip_init(void* p, const tgsim_gossip* g) {
         g->msg_len == 0 || g->msg_len > 65535 || o->o.n_peers < 2)
         return -EINVAL;
     if (g->start_tick < o->now_tick) return fail(o, -EINVAL, "gossip: start tick in the past");
+    /* receipts and flood starts are 32-bit ticks that saturate at 0xFFFFFFFE (0xFFFFFFFF: no receipt) */
+    if (g->start_tick + (uint64_t)(g->n_floods - 1) * g->start_gap_ticks > 0xFFFFFFFEull)
+        return fail(o, -EINVAL, "gossip: the schedule ends beyond tick 2^32");
     o->g = *g;
     free(o->g_first);
     free(o->g_fwd);
@@ -1120,6 +1123,8 @@ int tgo_gen_gossip(void* p, uint32_t n_ticks) {
     if (o->n_off) return fail(o, -EBUSY, "host packets already pending for the next step");
     if (o->gossip_late)
         return fail(o, -EINVAL, "gossip: a receipt preceded an earlier window (tgsim_gossip_init starts a new flood)");
+    if (o->now_tick + o->gq_ticks + n_ticks > 0xFFFFFFFEull)
+        return fail(o, -EOVERFLOW, "gossip: the window ends beyond tick 2^32");
     for (size_t i = 0; i < o->gq_n; ++i) /* a queued late window is reported first */
         if (o->gq[i].late) return gen_report_late(o, i);
     uint64_t A = o->now_tick + o->gq_ticks, B = A + n_ticks;

@@ -2511,6 +2511,9 @@ int tgsim_gossip_init(void* e, const tgsim_gossip* g) {
   if (E->ping_on) return E->fail(-EBUSY, "%s: the ping driver is armed (tgsim_ping_init(engine, NULL, NULL) disarms it)", "gossip_init");
   if (E->flow_on) return E->fail(-EBUSY, "%s: the flow driver is armed (tgsim_flow_init(engine, NULL, NULL, 0) disarms it)", "gossip_init");
   if (g->start_tick < E->now_tick + E->gen_q_ticks) return E->fail(-EINVAL, "gossip: start tick in the past");
+  // receipts and flood starts are 32-bit ticks that saturate at 0xFFFFFFFE (0xFFFFFFFF: no receipt)
+  if (g->start_tick + static_cast<uint64_t>(g->n_floods - 1) * g->start_gap_ticks > 0xFFFFFFFEull)
+    return E->fail(-EINVAL, "gossip: the schedule ends beyond tick 2^32");
   HIPCHK(hipSetDevice(E->dev));
   E->gossip = *g;
   E->gossip_late = false;
@@ -2574,6 +2577,8 @@ int tgsim_gen_gossip(void* e, uint32_t n_ticks) {
   if (!E->staged.empty()) return E->fail(-EBUSY, "host packets already pending for the next step");
   if (E->gossip_late)
     return E->fail(-EINVAL, "gossip: a receipt preceded an earlier window (tgsim_gossip_init starts a new flood)");
+  if (E->now_tick + E->gen_q_ticks + n_ticks > 0xFFFFFFFEull)
+    return E->fail(-EOVERFLOW, "gossip: the window ends beyond tick 2^32");
   HIPCHK(hipSetDevice(E->dev));
   for (size_t i = 0; i < E->gen_q.size(); ++i) {  // a window still unsized is sized (and written) before
                                                   // this one runs
@@ -3564,6 +3569,8 @@ int tgsim_stats(void* e, tgsim_stats_t* out) {
   HIPCHK(hipSetDevice(E->dev));
   int rc = sync_stream(E);
   if (rc) return rc;
+  // the counters of a window whose simulation failed (sticky error bits) are not the run's
+  if ((rc = check_sim_error(E))) return rc;
   std::vector<unsigned long long> all(static_cast<size_t>(kStSlots) * kStatCopies);
   HIPCHK(hipMemcpy(all.data(), E->d_stats.p, sizeof(unsigned long long) * all.size(), hipMemcpyDeviceToHost));
   unsigned long long s[kStSlots] = {};

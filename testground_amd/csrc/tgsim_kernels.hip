@@ -453,6 +453,7 @@ struct SimQueue {
   uint32_t n_emit, src;
   // per-lane accumulators (summed over the wave at the end)
   uint32_t sched, corrupted, lost;
+  uint32_t terr;  // a departure time left the record format (kErrTimeOverflow, as perr for e)
   uint64_t bytes;
 #ifdef TGSIM_PROFILE
   uint64_t pf[kProfSlots];
@@ -517,9 +518,17 @@ struct SimQueue {
   // Commits the HTB service of the first n queue items (lanes < n): slot -> ring entry, record.
   // An item whose destination went away while it was queued (kDeadDst, k_purge) still takes its
   // HTB turn and its place in the ring (it leaves the sender) but emits no record.
+  // A departure past the time field (a backlog on a slow link: e fits, d does not).  kOver: clamped
+  // here like an eligibility time, since above kEMask a record's t_ns holds its destination slot
+  // (slot_bits).  The dense windows' records hold nothing but the time there: commit_plain keeps d and
+  // only notes what lies above the field.
   __device__ __forceinline__ void commit(bool c, uint32_t n, const uint4& qi, uint64_t d, uint64_t tat_after) {
-    if constexpr (kOver) commit_over(c, n, qi, d, tat_after);
-    else commit_plain(c, n, qi, d, tat_after);
+    if constexpr (kOver) {
+      if (c && d > kEMask) { terr = 1; d = kEMask; }
+      commit_over(c, n, qi, d, tat_after);
+    } else {
+      commit_plain(c, n, qi, d, tat_after);
+    }
   }
   // records past the region with no pool space are dropped (kErrEmitPool)
   // (as emit_record: the destination slot first, then the bucket or the emit records)
@@ -564,6 +573,7 @@ struct SimQueue {
     const bool live = c && qi.w != kDeadDst;
     const uint64_t lm = __ballot(live);
     if (c) {
+      terr |= (uint32_t)(d >> kSlotShift);  // nonzero: d is past the time field
       *reinterpret_cast<uint2*>(&slot(rn + lane)) = make_uint2((uint32_t)d, (uint32_t)(d >> 32));
       if (live) {
         const uint32_t len = qi.y >> 14 & 0xFFFFu, flags = qi.y >> 30;
@@ -1092,7 +1102,7 @@ __device__ __forceinline__ uint32_t sim_source(const SimArgs& a, const uint32_t 
   Q.bkt = kList ? a.dst_bkt : nullptr;
   Q.bkt_log = a.bkt_log;
   Q.rf = kRecv ? recv_fold(a) : RecvFold{};
-  Q.sched = Q.corrupted = Q.lost = 0;
+  Q.sched = Q.corrupted = Q.lost = Q.terr = 0;
   Q.bytes = 0;
 #ifdef TGSIM_PROFILE
   for (int k = 0; k < (int)kProfSlots; ++k) Q.pf[k] = 0;
@@ -1799,7 +1809,7 @@ __device__ __forceinline__ uint32_t sim_source(const SimArgs& a, const uint32_t 
   const uint32_t lost = readlane32((uint32_t)scan_sum_i32((int32_t)Q.lost), kWave - 1);
   const uint64_t bytes = wave_sum(Q.bytes);
   const uint64_t qbytes = 16ull * (Q.qn + Q.pn + Q.fn + pk_end) + 8ull * Q.rn;
-  const bool err = __ballot(perr != 0) != 0;
+  const bool err = __ballot((perr | Q.terr) != 0) != 0;
   const uint32_t c_clone = readlane32((uint32_t)scan_sum_i32((int32_t)n_clone), kWave - 1);
   flush_verdicts();
   if (lane == 0) {
@@ -2063,9 +2073,10 @@ struct Served {
   uint32_t sched, cor, lost;  // records written, the corrupted among them, items to dead destinations
   uint32_t sk0;        // the served entries released with the old ring (a prefix)
   bool releasing;      // ... which may still grow: every one so far departed before the last enqueue
+  uint32_t terr;       // per lane: a departure time left the record format (kErrTimeOverflow)
 };
 __device__ __forceinline__ Served serve_begin(const SrcState& st, const OldRing& ring, uint64_t T_enq) {
-  return {st.tat, 0, 0, 0, 0, 0, 0, T_enq && !ring.stop};
+  return {st.tat, 0, 0, 0, 0, 0, 0, T_enq && !ring.stop, 0};
 }
 // One round: lanes [0, ns) hold the served items base .. base + ns - 1 in key order (x).  HTB as one
 // max-plus scan (d = max(e, TAT before), TAT' = max(TAT, e - burst) + cost), then the records (dead
@@ -2092,7 +2103,8 @@ __device__ __forceinline__ void serve_round(const SimArgs& a, const SrcParams& p
   const uint64_t ta = sv.tat + A;
   const uint64_t tat_after = ta > Bm ? ta : Bm;
   const uint64_t before = shr1_u64(tat_after, sv.tat);
-  const uint64_t d = e > before ? e : before;
+  uint64_t d = e > before ? e : before;
+  if (hs && d > kEMask) { sv.terr = 1; d = kEMask; }  // as an eligibility time: t_ns above kEMask holds the slot
   if (ns) sv.tat = readlane64(tat_after, ns - 1);
   if constexpr (kStamp) stamp(a, s, lane, 3, __builtin_amdgcn_s_memrealtime());
   bool live = hs && x.w != kDeadDst;
@@ -2150,7 +2162,7 @@ __device__ __forceinline__ void finish_source(const SimArgs& a, uint32_t s, cons
     a.emit_n[s] = sv.emitted;
   }
   const uint64_t t_bytes = wave_sum(sv.bytes);
-  const bool err = __ballot(perr != 0) != 0;
+  const bool err = __ballot((perr | sv.terr) != 0) != 0;
   if (lane < 8 && vcnt) atomicAdd(&sc[kStVerdict0 + lane], (unsigned long long)vcnt);
   if (lane == 0) {
     const uint64_t qb = 16ull * q_len(st) + 8ull * r_len(st) + 16ull * wpos + 8ull * rn_new;

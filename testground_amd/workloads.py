@@ -13,12 +13,14 @@ A reaction to a delivery at time d (reply, echo, forward) is offered at tick flo
 """
 from __future__ import annotations
 
+import errno
 import ipaddress
 from typing import Dict, List, Tuple
 
 import numpy as np
 
 from . import abi
+from .engine import EngineError
 from .network import Config, FilterAction, LinkRule, LinkShape, Millisecond, RoutingPolicyType, configs_array
 
 SEED = 0x7E576A0D00000001
@@ -256,6 +258,8 @@ class PingModel:
     def window_packets(self, window: int) -> np.ndarray:
         """The window's offered packets in (src, tick, seq, dst) order; the due entries leave the calendar."""
         p, win0, win1 = self.ping, self.now, self.now + window
+        if win1 >= 1 << 31:  # the engine's -EOVERFLOW: ticks of the schedule and the calendar stay below 2^31
+            raise EngineError(-errno.EOVERFLOW, "ping: the window ends beyond tick 2^31")
         j = np.arange(ping_probes_before(p, win0), ping_probes_before(p, win1), dtype=np.int64)
         src = np.tile(self.src, len(j))
         dst = np.tile(self.dst, len(j))
@@ -470,6 +474,8 @@ class FlowModel:
         """The window's offered packets in (src, tick, seq, dst) order: the segments due in it, and the
         calendar's ACKs due in it, which leave the calendar."""
         p, win0, win1 = self.flow, self.now, self.now + window
+        if win1 >= 1 << 31:  # the engine's -EOVERFLOW: ticks of the timers and the calendar stay below 2^31
+            raise EngineError(-errno.EOVERFLOW, "flow: the window ends beyond tick 2^31")
         name, longest = self._window_limit()
         if window > longest:
             raise ValueError(f"flow: a window of {window} ticks is longer than {name} {longest}")
@@ -646,6 +652,8 @@ class FlowCCModel(FlowModel):
 
     def window_packets(self, window: int) -> np.ndarray:
         p, win0, win1 = self.flow, self.now, self.now + window
+        if win1 >= 1 << 31:  # the engine's -EOVERFLOW: ticks of the timers and the calendar stay below 2^31
+            raise EngineError(-errno.EOVERFLOW, "flow: the window ends beyond tick 2^31")
         name, longest = self._window_limit()
         if window > longest:
             raise ValueError(f"flow: a window of {window} ticks is longer than {name} {longest}")
