@@ -527,7 +527,8 @@ int64_t tgsim_ping_pairs(void* engine, uint32_t peer, uint32_t n, tgsim_ping_pai
  *            generated, no flow state changes, and the error stays until the next tgsim_flow_init;
  *            the reports stay readable.
  *   Verdicts the sender learns nothing from them: a filtered, lost or queue-full segment is recovered
- *            by its timer only.
+ *            by its timer only (unless armed with tgsim_flow_init_fb, further down: the verdict
+ *            feedback counts them per flow and can fail a flow on a refusal).
  * Single engine only (it must own every peer), as for ping. */
 #define TGSIM_FLOW_SLOTS 16u
 enum tgsim_flow_state { TGSIM_FLOW_ACTIVE = 0, TGSIM_FLOW_DONE = 1, TGSIM_FLOW_FAILED = 2 };
@@ -623,9 +624,9 @@ int64_t tgsim_flow_rows(void* engine, uint64_t first, uint64_t n, tgsim_flow_row
  *             loss_events += 1.  A late window still changes no state, the cc rows included.  A
  *             FAST segment is due like any other: with max_attempts == 1 it fails the flow at its tick.
  *   Step      as above, the counters and the windows depend on the step length, the fail tick does not.
- *   Not here  cumulative or delayed ACKs, pacing, and failing at once on a BLACKHOLE or PROHIBIT
- *             verdict (still the follow-up DESIGN.md §5.8 names); an RTT estimator and timer backoff
- *             are opt-in further down (tgsim_flow_init_rto). */
+ *   Not here  cumulative or delayed ACKs and pacing; an RTT estimator and timer backoff
+ *             (tgsim_flow_init_rto) and failing at once on a refusal verdict (tgsim_flow_init_fb)
+ *             are opt-in further down. */
 typedef struct {
     uint32_t init_cwnd;     /* 1..window: segments released at start_tick                  */
     uint32_t init_ssthresh; /* 0 -> window; else 2..window                                  */
@@ -688,8 +689,8 @@ int     tgsim_flow_cc_report(void* engine, tgsim_flow_cc_summary* out);
  *             per window.
  *   Late      a late window changes no state, the rto rows and `sent` included.
  *   Step      as above, the counters and the samples depend on the step length, the fail tick does not.
- *   Not here  cumulative or delayed ACKs, pacing, and failing at once on a BLACKHOLE or PROHIBIT
- *             verdict (still the follow-up DESIGN.md §5.8 names). */
+ *   Not here  cumulative or delayed ACKs and pacing; failing at once on a refusal verdict is opt-in
+ *             further down (tgsim_flow_init_fb). */
 typedef struct {
     uint32_t min_rto_ticks; /* >= 1; also the longest window tgsim_gen_flow accepts while armed */
     uint32_t max_rto_ticks; /* min_rto_ticks .. 2^27                                            */
@@ -720,6 +721,70 @@ int tgsim_flow_init_rto(void* engine, const tgsim_flow* p, const tgsim_flow_cc* 
  * synchronize, and fail, like tgsim_flow_cc_rows and tgsim_flow_cc_report. */
 int64_t tgsim_flow_rto_rows(void* engine, uint64_t first, uint64_t n, tgsim_flow_rto_row* out, size_t cap);
 int     tgsim_flow_rto_report(void* engine, tgsim_flow_rto_summary* out);
+
+/* ---- verdict feedback of the flow driver (opt-in per arming) ---------------- */
+/* What became of a flow's offers, and a sender that learns of a refusal as a real one does (EINVAL
+ * or EACCES on the first write, see TGSIM_V_BLACKHOLE and TGSIM_V_PROHIBIT): per-flow verdict
+ * counters folded on the device after each window's simulation, and a mask of refusal verdicts that
+ * fail a flow at the tick of the refused offer.  Armed with tgsim_flow_init_fb and a non-NULL fb,
+ * with or without cc and rto (the three are independent); without it every rule above holds as
+ * written.  With it, everything above that is not named here stays as written.
+ *
+ *   State     per flow, the 32-B tgsim_flow_fb_row, all zero at arming.
+ *   Fold      after the window [T, T + n) has been simulated, every data packet the driver offered in
+ *             it (seq bit 31 clear) is attributed to its flow (its source, slot bits 23..26), and the
+ *             low nibble v of its verdict byte is counted: 0 -> scheduled, 5 -> lost, 6 -> queue_full,
+ *             1..4 -> refused; a high nibble other than TGSIM_V_NONE adds one to cloned.  Every flow
+ *             is counted, whatever its state: after every step scheduled + lost + queue_full + refused
+ *             == the flow row's offered.  ACK packets are attributed to no flow: their verdicts are
+ *             tgsim_stats_t.by_verdict less these sums.
+ *   Fail      the offer tick of a packet is T + its tick.  Let R be the flow's refused offers of this
+ *             window whose verdict v has bit 1 << v set in fail_mask.  When R is not empty and the flow
+ *             is ACTIVE, or was failed by this very window's generation (FAILED, fail_verdict == 0,
+ *             done_ns >= T * tick_ns: the timer rule stopped its offers at a later tick of the same
+ *             window), then with F the earliest offer tick in R: state = FAILED, done_ns = F *
+ *             tick_ns, and fail_verdict, fail_seg and fail_attempt come from the offer of R at tick F
+ *             with the lowest seq.  Offers of the flow later in that window were already made and stay
+ *             counted in offered; their ACKs are stale.  FAILED is final.  A refused ACK fails
+ *             nothing: the receiver stays stateless and the sender's timer handles it as before.
+ *   Order     a window's verdicts take effect before the records the same step emits are folded: an
+ *             ACK delivered in the step that failed its flow is stale.  The cc and rto rows of a flow
+ *             failed by verdict stay as they were.
+ *   Late      a late window is never simulated, so it changes no fb row.
+ *   Step      the fail tick is by tick, like the timer's, and does not depend on the step length; the
+ *             counters do.
+ *   Not here  reacting to a local QUEUE_FULL as a congestion signal (it is counted only). */
+/* bits a fail_mask may carry: 1<<TGSIM_V_DISCONNECTED | 1<<TGSIM_V_NO_ROUTE | 1<<TGSIM_V_BLACKHOLE | 1<<TGSIM_V_PROHIBIT */
+#define TGSIM_FLOW_FB_REFUSALS 0x1Eu
+typedef struct {
+    uint32_t fail_mask;     /* bit 1 << v: a data offer refused with verdict v fails its flow; 0: count only */
+    uint32_t _pad[3];
+} tgsim_flow_fb;            /* 16 B */
+typedef struct {            /* one flow; 32 B */
+    uint32_t scheduled, lost, queue_full, refused; /* the flow's data offers by verdict, low nibble 0 / 5 / 6 / 1..4 */
+    uint32_t cloned;        /* data offers whose high nibble is not TGSIM_V_NONE                         */
+    uint32_t fail_verdict;  /* 0: not failed, or failed by its timer; else the refusing verdict 1..4      */
+    uint32_t fail_seg, fail_attempt; /* segment and attempt field of the refused offer; 0 when fail_verdict == 0 */
+} tgsim_flow_fb_row;
+typedef struct {            /* 96 B */
+    uint64_t scheduled, lost, queue_full, refused, cloned;
+    uint64_t refused_flows; /* flows with refused > 0                                   */
+    uint64_t failed_timer;  /* FAILED with fail_verdict == 0                            */
+    uint64_t failed_by[4];  /* FAILED with fail_verdict == 1 + index                    */
+    uint64_t _pad;
+} tgsim_flow_fb_summary;
+/* tgsim_flow_init_rto with the verdict feedback: every arming, busy and disarm rule of tgsim_flow_init
+ * holds, fb == NULL is tgsim_flow_init_rto itself, cc and rto may each be NULL or not, and a fail_mask
+ * with a bit outside TGSIM_FLOW_FB_REFUSALS is -EINVAL with a tgsim_last_error text that names
+ * fail_mask and its value in hex.  fail_mask == 0 is legal: the flows are counted and never failed by
+ * a verdict. */
+int tgsim_flow_init_fb(void* engine, const tgsim_flow* p, const tgsim_flow_cc* cc, const tgsim_flow_rto* rto,
+                       const tgsim_flow_fb* fb, const tgsim_flow_spec* flows, uint64_t n_flows);
+/* The fb rows of flows [first, first + n), and the fb summary reduced on the device.  -EINVAL
+ * ("verdict feedback is not armed") when flows are armed without fb or not at all; otherwise they
+ * synchronize, and fail, like tgsim_flow_rto_rows and tgsim_flow_rto_report. */
+int64_t tgsim_flow_fb_rows(void* engine, uint64_t first, uint64_t n, tgsim_flow_fb_row* out, size_t cap);
+int     tgsim_flow_fb_report(void* engine, tgsim_flow_fb_summary* out);
 
 /* ---- per-group traffic matrix (who offered what to whom, and what became of it) -------------- */
 /* Every peer belongs to one group (a region, a composition group); the engine folds each window's

@@ -12,12 +12,19 @@
   curve  goodput per flow against link loss, with and without congestion control (the README's table)
   hetero 10,000 peers with latencies U[1,100] ms: a fixed timer of 60 ms, one above the largest round
          trip, and the RTT estimator from that same timer (the README's table)
+  partition  the curve's 10,000 peers, links and flows with congestion control; at tick 100,000 every
+         peer of region A (16.0.0.0/19: peers 0..8,189) gets a Drop rule for region B's prefix
+         (16.0.32.0/19: the other 1,810).  Once with the verdict feedback failing flows on a refusal,
+         once with fail_mask 0 (counted only: the timers fail them): flows failed and by what, the mean
+         and largest fail tick - partition tick, the data packets offered after the partition
+         (the README's table)
 
 `--cc` arms run, steady and trace with congestion control (init_cwnd 2, dupthresh 3,
 the cap `window` as without) and `--loss PCT` puts that loss on every link; with either the run takes
 CC_WINDOWS windows, since the windows open from 2 segments and lost ones wait for a timer.  `--rto`
 arms them with the RTT estimator as well (from the timer of 20 ms, a floor of one
-window, backoff on), with or without `--cc`.
+window, backoff on), with or without `--cc`.  `--fb` arms them with the verdict feedback (DESIGN.md
+§5.11, fail_mask = every refusal): nothing is refused in this workload, so it times the fold alone.
 
 Every link 5 ms, lossless, unlimited, reorder off; 800,000 flows of 64 segments of 1,000 bytes, window
 8, ACKs of 64 bytes, a timer of 20 ms that never fires; windows of 5,000 ticks.  Every flow starts at
@@ -53,6 +60,8 @@ OFFSETS = np.array([1, 17, 263, 4099, 9973, 31337, 54321, 77777])
 RTO = dict(min_rto_ticks=WIN, max_rto_ticks=2_000_000, backoff=1)
 # hetero: per-peer latency U[1,100] ms (round trips of 2 to 200 ms), jitter U[0.1,0.5] ms on every peer, 1 %
 # loss; the minimum netem delay is 0.5 ms, which is the lookahead and the window.  Unlimited links.
+FB = dict(fail_mask=abi.FLOW_FB_REFUSALS)
+PARTITION = dict(at_window=20, prefix_b=("16.0.32.0", 19), first_b=(1 << 13) - 2, max_windows=1200)
 HETERO = dict(n=10_000, win=500, lookahead_ns=nw.Millisecond // 2, loss=1.0, above_ticks=210_000, max_windows=16_000,
               bin_ns=20 * nw.Millisecond, n_bins=256, seed=11)
 
@@ -70,9 +79,9 @@ def engine(flags, loss=0.0, n=N, rate_bps=0):
     return eng
 
 
-def device_loop(windows=WINDOWS, cc=None, loss=0.0, rto=None):
+def device_loop(windows=WINDOWS, cc=None, loss=0.0, rto=None, fb=None):
     eng, t = engine(abi.OPT_DISCARD_DELIVERIES, loss), []
-    eng.flow_init(flow_table(), cc=cc, rto=rto, **FLOW)
+    eng.flow_init(flow_table(), cc=cc, rto=rto, fb=fb, **FLOW)
     for w in range(windows):
         eng.sync()
         t0 = time.perf_counter()
@@ -85,6 +94,8 @@ def device_loop(windows=WINDOWS, cc=None, loss=0.0, rto=None):
         rep["cc"] = eng.flow_cc_report()
     if rto is not None:
         rep["rto"] = eng.flow_rto_report()
+    if fb is not None:
+        rep["fb"] = eng.flow_fb_report()
     return rep, t
 
 
@@ -148,6 +159,43 @@ def curve_point(loss, cc):
     return out
 
 
+def partition_point(fail_mask):
+    """One run of the partition to the end (or max_windows)."""
+    n, p = CURVE["n"], PARTITION
+    eng = engine(abi.OPT_DISCARD_DELIVERIES, 0.0, n, CURVE["rate_bps"])
+    eng.flow_init(flow_table(n), cc=CC, fb=dict(fail_mask=fail_mask),
+                  **dict(FLOW, rto_ticks=CURVE["rto_ticks"], max_attempts=16, n_bins=0, bin_ns=0))
+    wl.flow_run(eng, p["at_window"], WIN)
+    before, cut_tick = eng.flow_report(), eng.stats()["now_tick"]
+    shape = nw.LinkShape(Latency=LAT, Bandwidth=CURVE["rate_bps"])
+    for i in range(p["first_b"]):  # region A: every peer below 16.0.32.0
+        eng.configure(i, nw.Config(Network="default", Enable=True, Default=shape,
+                                   Rules=[nw.LinkRule(Subnet=p["prefix_b"], LinkShape=nw.LinkShape(Filter=nw.FilterAction.Drop))]))
+    windows, t0 = p["at_window"], time.perf_counter()
+    while windows < p["max_windows"]:
+        wl.flow_run(eng, 40, WIN)
+        windows += 40
+        if eng.flow_report()["active"] == 0:
+            break
+    eng.sync()
+    wall = time.perf_counter() - t0
+    rows, frows, rep, frep = eng.flow_rows(), eng.flow_fb_rows(), eng.flow_report(), eng.flow_fb_report()
+    failed = rows["state"] == abi.FLOW_FAILED
+    after = rows["done_ns"].astype(np.int64) // eng.tick_ns - cut_tick
+    by = {"verdict": after[failed & (frows["fail_verdict"] > 0)], "timer": after[failed & (frows["fail_verdict"] == 0)]}
+    t = flow_table(n)
+    return {"fail_mask": fail_mask, "peers": n, "flows": len(t), "partition_tick": int(cut_tick),
+            "flows_a_to_b": int(((t["src"] < p["first_b"]) & (t["dst"] >= p["first_b"])).sum()),
+            "flows_b_to_a": int(((t["src"] >= p["first_b"]) & (t["dst"] < p["first_b"])).sum()),
+            "windows": windows, "wall_s_after_partition": round(wall, 2), "done": rep["done"], "failed": rep["failed"],
+            "active": rep["active"], "failed_by_verdict": int((failed & (frows["fail_verdict"] > 0)).sum()),
+            "failed_by_timer": frep["failed_timer"],
+            **{f"fail_after_partition_ticks_{stat}_by_{k}": (None if not len(v) else round(float(v.mean()), 1) if stat == "mean"
+                                                             else int(v.max())) for k, v in by.items() for stat in ("mean", "max")},
+            "data_offered_after_partition": rep["data_offered"] - before["data_offered"],
+            "refused": frep["refused"], "retransmits": rep["retransmits"], "fb": frep}
+
+
 def host_loop(windows=HOST_WINDOWS):
     eng, t = engine(0), []
     m = wl.FlowModel(eng, FLOW, flow_table())
@@ -162,13 +210,14 @@ def main():
     mode = sys.argv[1]
     cc = CC if "--cc" in sys.argv else None
     rto = RTO if "--rto" in sys.argv else None
+    fb = FB if "--fb" in sys.argv else None
     loss = float(sys.argv[sys.argv.index("--loss") + 1]) if "--loss" in sys.argv else 0.0
     windows, steady = (CC_WINDOWS, CC_STEADY) if cc is not None or loss else (WINDOWS, STEADY)
     if mode == "run":
-        print(json.dumps({k: v for k, v in device_loop(windows, cc, loss, rto)[0].items() if k != "hist"}))
+        print(json.dumps({k: v for k, v in device_loop(windows, cc, loss, rto, fb)[0].items() if k != "hist"}))
     elif mode == "steady":
-        rep, td = device_loop(windows, cc, loss, rto)
-        print(json.dumps({"cc": cc, "rto": rto, "loss_pct": loss, "windows": windows, "steady": [steady[0], steady[-1]],
+        rep, td = device_loop(windows, cc, loss, rto, fb)
+        print(json.dumps({"cc": cc, "rto": rto, "fb": fb, "loss_pct": loss, "windows": windows, "steady": [steady[0], steady[-1]],
                           "report": {k: v for k, v in rep.items() if k != "hist"},
                           "device_ms_per_window": [round(1e3 * x, 3) for x in td],
                           "device_steady_ms": round(1e3 * statistics.median(td[w] for w in steady), 3),
@@ -178,6 +227,9 @@ def main():
         for loss_pct in CURVE["losses"]:
             for c in (None, CC):
                 print(json.dumps(curve_point(loss_pct, c)), flush=True)
+    elif mode == "partition":
+        for mask in (FB["fail_mask"], 0):
+            print(json.dumps(partition_point(mask)), flush=True)
     elif mode == "hetero":
         h = HETERO
         for row in (("fixed 60 ms", 60_000, None), ("fixed above the largest round trip", h["above_ticks"], None),
@@ -213,6 +265,8 @@ def main():
                   "k_flow_recv_ack": seg * 24 + flows * (16 + 2 * (32 + ccb + rtb) + 2 * 8) + seg * (5 + snt),
                   # (rto: the row's timer read, a `sent` tick written per first offer)
                   "k_flow_count": state, "k_flow_write": state + seg * 16 + seg * (5 + snt) + flows * (32 + ccb + rtb),
+                  # (fb: the window's packets and verdict bytes, and in a window of segments the fb row in and out)
+                  "k_flow_fb": seg * 17 + flows * 2 * 32,
                   "k_flow_rto_report": flows * 32,
                   "k_flow_cc_report": flows * (32 + 32),  # the cc row, and the flow row for its state
                   "k_ping_count_cal": seg * 16, "k_ping_write_cal": seg * 16 + seg * 16, "k_ping_order": seg * 16 * 2}

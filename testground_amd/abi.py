@@ -187,6 +187,25 @@ class FlowRtoSummary(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in FLOW_RTO_SUMMARY_FIELDS]
 
 
+# Verdict feedback of the flow driver (tgsim_flow_init_fb): the refusal verdicts a fail_mask may name.
+FLOW_FB_REFUSALS = 0x1E
+
+
+class FlowFb(C.Structure):
+    _fields_ = [("fail_mask", C.c_uint32), ("_pad", C.c_uint32 * 3)]
+
+
+FLOW_FB_ROW_DTYPE = np.dtype([("scheduled", "<u4"), ("lost", "<u4"), ("queue_full", "<u4"), ("refused", "<u4"),
+                              ("cloned", "<u4"), ("fail_verdict", "<u4"), ("fail_seg", "<u4"), ("fail_attempt", "<u4")])
+# (the last four are tgsim_flow_fb_summary.failed_by[0..3]: FAILED by verdict 1..4)
+FLOW_FB_SUMMARY_FIELDS = ("scheduled", "lost", "queue_full", "refused", "cloned", "refused_flows", "failed_timer",
+                          "failed_disconnected", "failed_no_route", "failed_blackhole", "failed_prohibit")
+
+
+class FlowFbSummary(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in FLOW_FB_SUMMARY_FIELDS + ("_pad",)]
+
+
 # Per-group traffic matrix (tgsim_groups_init / tgsim_group_matrix): the words of a cell.
 GROUP_MAX = 64
 GROUP_WORDS = 14
@@ -221,6 +240,7 @@ assert C.sizeof(Flow) == 32 and FLOW_SPEC_DTYPE.itemsize == 16 and FLOW_ROW_DTYP
 assert C.sizeof(FlowSummary) == 120
 assert C.sizeof(FlowCC) == 16 and FLOW_CC_ROW_DTYPE.itemsize == 32 and C.sizeof(FlowCCSummary) == 64
 assert C.sizeof(FlowRto) == 16 and FLOW_RTO_ROW_DTYPE.itemsize == 32 and C.sizeof(FlowRtoSummary) == 64
+assert C.sizeof(FlowFb) == 16 and FLOW_FB_ROW_DTYPE.itemsize == 32 and C.sizeof(FlowFbSummary) == 96
 assert C.sizeof(CommInfo) == 72 and C.sizeof(Gossip) == 24 and C.sizeof(Opts) == 56 and C.sizeof(Shape) == 56 and C.sizeof(Config) == 104
 
 # Every symbol include/tgsim.h declares (checked by tests/test_abi.py).
@@ -240,6 +260,7 @@ EXPORTS = [
     "tgsim_flow_init", "tgsim_gen_flow", "tgsim_flow_report", "tgsim_flow_rows",
     "tgsim_flow_init_cc", "tgsim_flow_cc_rows", "tgsim_flow_cc_report",
     "tgsim_flow_init_rto", "tgsim_flow_rto_rows", "tgsim_flow_rto_report",
+    "tgsim_flow_init_fb", "tgsim_flow_fb_rows", "tgsim_flow_fb_report",
     "tgsim_groups_init", "tgsim_group_matrix",
     "tgsim_comm_id", "tgsim_comm_init", "tgsim_comm_step", "tgsim_comm_launch", "tgsim_comm_finish", "tgsim_comm_run", "tgsim_comm_barrier", "tgsim_comm_info",
     "tgsim_bridge_create", "tgsim_bridge_destroy", "tgsim_bridge_send", "tgsim_bridge_step",
@@ -325,6 +346,10 @@ def declare(lib: C.CDLL, prefix: str) -> None:
     f("flow_init_rto", C.c_int, vp, C.POINTER(Flow), C.POINTER(FlowCC), C.POINTER(FlowRto), C.c_void_p, C.c_uint64)
     f("flow_rto_rows", C.c_int64, vp, C.c_uint64, C.c_uint64, C.c_void_p, C.c_size_t)
     f("flow_rto_report", C.c_int, vp, C.POINTER(FlowRtoSummary))
+    f("flow_init_fb", C.c_int, vp, C.POINTER(Flow), C.POINTER(FlowCC), C.POINTER(FlowRto), C.POINTER(FlowFb), C.c_void_p,
+      C.c_uint64)
+    f("flow_fb_rows", C.c_int64, vp, C.c_uint64, C.c_uint64, C.c_void_p, C.c_size_t)
+    f("flow_fb_report", C.c_int, vp, C.POINTER(FlowFbSummary))
     f("groups_init", C.c_int, vp, C.c_void_p, C.c_uint32)
     f("group_matrix", C.c_int64, vp, C.c_void_p, C.c_size_t, C.c_int)
     f("offered", C.c_int64, vp, C.c_void_p, C.c_size_t)

@@ -487,6 +487,10 @@ struct tgsim_engine_s {
   bool flow_rto_on = false;      // armed by tgsim_flow_init_rto with an rto
   tgsim_flow_rto flow_rto{};
   DevBuf<tgsim_flow_rto_row> d_frt;
+  bool flow_fb_on = false;       // armed by tgsim_flow_init_fb with an fb
+  tgsim_flow_fb flow_fb{};
+  DevBuf<tgsim_flow_fb_row> d_ffb;
+  hipEvent_t ev_fb = nullptr;    // after the last k_flow_fb (simulate stream): flow_recv waits for it
   DevBuf<uint32_t> d_fsent;
   hipEvent_t ev_flow = nullptr;  // after the last k_flow_recv_ack (delivery stream)
 
@@ -1177,6 +1181,8 @@ void groups_release(Eng* E) {
   E->n_groups = 0;
 }
 
+FlowArgs flow_args(Eng* E, uint64_t win0, uint32_t n_ticks);  // (with the flow driver, further down)
+
 int run_sim(Eng* E, uint32_t n_ticks, bool local_hist = false) {
   int erc = check_sim_error(E);
   if (erc) return erc;
@@ -1329,6 +1335,15 @@ int run_sim(Eng* E, uint32_t n_ticks, bool local_hist = false) {
     }
     launch_group_src(group_args(E), E->d_off.p, E->d_in.p, E->d_verdict.p, E->S, E->n_in, E->st);
     HIPCHK(hipGetLastError());
+  }
+  if (E->flow_fb_on) {  // the flows' verdict feedback, from the step's input and verdict bytes like the fold above
+    if (!E->ev_sim_t) {  // the delivery's sort waits for k_sim; only its flow receipts wait for this fold (ev_fb)
+      HIPCHK(hipEventRecord(E->ev_sim, E->st));
+      E->ev_sim_t = E->ev_sim;
+    }
+    launch_flow_fb(flow_args(E, E->now_tick, n_ticks), E->d_off.p, E->d_in.p, E->d_verdict.p, E->n_in, E->st);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(E->ev_fb, E->st));
   }
   // (no heavy-first order kernel behind a single window: on the simulate stream it delayed the next
   // window by its launch and ~9 us, more than the order saved -- sub-capacity storm 1.38 against
@@ -1534,6 +1549,8 @@ void flow_release(Eng* E) {
   ping_release(E);
   E->d_fspec.release(); E->d_frow.release(); E->d_fbits.release(); E->d_fdue.release(); E->d_ffirst.release();
   E->d_fcnt.release(); E->d_fatt.release(); E->d_fcc.release(); E->d_frt.release(); E->d_fsent.release();
+  E->d_ffb.release();
+  E->flow_fb_on = false;
   E->flow_on = false;
   E->flow_cc_on = false;
   E->flow_rto_on = false;
@@ -1577,12 +1594,16 @@ FlowArgs flow_args(Eng* E, uint64_t win0, uint32_t n_ticks) {
   f.min_rto = E->flow_rto.min_rto_ticks;
   f.max_rto = E->flow_rto.max_rto_ticks;
   f.backoff = E->flow_rto.backoff;
+  f.fb = E->flow_fb_on ? E->d_ffb.p : nullptr;
+  f.fail_mask = E->flow_fb.fail_mask;
   return f;
 }
 
 // The flow receipts of one window's delivery-ordered records, where ping_recv would run; the next
 // generation waits for ev_flow.
 int flow_recv(Eng* E, const tgsim_delivery* recs, const uint64_t* off, uint32_t nd, uint64_t n, hipStream_t sq) {
+  // the window's verdict feedback writes the same rows on the simulate stream, and takes effect first
+  if (E->flow_fb_on) HIPCHK(hipStreamWaitEvent(sq, E->ev_fb, 0));
   launch_flow_recv(flow_args(E, 0, 0), recs, off, nd, n, sq);
   HIPCHK(hipGetLastError());
   HIPCHK(hipEventRecord(E->ev_flow, sq));
@@ -2367,6 +2388,7 @@ void tgsim_destroy(void* e) {
   if (E->h_ppub) (void)hipHostFree(E->h_ppub);
   if (E->ev_ping) (void)hipEventDestroy(E->ev_ping);
   if (E->ev_flow) (void)hipEventDestroy(E->ev_flow);
+  if (E->ev_fb) (void)hipEventDestroy(E->ev_fb);
   if (E->h_gerr) (void)hipHostFree(E->h_gerr);
   if (E->h_pub) (void)hipHostFree(E->h_pub);
   if (E->ev_gpub) (void)hipEventDestroy(E->ev_gpub);
@@ -2929,6 +2951,11 @@ int tgsim_flow_init_cc(void* e, const tgsim_flow* p, const tgsim_flow_cc* cc, co
 
 int tgsim_flow_init_rto(void* e, const tgsim_flow* p, const tgsim_flow_cc* cc, const tgsim_flow_rto* rto,
                         const tgsim_flow_spec* flows, uint64_t n_flows) {
+  return tgsim_flow_init_fb(e, p, cc, rto, nullptr, flows, n_flows);
+}
+
+int tgsim_flow_init_fb(void* e, const tgsim_flow* p, const tgsim_flow_cc* cc, const tgsim_flow_rto* rto,
+                       const tgsim_flow_fb* fb, const tgsim_flow_spec* flows, uint64_t n_flows) {
   Eng* E = as_eng(e);
   if (!E) return -EINVAL;
   HIPCHK(hipSetDevice(E->dev));
@@ -2966,6 +2993,8 @@ int tgsim_flow_init_rto(void* e, const tgsim_flow* p, const tgsim_flow_cc* cc, c
       return E->fail(-EINVAL, "flow: rto_ticks %u outside min_rto_ticks..max_rto_ticks (%u..%u): it is the initial timer",
                      p->rto_ticks, rto->min_rto_ticks, rto->max_rto_ticks);
   }
+  if (fb && (fb->fail_mask & ~TGSIM_FLOW_FB_REFUSALS))
+    return E->fail(-EINVAL, "flow: fail_mask 0x%x has bits outside the refusal verdicts (0x%x)", fb->fail_mask, TGSIM_FLOW_FB_REFUSALS);
   if (n_flows > static_cast<uint64_t>(E->N) * TGSIM_FLOW_SLOTS)
     return E->fail(-EINVAL, "flow: %llu flows for %u peers (at most %u per source)", static_cast<unsigned long long>(n_flows), E->N,
                    TGSIM_FLOW_SLOTS);
@@ -2998,6 +3027,7 @@ int tgsim_flow_init_rto(void* e, const tgsim_flow* p, const tgsim_flow_cc* cc, c
   int rc = sync_stream(E);  // a re-init: the last delivery's receipts may still run
   if (rc) return rc;
   if (!E->ev_flow) HIPCHK(hipEventCreateWithFlags(&E->ev_flow, hipEventDisableTiming));
+  if (fb && !E->ev_fb) HIPCHK(hipEventCreateWithFlags(&E->ev_fb, hipEventDisableTiming));
   if (!E->h_ppub) {
     HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&E->h_ppub), (kPingPubWords + 1) * sizeof(uint64_t),
                          hipHostMallocCoherent | hipHostMallocMapped));
@@ -3016,6 +3046,12 @@ int tgsim_flow_init_rto(void* e, const tgsim_flow* p, const tgsim_flow_cc* cc, c
   if (rto) {
     HIPCHK(E->d_frt.ensure_exact(n_flows));
     HIPCHK(E->d_fsent.ensure_exact(n_flows * p->window));
+  }
+  E->flow_fb_on = fb != nullptr;
+  E->flow_fb = fb ? *fb : tgsim_flow_fb{};
+  if (fb) {
+    HIPCHK(E->d_ffb.ensure_exact(n_flows));
+    HIPCHK(hipEventRecord(E->ev_fb, E->st));  // (flow_recv waits for it even behind a window that offered nothing)
   }
   E->ping_cur = 0;
   E->ping_kept = 0;
@@ -3256,6 +3292,49 @@ int tgsim_flow_rto_report(void* e, tgsim_flow_rto_summary* out) {
   out->rto_sum = res[5];
   out->rto_min = ~res[6];
   out->rto_max = res[7];
+  return 0;
+}
+
+int64_t tgsim_flow_fb_rows(void* e, uint64_t first, uint64_t n, tgsim_flow_fb_row* out, size_t cap) {
+  Eng* E = as_eng(e);
+  if (!E) return -EINVAL;
+  if (!E->flow_on || !E->flow_fb_on) return E->fail(-EINVAL, "flow_fb_rows: verdict feedback is not armed (tgsim_flow_init_fb)");
+  if (first > E->n_flows || n > E->n_flows - first)
+    return E->fail(-EINVAL, "flow_fb_rows: flows [%llu, %llu) outside [0, %llu)", static_cast<unsigned long long>(first),
+                   static_cast<unsigned long long>(first + n), static_cast<unsigned long long>(E->n_flows));
+  if (cap < n) return E->fail(-ENOSPC, "flow_fb_rows: %zu rows for %llu", cap, static_cast<unsigned long long>(n));
+  if (n && !out) return E->fail(-EINVAL, "flow_fb_rows: no output buffer");
+  HIPCHK(hipSetDevice(E->dev));
+  int rc = sync_stream(E);
+  if (rc) return rc;
+  if (!n) return 0;
+  HIPCHK(hipMemcpyAsync(out, E->d_ffb.p + first, sizeof(tgsim_flow_fb_row) * n, hipMemcpyDeviceToHost, E->st));
+  HIPCHK(hipStreamSynchronize(E->st));
+  return static_cast<int64_t>(n);
+}
+
+int tgsim_flow_fb_report(void* e, tgsim_flow_fb_summary* out) {
+  Eng* E = as_eng(e);
+  if (!E) return -EINVAL;
+  if (!E->flow_on || !E->flow_fb_on) return E->fail(-EINVAL, "flow_fb_report: verdict feedback is not armed (tgsim_flow_init_fb)");
+  if (!out) return E->fail(-EINVAL, "flow_fb_report: no summary buffer");
+  HIPCHK(hipSetDevice(E->dev));
+  int rc = sync_stream(E);  // the last window's fold runs on the simulate stream, its receipts on the delivery stream
+  if (rc) return rc;
+  launch_flow_fb_report(flow_args(E, 0, 0), E->d_pres.p, E->st);
+  HIPCHK(hipGetLastError());
+  unsigned long long res[kFlowFbResWords];
+  HIPCHK(hipMemcpyAsync(res, E->d_pres.p, sizeof res, hipMemcpyDeviceToHost, E->st));
+  HIPCHK(hipStreamSynchronize(E->st));
+  *out = tgsim_flow_fb_summary{};
+  out->scheduled = res[0];
+  out->lost = res[1];
+  out->queue_full = res[2];
+  out->refused = res[3];
+  out->cloned = res[4];
+  out->refused_flows = res[5];
+  out->failed_timer = res[6];
+  for (int k = 0; k < 4; ++k) out->failed_by[k] = res[7 + k];
   return 0;
 }
 

@@ -379,9 +379,13 @@ struct FlowArgs {
   tgsim_flow_rto_row* rt;       // [n_flows]
   uint32_t* sent;               // [n_flows][window] ring beside due and att: the tick of attempt 0
   uint32_t min_rto, max_rto;
+  // verdict feedback (tgsim_flow_init_fb); fb == nullptr: armed without it
+  uint32_t fail_mask;           // bit 1 << v: a data offer refused with verdict v fails its flow
+  tgsim_flow_fb_row* fb;        // [n_flows]
 };
 constexpr uint32_t kFlowCcResWords = 7;  // loss_events fast_retransmits timeouts active cwnd_sum cwnd_min cwnd_max
 constexpr uint32_t kFlowRtoResWords = 8;  // samples sampled_flows srtt_sum srtt_min srtt_max rto_sum rto_min rto_max
+constexpr uint32_t kFlowFbResWords = 11;  // scheduled lost queue_full refused cloned refused_flows failed_timer failed_by[4]
 
 // Per-group traffic matrix (tgsim_groups_init / tgsim_group_matrix).
 constexpr uint32_t kGroupWords = TGSIM_GROUP_WORDS, kGroupMax = TGSIM_GROUP_MAX;

@@ -3833,6 +3833,7 @@ __global__ __launch_bounds__(256) void k_flow_init(FlowArgs f) {
       c.next = f.init_cwnd < sp.n_seg ? f.init_cwnd : sp.n_seg;
       f.cc[i] = c;
     }
+    if (f.fb) f.fb[i] = tgsim_flow_fb_row{};
   }
   if (i < kPingReplicas * kPingMaxBins) f.cal.hist[i] = 0ull;
   if (i < kPingCtrWords) f.cal.ctr[i] = i == kPcLate ? ~0ull : 0ull;
@@ -3912,6 +3913,95 @@ __global__ __launch_bounds__(256) void k_flow_rto_report(FlowArgs f, unsigned lo
     if (w == 3 || w == 4 || w == 6 || w == 7) atomicMax(&res[w], acc[w]);
     else atomicAdd(&res[w], acc[w]);
   }
+}
+
+// Verdict feedback (tgsim_flow_init_fb), behind a window's simulate kernel: one lane
+// per flow, as in k_flow_recv_ack, so no atomics on flow state.  The lane walks its source's row of
+// the step's input and the verdict bytes beside it, takes the data packets of its own slot and keeps
+// the counts and the least (tick, seq) of the refusals in fail_mask in registers (the lanes of one
+// source's flows are neighbours and read the same lines).  It stores the fb row, and on a failure the
+// flow row, only when it saw a packet; a flow whose source offered nothing leaves after two off[]
+// loads.  One loop, bounded by the off[] range (never past n_in); no workgroup waits on another.
+__global__ __launch_bounds__(256) void k_flow_fb(FlowArgs f, const uint64_t* __restrict__ off, const InRec* __restrict__ in,
+                                                 const uint8_t* __restrict__ verdict, uint64_t n_in) {
+  const uint64_t fl = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (fl >= f.n_flows) return;
+  const tgsim_flow_spec sp = f.spec[fl];
+  uint64_t b = off[sp.src], e = off[sp.src + 1];
+  e = e < n_in ? e : n_in;  // (never past the buffers the window sized)
+  if (b >= e) return;
+  const uint32_t slot = (uint32_t)(fl - f.first[sp.src]);
+  uint32_t seen = 0, sched = 0, lost = 0, full = 0, refused = 0, cloned = 0, fv = 0;
+  uint64_t key = ~0ull;  // tick << 32 | seq of the earliest refusal that fails the flow
+  for (; b < e; ++b) {
+    const InRec r = in[b];
+    if ((r.seq >> 31) || flow_slot(r.seq) != slot) continue;
+    const uint32_t vb = verdict[b], v = vb & 15u;
+    ++seen;
+    sched += v == TGSIM_V_SCHEDULED;
+    lost += v == TGSIM_V_LOSS;
+    full += v == TGSIM_V_QUEUE_FULL;
+    cloned += (vb >> 4) != TGSIM_V_NONE;
+    if (v >= TGSIM_V_DISCONNECTED && v <= TGSIM_V_PROHIBIT) {
+      ++refused;
+      const uint64_t k = (uint64_t)r.tick << 32 | r.seq;
+      if ((f.fail_mask >> v & 1u) && k < key) {
+        key = k;
+        fv = v;
+      }
+    }
+  }
+  if (!seen) return;
+  tgsim_flow_fb_row q = f.fb[fl];
+  q.scheduled += sched;
+  q.lost += lost;
+  q.queue_full += full;
+  q.refused += refused;
+  q.cloned += cloned;
+  if (fv) {
+    tgsim_flow_row row = f.rows[fl];
+    const uint64_t t0 = f.cal.win0 * f.cal.tick_ns;
+    // ACTIVE, or failed by this window's generation: its timer ran out at a later tick of the window
+    if (row.state == TGSIM_FLOW_ACTIVE || (row.state == TGSIM_FLOW_FAILED && !q.fail_verdict && row.done_ns >= t0)) {
+      row.state = TGSIM_FLOW_FAILED;
+      row.done_ns = (f.cal.win0 + (key >> 32)) * f.cal.tick_ns;
+      f.rows[fl] = row;
+      q.fail_verdict = fv;
+      q.fail_seg = flow_seg((uint32_t)key);
+      q.fail_attempt = (uint32_t)key >> 27 & 15u;
+    }
+  }
+  f.fb[fl] = q;
+}
+
+// tgsim_flow_fb_report, as k_flow_report below: the five counters and the flows with a refusal over
+// every flow, and the FAILED flows by cause (word 6: the timer; words 7..10: verdict 1..4).
+__global__ __launch_bounds__(256) void k_flow_fb_report(FlowArgs f, unsigned long long* res) {
+  __shared__ unsigned long long acc[kFlowFbResWords];
+  if (threadIdx.x < kFlowFbResWords) acc[threadIdx.x] = 0ull;
+  __syncthreads();
+  uint64_t v[kFlowFbResWords] = {};
+  for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < f.n_flows; i += (uint64_t)gridDim.x * 256) {
+    const tgsim_flow_fb_row q = f.fb[i];
+    v[0] += q.scheduled;
+    v[1] += q.lost;
+    v[2] += q.queue_full;
+    v[3] += q.refused;
+    v[4] += q.cloned;
+    v[5] += q.refused > 0;
+    if (f.rows[i].state == TGSIM_FLOW_FAILED) {
+      v[6] += q.fail_verdict == 0;
+#pragma unroll
+      for (uint32_t k = 0; k < 4; ++k) v[7 + k] += q.fail_verdict == 1 + k;
+    }
+  }
+#pragma unroll
+  for (uint32_t w = 0; w < kFlowFbResWords; ++w) {
+    const uint64_t t = wave_sum(v[w]);
+    if ((threadIdx.x & 63u) == 0 && t) atomicAdd(&acc[w], (unsigned long long)t);
+  }
+  __syncthreads();
+  if (threadIdx.x < kFlowFbResWords && acc[threadIdx.x]) atomicAdd(&res[threadIdx.x], acc[threadIdx.x]);
 }
 
 // tgsim_flow_report: one pass over the rows; a workgroup reduces in LDS and ends with one set of
@@ -5319,6 +5409,17 @@ void launch_flow_cc_report(const FlowArgs& f, unsigned long long* res, hipStream
 void launch_flow_rto_report(const FlowArgs& f, unsigned long long* res, hipStream_t st) {
   (void)hipMemsetAsync(res, 0, sizeof(unsigned long long) * kFlowRtoResWords, st);
   hipLaunchKernelGGL(k_flow_rto_report, dim3(std::min(ping_grid(f.n_flows), 256u)), dim3(256), 0, st, f, res);
+}
+
+void launch_flow_fb(const FlowArgs& f, const uint64_t* off, const InRec* in, const uint8_t* verdict, uint64_t n_in,
+                    hipStream_t st) {
+  if (!f.n_flows || !n_in) return;
+  hipLaunchKernelGGL(k_flow_fb, dim3((uint32_t)((f.n_flows + 255) / 256)), dim3(256), 0, st, f, off, in, verdict, n_in);
+}
+
+void launch_flow_fb_report(const FlowArgs& f, unsigned long long* res, hipStream_t st) {
+  (void)hipMemsetAsync(res, 0, sizeof(unsigned long long) * kFlowFbResWords, st);
+  hipLaunchKernelGGL(k_flow_fb_report, dim3(std::min(ping_grid(f.n_flows), 256u)), dim3(256), 0, st, f, res);
 }
 
 void launch_ping_pairs(const PingArgs& a, uint64_t i0, uint64_t n, tgsim_ping_pair* out, hipStream_t st) {

@@ -102,6 +102,13 @@ void launch_flow_cc_report(const FlowArgs& f, unsigned long long* res, hipStream
 // With f.rt set they run the RTT-estimator instantiations (either way with f.cc).  _rto_report: res =
 // kFlowRtoResWords words, the two minima complemented (words 3 and 6 hold the maximum of ~x).
 void launch_flow_rto_report(const FlowArgs& f, unsigned long long* res, hipStream_t st);
+// With f.fb set _init zeroes the fb rows.  _fb: the verdict feedback of one simulated window behind
+// its simulate kernel (a lane per flow over its source's row of the step's input off[n_peers + 1], in,
+// verdict; f.cal.win0 = the window's first tick); no packet at or past n_in is read.  _fb_report: res
+// = kFlowFbResWords words.
+void launch_flow_fb(const FlowArgs& f, const uint64_t* off, const InRec* in, const uint8_t* verdict, uint64_t n_in,
+                    hipStream_t st);
+void launch_flow_fb_report(const FlowArgs& f, unsigned long long* res, hipStream_t st);
 // Per-group traffic matrix (tgsim_group_matrix).  _src: words 0..9 from a window's input (off[n_src + 1],
 // in, verdict) behind its simulate kernel; n_in: the window's offered packets (picks the lanes per
 // source).  _dst: words 10..13 from delivery-ordered records, segment sg = off[sg] ..

@@ -233,7 +233,7 @@ class CABIEngine:
     # -- flow driver (tgsim_flow_*) ----------------------------------------------------------------
     def flow_init(self, flows=None, seg_len: int = 1460, ack_len: int = 64, window: int = 16, rto_ticks: int = 1,
                   max_attempts: int = 8, bin_ns: int = 0, n_bins: int = 0, cc: Optional[dict] = None,
-                  rto: Optional[dict] = None) -> None:
+                  rto: Optional[dict] = None, fb: Optional[dict] = None) -> None:
         """Arms the device flow driver: `flows` is an abi.FLOW_SPEC_DTYPE table sorted by src
         (workloads.flow_table_mesh); a fixed window of `window` segments, one ACK per delivered
         segment, a retransmission timer of rto_ticks per segment, at most max_attempts offers of a
@@ -242,7 +242,14 @@ class CABIEngine:
         congestion window and fast retransmit of tgsim_flow_init_cc: `window` is then the cap.  `rto`
         (a dict of min_rto_ticks, max_rto_ticks and backoff; missing keys as
         workloads.FLOW_RTO_DEFAULT) arms it through tgsim_flow_init_rto with the RTT estimator:
-        rto_ticks is then each flow's initial timer, and min_rto_ticks the longest window."""
+        rto_ticks is then each flow's initial timer, and min_rto_ticks the longest window.  `fb` (a dict
+        of fail_mask, default 0: count only) arms it through tgsim_flow_init_fb with the verdict
+        feedback: per-flow verdict counters (flow_fb_rows, flow_fb_report), and a flow whose data
+        offer is refused with a verdict in fail_mask (bits 1 << abi.V_*, within abi.FLOW_FB_REFUSALS)
+        fails at that offer's tick."""
+        self.flow_fb_armed = False
+        if fb is not None and flows is not None:
+            return self._flow_init_fb(flows, abi.Flow(seg_len, ack_len, window, rto_ticks, max_attempts, n_bins, bin_ns), cc, rto, fb)
         if rto is not None and flows is not None:
             return self._flow_init_rto(flows, abi.Flow(seg_len, ack_len, window, rto_ticks, max_attempts, n_bins, bin_ns), cc, rto)
         fn = self._gossip_fn("flow_init" if cc is None or flows is None else "flow_init_cc")
@@ -274,6 +281,36 @@ class CABIEngine:
         self._check(fn(self._h, C.byref(p), c, C.byref(r), t.ctypes.data, len(t)), "flow_init_rto")
         self.flow_cc_armed, self.flow_rto_armed = cc is not None, True
         self._n_flows = len(t)
+
+    def _flow_init_fb(self, flows, p, cc: Optional[dict], rto: Optional[dict], fb: dict) -> None:
+        fn = self._gossip_fn("flow_init_fb")
+        self.flow_cc_armed = self.flow_rto_armed = False
+        t = np.ascontiguousarray(flows, dtype=abi.FLOW_SPEC_DTYPE)
+        if t.ndim != 1:
+            raise ValueError("flow_init: flows must be a 1-d abi.FLOW_SPEC_DTYPE table")
+        c = None if cc is None else C.byref(abi.FlowCC(cc.get("init_cwnd", 1), cc.get("init_ssthresh", 0), cc.get("dupthresh", 3), 0))
+        r = None if rto is None else C.byref(abi.FlowRto(rto.get("min_rto_ticks", 1), rto.get("max_rto_ticks", abi.FLOW_MAX_RTO),
+                                                         rto.get("backoff", 1), 0))
+        b = abi.FlowFb(fb.get("fail_mask", 0))
+        self._check(fn(self._h, C.byref(p), c, r, C.byref(b), t.ctypes.data, len(t)), "flow_init_fb")
+        self.flow_cc_armed, self.flow_rto_armed, self.flow_fb_armed = cc is not None, rto is not None, True
+        self._n_flows = len(t)
+
+    def flow_fb_rows(self, first: int = 0, n: Optional[int] = None) -> np.ndarray:
+        """abi.FLOW_FB_ROW_DTYPE rows of flows [first, first + n) (tgsim_flow_fb_rows)."""
+        fn = self._gossip_fn("flow_fb_rows")
+        total = getattr(self, "_n_flows", None) or 0  # (unarmed: the call says so)
+        n = max(total - first, 0) if n is None else n
+        out = np.zeros(n, dtype=abi.FLOW_FB_ROW_DTYPE)
+        self._check(fn(self._h, first, n, out.ctypes.data, len(out)), "flow_fb_rows")
+        return out
+
+    def flow_fb_report(self) -> dict:
+        """The verdict feedback's summary over every flow (abi.FLOW_FB_SUMMARY_FIELDS), reduced on the
+        device (tgsim_flow_fb_report): the data offers by verdict, and the FAILED flows by cause."""
+        s = abi.FlowFbSummary()
+        self._check(self._gossip_fn("flow_fb_report")(self._h, C.byref(s)), "flow_fb_report")
+        return {k: int(getattr(s, k)) for k in abi.FLOW_FB_SUMMARY_FIELDS}
 
     def flow_rto_rows(self, first: int = 0, n: Optional[int] = None) -> np.ndarray:
         """abi.FLOW_RTO_ROW_DTYPE rows of flows [first, first + n) (tgsim_flow_rto_rows)."""

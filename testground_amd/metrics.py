@@ -106,7 +106,9 @@ def flow_lines(report: Dict, bin_ns: int, plan: str, run: str, ts_ns: int) -> Li
     cc=eng.flow_cc_report()), flows armed with cc) adds one `flow.cc.<field>` line per field of it,
     the cwnd minimum and maximum only while a flow is ACTIVE.  One that carries the estimator's summary
     under "rto" (eng.flow_rto_report(), flows armed with rto) adds one `flow.rto.<field>` line per
-    field of it, the minima and maxima only once a flow has a sample."""
+    field of it, the minima and maxima only once a flow has a sample.  One that carries the verdict
+    feedback's summary under "fb" (eng.flow_fb_report(), flows armed with fb) adds one
+    `flow.fb.<field>` line per field of it."""
     tags = f"run={_escape(run)}"
     out: List[str] = []
     for name, key in FLOW_METRICS:
@@ -126,6 +128,9 @@ def flow_lines(report: Dict, bin_ns: int, plan: str, run: str, ts_ns: int) -> Li
         if key.endswith(("_min", "_max")) and not rto["sampled_flows"]:
             continue
         out.append(f"{_escape(f'results.{plan}.flow.rto.{key}')},{tags} value={int(rto[key])}i {ts_ns}")
+    fb = report.get("fb")
+    for key in abi.FLOW_FB_SUMMARY_FIELDS if fb else ():
+        out.append(f"{_escape(f'results.{plan}.flow.fb.{key}')},{tags} value={int(fb[key])}i {ts_ns}")
     meas = _escape(f"results.{plan}.flow.fct_hist")
     out += [f"{meas},{tags},bin={b * int(bin_ns)} value={int(c)}i {ts_ns}" for b, c in enumerate(report["hist"]) if c]
     return out

@@ -470,6 +470,10 @@ class FlowModel:
     def _non_stale_ack(self, f: int, seg: int, seq: int, tick: int) -> None:
         pass
 
+    # The verdict feedback (FlowFbMixin): a simulated window's packets and verdict bytes, ahead of its records.
+    def _verdicts(self, pk: np.ndarray, v: np.ndarray, win0: int) -> None:
+        pass
+
     def window_packets(self, window: int) -> np.ndarray:
         """The window's offered packets in (src, tick, seq, dst) order: the segments due in it, and the
         calendar's ACKs due in it, which leave the calendar."""
@@ -579,6 +583,7 @@ class FlowModel:
         self.eng.step(window)
         self.now += window
         v, d = self.eng.verdicts(), self.eng.drain()
+        self._verdicts(pk, v, self.now - window)
         self.receive(d)
         self.windows += 1
         if len(self.cal):  # 1: due in the next window; 2 and more: moved to the other calendar buffer first
@@ -895,6 +900,87 @@ class FlowRtoMixin:
                 "rto_max": int(rto.max()) if on.any() else 0}
 
 
+FLOW_FB_DEFAULT = dict(fail_mask=0)
+
+
+class FlowFbMixin:
+    """The verdict feedback of tgsim_flow_init_fb (include/tgsim.h) over any of the models: `fb` holds
+    fail_mask.  After a window's simulation its data packets are counted per flow by verdict, and a
+    flow with a refused offer whose verdict is in fail_mask fails at the earliest such offer's tick,
+    ahead of the records the same step emitted."""
+
+    def __init__(self, eng, flow: Dict, flows: np.ndarray, *cc, fb: Dict, **kw):
+        super().__init__(eng, flow, flows, *cc, **kw)
+        self.fb_p = dict(FLOW_FB_DEFAULT, **fb)
+        if self.fb_p["fail_mask"] & ~abi.FLOW_FB_REFUSALS:
+            raise ValueError(f"flow: fail_mask {self.fb_p['fail_mask']:#x} has bits outside the refusal verdicts")
+        self.fb = np.zeros(len(self.spec), dtype=abi.FLOW_FB_ROW_DTYPE)
+        # what the run exercised: timer failures of a window replaced by a refusal of the same window,
+        # stale ACKs, in the step that failed them, of flows a verdict failed, refusals outside the mask
+        self.fail_replaced = self.stale_after_fail = self.refused_unmasked = 0
+        self._failed_now: list = []
+
+    def _verdicts(self, pk: np.ndarray, v: np.ndarray, win0: int) -> None:
+        mask, first = self.fb_p["fail_mask"], {}  # flow -> (tick, seq, verdict) of the refusal that fails it
+        self._failed_now = []
+        for src, seq, tick, vb in zip(pk["src"].tolist(), pk["seq"].tolist(), pk["tick"].tolist(), np.asarray(v).tolist()):
+            if seq & abi.FLOW_ACK:
+                continue
+            f, low = int(self.first[src]) + (seq >> abi.FLOW_SLOT_SHIFT & 15), vb & 15
+            row = self.fb[f]
+            if low == abi.V_SCHEDULED:
+                row["scheduled"] += 1
+            elif low == abi.V_LOSS:
+                row["lost"] += 1
+            elif low == abi.V_QUEUE_FULL:
+                row["queue_full"] += 1
+            elif abi.V_DISCONNECTED <= low <= abi.V_PROHIBIT:
+                row["refused"] += 1
+                if not mask >> low & 1:
+                    self.refused_unmasked += 1
+                elif f not in first or (tick, seq) < first[f][:2]:
+                    first[f] = (tick, seq, low)
+            row["cloned"] += vb >> 4 != abi.V_NONE
+        for f, (tick, seq, low) in first.items():
+            timer = (self.state[f] == abi.FLOW_FAILED and not self.fb[f]["fail_verdict"]
+                     and self.done_ns[f] >= win0 * self.tick_ns)
+            if self.state[f] != abi.FLOW_ACTIVE and not timer:
+                continue
+            self.fail_replaced += bool(timer)
+            self.state[f], self.done_ns[f] = abi.FLOW_FAILED, (win0 + tick) * self.tick_ns
+            self.fb[f]["fail_verdict"], self.fb[f]["fail_seg"] = low, seq & abi.FLOW_SEG_MASK
+            self.fb[f]["fail_attempt"] = seq >> abi.FLOW_ATTEMPT_SHIFT & 15
+            self._failed_now.append(f)
+
+    def receive(self, d: np.ndarray) -> None:
+        before = int(self.stale[self._failed_now].sum())
+        super().receive(d)
+        self.stale_after_fail += int(self.stale[self._failed_now].sum()) - before
+        self._failed_now = []
+
+    def fb_rows(self) -> np.ndarray:
+        return self.fb.copy()
+
+    def fb_report(self) -> Dict:
+        failed, fv = self.state == abi.FLOW_FAILED, self.fb["fail_verdict"]
+        out = {k: int(self.fb[k].sum()) for k in ("scheduled", "lost", "queue_full", "refused", "cloned")}
+        out["refused_flows"] = int((self.fb["refused"] > 0).sum())
+        out["failed_timer"] = int((failed & (fv == 0)).sum())
+        for k, name in enumerate(abi.FLOW_FB_SUMMARY_FIELDS[-4:]):
+            out[name] = int((failed & (fv == 1 + k)).sum())
+        return out
+
+
+def flow_model(eng, flow: Dict, flows: np.ndarray, cc=None, rto=None, fb=None):
+    """The host model for an arming: FlowModel, with the congestion window when `cc` is given, the RTT
+    estimator when `rto` is, the verdict feedback when `fb` is (the dicts of Engine.flow_init)."""
+    bases = ((FlowFbMixin,) if fb is not None else ()) + ((FlowRtoMixin,) if rto is not None else ())
+    bases += (FlowModel if cc is None else FlowCCModel,)
+    cls = bases[0] if len(bases) == 1 else type("Flow" + "".join(b.__name__[4:-5] for b in bases[:-1]) + bases[-1].__name__[4:], bases, {})
+    kw = dict(**({} if rto is None else {"rto": rto}), **({} if fb is None else {"fb": fb}))
+    return cls(eng, flow, flows, *(() if cc is None else (cc,)), **kw)
+
+
 class FlowRtoModel(FlowRtoMixin, FlowModel):
     """FlowModel armed with `rto`: FlowRtoModel(eng, flow, flows, rto=dict(...))."""
 
@@ -904,7 +990,7 @@ class FlowCCRtoModel(FlowRtoMixin, FlowCCModel):
 
 
 def flow_reference(eng, flow: Dict, flows: np.ndarray, n_windows: int, window: int, probe_at=(), before=None,
-                   cc=None, rto=None) -> Dict:
+                   cc=None, rto=None, fb=None) -> Dict:
     """The flow loop driven from the host over `eng` (submit / step / verdicts / drain): per-window
     (verdicts, deliveries) under "windows", the final "rows" and "summary" (report fields and hist),
     and under "probes" the (rows, summary) after each window index in probe_at.  before(w) runs ahead
@@ -912,8 +998,12 @@ def flow_reference(eng, flow: Dict, flows: np.ndarray, n_windows: int, window: i
     Engine.flow_init) the model is FlowCCModel, the result has "cc_rows" and "cc_summary" too, and a
     probe is (rows, summary, cc_rows, cc_summary).  With `rto` (the dict of Engine.flow_init) the model
     is FlowRtoModel or FlowCCRtoModel, the result has "rto_rows" and "rto_summary" too, and a probe ends
-    with (rto_rows, rto_summary)."""
-    if rto is None:
+    with (rto_rows, rto_summary).  With `fb` (the dict of Engine.flow_init) the model has the verdict
+    feedback (FlowFbMixin), the result has "fb_rows" and "fb_summary" too, and a probe ends with (fb_rows,
+    fb_summary)."""
+    if fb is not None:
+        m = flow_model(eng, flow, flows, cc, rto, fb)
+    elif rto is None:
         m = FlowModel(eng, flow, flows) if cc is None else FlowCCModel(eng, flow, flows, cc)
     else:
         m = FlowRtoModel(eng, flow, flows, rto=rto) if cc is None else FlowCCRtoModel(eng, flow, flows, cc, rto=rto)
@@ -924,12 +1014,15 @@ def flow_reference(eng, flow: Dict, flows: np.ndarray, n_windows: int, window: i
         out["windows"].append(m.step(window))
         if w in probe_at:
             out["probes"][w] = ((m.rows(), m.report()) + (() if cc is None else (m.cc_rows(), m.cc_report()))
-                                + (() if rto is None else (m.rto_rows(), m.rto_report())))
+                                + (() if rto is None else (m.rto_rows(), m.rto_report()))
+                                + (() if fb is None else (m.fb_rows(), m.fb_report())))
     out["rows"], out["summary"] = m.rows(), m.report()
     if cc is not None:
         out["cc_rows"], out["cc_summary"] = m.cc_rows(), m.cc_report()
     if rto is not None:
         out["rto_rows"], out["rto_summary"] = m.rto_rows(), m.rto_report()
+    if fb is not None:
+        out["fb_rows"], out["fb_summary"] = m.fb_rows(), m.fb_report()
     return out
 
 
@@ -937,10 +1030,11 @@ def flow_run(eng, n_windows: int, window: int, collect: bool = False, probe_at=(
     """The device loop on an armed engine (Engine.flow_init): n_windows of gen_flow + step.  Nothing
     reaches the host unless asked for: collect keeps each window's (verdicts, deliveries), probe_at
     the (rows, report) after those windows, and the (cc rows, cc report) beside them when the engine
-    is armed with congestion control, and the (rto rows, rto report) last when it is armed with the RTT
-    estimator."""
+    is armed with congestion control, the (rto rows, rto report) when it is armed with the RTT
+    estimator, and the (fb rows, fb report) last when it is armed with the verdict feedback."""
     out = {"windows": [], "probes": {}}
     cc, rto = getattr(eng, "flow_cc_armed", False), getattr(eng, "flow_rto_armed", False)
+    fb = getattr(eng, "flow_fb_armed", False)
     for w in range(n_windows):
         if before is not None:
             before(w)
@@ -950,7 +1044,8 @@ def flow_run(eng, n_windows: int, window: int, collect: bool = False, probe_at=(
             out["windows"].append((eng.verdicts(), eng.drain()))
         if w in probe_at:
             out["probes"][w] = ((eng.flow_rows(), eng.flow_report()) + ((eng.flow_cc_rows(), eng.flow_cc_report()) if cc else ())
-                                + ((eng.flow_rto_rows(), eng.flow_rto_report()) if rto else ()))
+                                + ((eng.flow_rto_rows(), eng.flow_rto_report()) if rto else ())
+                                + ((eng.flow_fb_rows(), eng.flow_fb_report()) if fb else ()))
     return out
 
 
