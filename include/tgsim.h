@@ -231,7 +231,9 @@ int tgsim_gen_storm(void* engine, double lambda, uint32_t n_ticks);
 int tgsim_step(void* engine, uint32_t n_ticks);
 /* n_steps consecutive tgsim_step(engine, n_ticks) calls, with identical results (verdicts then
  * refer to the last window).  Windows of generated traffic (tgsim_gen_storm) on an engine that owns
- * every peer run up to kFuseMax = 8 per launch (TGSIM_FUSE, default 8): a source's next window starts as soon as its previous one
+ * every peer run in launches of up to TGSIM_FUSE windows (default and most: kFuseMax = 32; a longer
+ * call ends with a short launch of 6 where that shortens the wait after it), fewer per launch when their buffers would take more
+ * than half of the free device memory (TGSIM_FUSE_MEM_MB sets that budget): a source's next window starts as soon as its previous one
  * is done, so one window's slowest sources overlap the next window's first ones (no launch tail or
  * gap between the windows of a group).  A source whose previous window does not complete in time
  * (a hardware fault) is reported as -EIO. */
@@ -942,6 +944,8 @@ int64_t tgsim_debug_carry_bytes(void* engine);
 int64_t tgsim_debug_bucket_records(void* engine);
 /* Diagnostics: windows simulated by fused launches (tgsim_step_n) since the engine was created. */
 int64_t tgsim_debug_fused_windows(void* engine);
+/* Diagnostics: fused launches (groups of windows) since the engine was created. */
+int64_t tgsim_debug_fused_launches(void* engine);
 /* Diagnostics: windows simulated by the sparse kernels (k_sim_sparse + k_sim_multi + k_sim_list) since
  * the engine was created; the others ran the dense k_sim (or were fused). */
 int64_t tgsim_debug_sparse_windows(void* engine);

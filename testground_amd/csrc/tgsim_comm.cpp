@@ -559,7 +559,7 @@ int tgsim_comm_run(void* e, uint32_t n_ticks, uint32_t n_steps, uint32_t fuse, u
   Comm* C = comm_of(e);
   if (!C) return e ? engine_fail(e, -EINVAL, "comm_run: no communicator (tgsim_comm_init)") : -EINVAL;
   if (C->timed_out) return -ETIMEDOUT;  // a collective never completed (tgsim_last_error says which)
-  if (n_ticks == 0 || fuse == 0 || fuse > kFuseMax) return -EINVAL;
+  if (n_ticks == 0 || fuse == 0 || fuse > kFuseMaxSharded) return -EINVAL;
   if (C->launched) return engine_fail(e, -EBUSY, "comm_run: a launched window is not finished (tgsim_comm_finish)");
   if (engine_ping_armed(e)) return engine_fail(e, -EBUSY, "comm_run: the ping driver is armed (single engine, tgsim_step)");
   if (engine_flow_armed(e)) return engine_fail(e, -EBUSY, "comm_run: the flow driver is armed (single engine, tgsim_step)");

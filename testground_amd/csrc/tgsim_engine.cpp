@@ -420,19 +420,25 @@ struct tgsim_engine_s {
   };
   LocalSet fset[2][kFuseMax];
   DevBuf<uint64_t> f_lcnt[2];  // [window][destination] histograms of a group (zero between groups)
+  DevBuf<SimArgs> f_desc;      // the windows' descriptors of a group of more than 8 (k_fused_desc writes, k_sim_fused reads, on one stream)
+  uint32_t fuse_sets = 0;      // windows per group the buffer sets of both parities are sized for
+  uint32_t fuse_cap = 0;       // fuse_max after the memory rule (fuse_group_cap; 0: not decided yet)
+  uint64_t fuse_set_recs = 0;  // records per emit set that decision was made for
+  uint64_t fuse_held = 0;      // bytes it reserved (they are missing from the free memory a later decision sees)
+  int64_t fuse_mem_mb = -1;    // TGSIM_FUSE_MEM_MB: the fused groups' memory budget (-1: half of free memory)
   hipEvent_t ev_fgrp[2] = {};
   uint32_t fgrp = 0;                    // parity of the next fused group
   DevBuf<uint8_t> f_verdict[kFuseMax];  // verdicts of a group's windows but the last (discarded)
   DevBuf<uint32_t> d_done, d_ticket;    // per-source completion words (window-major), ticket counter
   uint32_t step_no = 0, ticket_no = 0;  // windows and tickets issued by fused launches so far
-  uint64_t fused_windows = 0;
+  uint64_t fused_windows = 0, fused_launches = 0;
   uint64_t sparse_windows = 0;  // windows run by the sparse kernels (tgsim_debug_sparse_windows)
   uint32_t fused_wgs = 0;
   uint32_t routed_pct = 0;      // sharded (routed) groups: 0 = one workgroup per ticket (the grid turns
                                 // over), else a persistent grid of this % of the resident workgroups
   CommSlot comm{};              // tgsim_comm_init's exchange state (tgsim_comm.cpp)
   static constexpr uint32_t prio_heavy = 512;  // heaviest sources of a fused launch at wave priority 3 (A/B: 128 +1 %, 512 +7.5 %, 2048 +7 %, 4096 +5 %)  // k_sim_fused's persistent grid (resident workgroups), at the first launch
-  int fuse_max = 8;  // TGSIM_FUSE: windows per fused launch, up to kFuseMax (1: never fuse; A/B at 30 windows: 4 34.8, 8 36.3, 16 36.3 G pkt/s)
+  int fuse_max = 32;  // TGSIM_FUSE: windows per fused launch, up to kFuseMax (1: never fuse); A/B at 30 windows in profiles/LOG.md, "Long fused groups"
   DevBuf<uint64_t> d_stamps;
   uint64_t n_stamp_wg = 0;
 
@@ -1871,6 +1877,92 @@ bool fusable(Eng* E, uint32_t n_ticks, uint32_t g, bool routed = false) {
   return true;
 }
 
+// How tgsim_step_n cuts n windows at a cap.  The groups are the fewest of at most
+// cap windows, of near-equal size, the largest first.  A call's last delivery has no launch to run
+// beside, so whoever synchronises after the call waits for it: ~25 us per window of the last group
+// (kTailWinUs), where one more launch costs ~180 us (kBoundaryUs; both measured on the C3 storm,
+// profiles/LOG.md "Long fused groups").  The call therefore ends with a short group of kFuseTail
+// windows wherever that model says it pays: 30 windows run 24 + 6 at a cap of 32 and 8 + 8 + 8 + 6
+// at 8, but 16 windows at a cap of 8 stay 8 + 8.  A cap below kFuseFloor (a knob setting for tests
+// and A/B runs) keeps the split it always had, full groups and then the rest:
+// tests/test_gpu_fused.py counts on a fifth window at a cap of 4 running unfused.
+constexpr uint32_t kFuseFloor = 8;
+constexpr uint32_t kFuseTail = 6, kTailWinUs = 25, kBoundaryUs = 180;
+uint32_t fuse_tail(uint32_t n, uint32_t cap) {
+  if (cap < kFuseFloor || n <= kFuseTail) return 0;
+  const uint32_t k_plain = (n + cap - 1) / cap, last_plain = n / k_plain;
+  const uint32_t k_tail = (n - kFuseTail + cap - 1) / cap + 1;
+  if (last_plain <= kFuseTail) return 0;
+  return kTailWinUs * (last_plain - kFuseTail) > kBoundaryUs * (k_tail - k_plain) ? kFuseTail : 0;
+}
+// The next group of a call with n windows left, whose last `tail` windows form its last group.
+uint32_t fuse_next_group(uint32_t n, uint32_t cap, uint32_t tail) {
+  if (cap < kFuseFloor) return std::min(n, cap);
+  const uint32_t body = n > tail ? n - tail : n;
+  const uint32_t k = (body + cap - 1) / cap;
+  return (body + k - 1) / k;
+}
+// The largest group a call of n windows forms (its first).
+uint32_t fuse_largest_group(uint32_t n, uint32_t cap) { return n ? fuse_next_group(n, cap, fuse_tail(n, cap)) : 0; }
+
+// The cap of tgsim_step_n's next n_steps windows, and the buffer sets to hold.  A window of a group
+// owns an emit set of 2 n_max + kHeapCap * S records in both parities, its share of the delivery's
+// scatter buffer (and of the sorted output of a discarding engine) and a verdict buffer.  Both
+// parities are sized for the largest group this call forms, or that the windows already generated
+// and queued behind it can form (they are resident; the caller will step them), and only ever
+// grow: a call pays for what it uses, and a warm-up call of a few windows ahead of a long one over
+// queued windows does not make the long one reallocate.  Before more is reserved the total is
+// compared with the budget (TGSIM_FUSE_MEM_MB, else half of the free device memory); if it does not
+// fit, the cap is what fits, never below kFuseFloor (what the engine used before), and sets beyond
+// it are released.
+int fuse_group_cap(Eng* E, uint32_t n_ticks, uint32_t n_steps, uint32_t* cap_out) {
+  const uint32_t want = static_cast<uint32_t>(E->fuse_max), floor = std::min(want, kFuseFloor);
+  *cap_out = E->fuse_cap ? std::min(E->fuse_cap, want) : want;
+  if (n_steps < 2 || E->S != E->N) return 0;
+  uint64_t n_max = 0;
+  for (size_t i = 0; i < E->gen_q.size(); ++i)
+    if (E->gen_q[i].ticks == n_ticks) n_max = std::max(n_max, E->gen_q[i].n);
+  if (n_max < 64ull * E->S) return 0;  // nothing here fuses (fusable)
+  const uint64_t set_recs = 2 * n_max + static_cast<uint64_t>(kHeapCap) * E->S;
+  const uint32_t ahead = E->gen_q.size() > n_steps ? static_cast<uint32_t>(std::min<size_t>(E->gen_q.size() - n_steps, 1u << 20)) : 0;
+  const auto sets_at = [&](uint32_t cap) {
+    return std::max(fuse_largest_group(n_steps, cap), fuse_largest_group(ahead, cap));
+  };
+  uint32_t cap = *cap_out, sets = sets_at(cap);
+  if (sets <= E->fuse_sets && set_recs <= E->fuse_set_recs) return 0;  // held already
+  if (sets > floor) {  // the memory rule
+    const auto grown = [](uint64_t n) { return n + n / 2; };  // DevBuf::ensure's headroom
+    const uint64_t copies = (E->o.flags & TGSIM_OPT_DISCARD_DELIVERIES) ? 4 : 3;  // 2 parities, scatter, sorted
+    const uint64_t per_win = copies * grown(set_recs) * sizeof(tgsim_delivery) + grown(n_max) +
+                             2 * grown(E->S) * sizeof(uint32_t) + 4ull * E->N * sizeof(uint64_t);
+    uint64_t budget;
+    if (E->fuse_mem_mb >= 0) {
+      budget = static_cast<uint64_t>(E->fuse_mem_mb) << 20;
+    } else {
+      size_t free_b = 0, total_b = 0;
+      HIPCHK(hipMemGetInfo(&free_b, &total_b));
+      budget = (free_b + E->fuse_held) / 2;  // what the sets hold now is reused
+    }
+    if (sets * per_win > budget) {
+      cap = static_cast<uint32_t>(std::min<uint64_t>(cap, std::max<uint64_t>(floor, budget / per_win)));
+      sets = sets_at(cap);
+      E->fuse_cap = cap;
+      for (auto& grp : E->fset)
+        for (uint32_t i = sets; i < kFuseMax; ++i) {
+          grp[i].emit.release();
+          grp[i].emit_n.release();
+        }
+      for (uint32_t i = sets; i < kFuseMax; ++i) E->f_verdict[i].release();
+      E->fuse_sets = std::min(E->fuse_sets, sets);
+    }
+    E->fuse_held = std::max(sets, E->fuse_sets) * per_win;
+  }
+  E->fuse_set_recs = std::max(E->fuse_set_recs, set_recs);
+  E->fuse_sets = std::max(E->fuse_sets, sets);  // grow only; step_fused allocates at the next group
+  *cap_out = cap;
+  return 0;
+}
+
 // g consecutive windows in one k_sim_fused launch, then the g local deliveries on the delivery
 // stream (beside the next group's launch, which writes the other parity's buffer sets).
 struct GroupRoute {  // a sharded group: the windows' records routed into slotted chunks
@@ -1912,19 +2004,22 @@ int step_fused(Eng* E, uint32_t n_ticks, uint32_t g, const GroupRoute* gr = null
   a.order = ordered && E->order_valid ? E->d_order.p : nullptr;
   FusedArgs f{};
   const uint64_t nseg = static_cast<uint64_t>(g) * E->N;  // (window, destination) segments
+  // the buffer sets of both parities are sized at once for the largest group planned so far
+  // (fuse_group_cap; a sharded group keeps its own sizing), so a call's first group pays the
+  // allocations, not a longer one in its middle
+  const uint32_t n_sets = std::max({E->fuse_sets, g, gr ? std::min(static_cast<uint32_t>(E->fuse_max), kFuseMaxSharded) : 0u});
+  E->fuse_sets = n_sets;
   for (auto& lc : E->f_lcnt)
-    if (lc.cap < static_cast<uint64_t>(kFuseMax) * E->N) {
-      HIPCHK(lc.ensure(static_cast<uint64_t>(kFuseMax) * E->N));
+    if (lc.cap < static_cast<uint64_t>(n_sets) * E->N) {
+      HIPCHK(lc.ensure_exact(static_cast<uint64_t>(n_sets) * E->N));
       HIPCHK(hipMemsetAsync(lc.p, 0, sizeof(uint64_t) * lc.cap, E->st));
     }
+  if (g > kFuseMaxSharded) HIPCHK(E->f_desc.ensure_exact(kFuseMax));
   uint64_t rec_bound = 0, n_max = 0;  // records the group's windows can emit; largest window
   for (uint32_t i = 0; i < g; ++i) {
     rec_bound += 2 * win[i].n + static_cast<uint64_t>(kHeapCap) * E->S;
     n_max = std::max(n_max, win[i].n);
   }
-  // every buffer set of both parities sized at once (the first group pays the allocations, not a
-  // later one in the middle of a run)
-  const uint32_t n_sets = std::max(static_cast<uint32_t>(E->fuse_max), g);
   for (auto& grp : E->fset)
     for (uint32_t i = 0; i < n_sets; ++i) {
       HIPCHK(grp[i].emit.ensure(2 * n_max + static_cast<uint64_t>(kHeapCap) * E->S));
@@ -1933,8 +2028,8 @@ int step_fused(Eng* E, uint32_t n_ticks, uint32_t g, const GroupRoute* gr = null
   HIPCHK(E->d_verdict.ensure(n_max ? n_max : 1));
   for (uint32_t i = 0; i + 1 < n_sets; ++i) HIPCHK(E->f_verdict[i].ensure(n_max ? n_max : 1));
   if (!gr) {  // the group delivery's scratch, for the largest group
-    const uint64_t segs = static_cast<uint64_t>(E->fuse_max) * E->N;
-    const uint64_t recs = static_cast<uint64_t>(E->fuse_max) * (2 * n_max + static_cast<uint64_t>(kHeapCap) * E->S);
+    const uint64_t segs = static_cast<uint64_t>(n_sets) * E->N;
+    const uint64_t recs = static_cast<uint64_t>(n_sets) * (2 * n_max + static_cast<uint64_t>(kHeapCap) * E->S);
     HIPCHK(E->d_doff.ensure(segs + 1));
     HIPCHK(E->d_dpos.ensure(segs));
     HIPCHK(E->d_dblk.ensure((segs + 1023) / 1024 + 1));
@@ -1961,6 +2056,7 @@ int step_fused(Eng* E, uint32_t n_ticks, uint32_t g, const GroupRoute* gr = null
   f.ticket_base = E->ticket_no;
   f.ticket = E->d_ticket.p;
   f.done = E->d_done.p;
+  f.desc = E->f_desc.p;
   hipEvent_t ev0, ev1;
   HIPCHK(take_event(E, &ev0));
   HIPCHK(take_event(E, &ev1));
@@ -1973,7 +2069,7 @@ int step_fused(Eng* E, uint32_t n_ticks, uint32_t g, const GroupRoute* gr = null
   f.persistent = gr ? (E->routed_pct ? 1u : 0u) : 1u;
   const uint32_t wgs = gr && E->routed_pct ? std::max(1u, E->fused_wgs * std::min(E->routed_pct, 100u) / 100u)
                                            : E->fused_wgs;
-  launch_sim_fused(a, f, wgs, E->st);
+  if (launch_sim_fused(a, f, wgs, E->st)) return E->fail(-EINVAL, "step_fused: a group of %u windows cannot be launched", g);
   HIPCHK(hipGetLastError());
   E->sim_calls++;  // behind the wait for set p's last readers (ev_fgrp): take_gen's count
   HIPCHK(hipEventRecord(ev1, E->st));
@@ -1984,6 +2080,7 @@ int step_fused(Eng* E, uint32_t n_ticks, uint32_t g, const GroupRoute* gr = null
   const uint32_t tickets = g * E->S;
   E->ticket_no += tickets + (f.persistent ? std::min(wgs, tickets) : 0u);
   E->fused_windows += g;
+  E->fused_launches++;
   if (ordered) {  // the next launch's dispatch order: the last window's HTB records, heaviest first
     HIPCHK(E->d_order.ensure(E->S));
     launch_order(E->fset[p][g - 1].emit_n.p, E->S, E->d_order.p, E->st);
@@ -2262,6 +2359,7 @@ int tgsim_create(const tgsim_opts* opts, void** out) {
     E->slack_forced = true;
   }
   if (const char* fz = getenv("TGSIM_FUSE")) E->fuse_max = std::max(1, std::min(atoi(fz), static_cast<int>(kFuseMax)));
+  if (const char* fm = getenv("TGSIM_FUSE_MEM_MB")) E->fuse_mem_mb = std::max(0ll, atoll(fm));
   for (hipEvent_t& ev : E->ev_fgrp) {
     if ((rc = E->hip(hipEventCreateWithFlags(&ev, kEvSync), "event"))) return bail(rc);
     if ((rc = E->hip(hipEventRecord(ev, E->dst_st), "event"))) return bail(rc);
@@ -2375,6 +2473,7 @@ void tgsim_destroy(void* e) {
   for (auto& grp : E->fset)
     for (auto& ls : grp) { ls.emit.release(); ls.emit_n.release(); }
   for (auto& v : E->f_lcnt) v.release();
+  E->f_desc.release();
   for (auto& v : E->f_verdict) v.release();
   E->d_done.release(); E->d_ticket.release();
   for (hipEvent_t ev : E->ev_fgrp)
@@ -3450,7 +3549,7 @@ int tgsim_step_sim_launch_slotted(void* e, uint32_t n_ticks, uint32_t n_ranks, c
 int tgsim_step_sim_launch_slotted_n(void* e, uint32_t n_ticks, uint32_t n_win, uint32_t n_ranks,
                                     const uint32_t* bounds, void* d_out, uint64_t slot_cap, void* routed_event) {
   Eng* E = as_eng(e);
-  if (!E || n_ticks == 0 || n_win == 0 || n_win > kFuseMax || n_ranks == 0 || n_ranks > 8 || !bounds || !d_out ||
+  if (!E || n_ticks == 0 || n_win == 0 || n_win > kFuseMaxSharded || n_ranks == 0 || n_ranks > 8 || !bounds || !d_out ||
       slot_cap == 0)
     return -EINVAL;
   if (n_win == 1)
@@ -3470,7 +3569,7 @@ int tgsim_step_sim_launch_slotted_n(void* e, uint32_t n_ticks, uint32_t n_win, u
 int tgsim_deliver_slotted_n_async(void* e, const void* d_in, uint32_t n_ranks, uint32_t n_win, uint64_t slot_cap,
                                   void* wait_event) {
   Eng* E = as_eng(e);
-  if (!E || !d_in || n_ranks == 0 || n_ranks > 8 || n_win == 0 || n_win > kFuseMax || slot_cap == 0) return -EINVAL;
+  if (!E || !d_in || n_ranks == 0 || n_ranks > 8 || n_win == 0 || n_win > kFuseMaxSharded || slot_cap == 0) return -EINVAL;
   HIPCHK(hipSetDevice(E->dev));
   return deliver(E, static_cast<const tgsim_delivery*>(d_in), static_cast<uint64_t>(n_ranks) * n_win * (slot_cap + 1),
                  static_cast<hipEvent_t>(wait_event), false, slot_cap, n_win);
@@ -3578,9 +3677,12 @@ int tgsim_step_n(void* e, uint32_t n_ticks, uint32_t n_steps) {
   if (!E || n_ticks == 0) return -EINVAL;
   if (E->route_n) return E->fail(-EBUSY, "launched steps are not finished yet");
   HIPCHK(hipSetDevice(E->dev));
+  uint32_t cap = 1;
+  int rc = fuse_group_cap(E, n_ticks, n_steps, &cap);
+  if (rc) return rc;
+  const uint32_t tail = fuse_tail(n_steps, cap);  // decided once per call (fuse_tail)
   while (n_steps) {
-    const uint32_t g = std::min(n_steps, static_cast<uint32_t>(E->fuse_max));
-    int rc;
+    const uint32_t g = fuse_next_group(n_steps, cap, tail);
     if (fusable(E, n_ticks, g)) {
       rc = step_fused(E, n_ticks, g);
       n_steps -= g;
@@ -3810,6 +3912,11 @@ int64_t tgsim_debug_sparse_windows(void* e) {
 int64_t tgsim_debug_fused_windows(void* e) {
   Eng* E = as_eng(e);
   return E ? static_cast<int64_t>(E->fused_windows) : -EINVAL;
+}
+
+int64_t tgsim_debug_fused_launches(void* e) {
+  Eng* E = as_eng(e);
+  return E ? static_cast<int64_t>(E->fused_launches) : -EINVAL;
 }
 
 void* tgsim_stream(void* e) {

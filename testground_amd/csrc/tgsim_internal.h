@@ -198,8 +198,10 @@ constexpr uint32_t kStampSlots = 8 + kProfSlots;  // 8 phase stamps + the profil
 // Fused launch of up to kFuseMax consecutive windows (k_sim_fused).  Window-major:
 // ticket t -> window t / S of the (t % S)-th source in dispatch order, started once the source's
 // window k - 1 has stored done[s] = step_base + k (the hand-off).  The windows differ only in these
-// per-window fields.
-constexpr uint32_t kFuseMax = 8;
+// per-window fields.  The windows' full SimArgs (the descriptors) live in a device buffer that
+// k_fused_desc fills ahead of the launch: 32 x 280 B do not fit the 4-KB kernel-argument segment.
+constexpr uint32_t kFuseMax = 32;
+constexpr uint32_t kFuseMaxSharded = 8;  // the sharded groups (tgsim_comm_run, the slotted launches) keep 8
 struct FusedWindow {
   const uint64_t* off;
   const InRec* in;
@@ -219,6 +221,26 @@ struct FusedArgs {
   uint32_t prio_n;      // tickets at dispatch positions below prio_n run at wave priority 3
   uint32_t persistent;  // 1: a grid of resident workgroups claims tickets until none is left; 0: one
                         // workgroup per ticket (the slots turn over, so an exchange can be dispatched)
+  SimArgs* desc;        // [n_win] the windows' descriptors on the device (the group parity's buffer)
+};
+// k_sim_fused8's control block (groups of up to kFuseMaxSharded windows, arguments in the
+// kernel-argument segment).
+struct FusedArgs8 {
+  FusedWindow w[kFuseMaxSharded];
+  uint32_t n_win, step_base, ticket_base;
+  uint32_t* ticket;
+  uint32_t* done;
+  uint32_t prio_n, persistent;
+};
+// What k_sim_fused itself takes by value: the launch's control words and the few SimArgs fields it
+// reads outside sim_source (the same in every window).
+struct FusedCtl {
+  uint32_t n_win, step_base, ticket_base, prio_n, persistent, n_src;
+  uint32_t* ticket;
+  uint32_t* done;
+  const uint32_t* order;
+  unsigned long long* stats;
+  uint64_t* err_host;
 };
 constexpr uint32_t kErrHandoff = 2u;  // a window waited too long for its source's previous window
 constexpr uint32_t kErrDeliverCap = 4u;  // a local delivery's records exceed its buffers (TGSIM_DELIVER_SLACK)

@@ -1851,8 +1851,87 @@ __global__ __launch_bounds__(kWave, 3) void k_sim_recv(SimArgs a) {
 // instead of one per window).  Persistent: the grid is what fits on the chip at once, and each
 // workgroup takes tickets in order until none is left (its next ticket claimed during the write-back
 // of the current one), so no slot waits for a workgroup dispatch between two sources.
+// The windows' arguments (window k's SimArgs at desc[k]: tables and state shared, step fields its own)
+// are in a device buffer that k_fused_desc fills on the same stream ahead of the launch and nothing
+// writes while k_sim_fused runs.  Window k's arguments are read in place through the constant
+// address space (scalar loads of invariant memory: re-read when needed instead of held in spilled
+// SGPRs), as they were in the kernel-argument segment, which 32 windows of 280 B outgrow.
+__device__ __forceinline__ const SimArgs& desc_window(const SimArgs* desc, uint32_t k) {
+  using ConstSimArgs = __attribute__((address_space(4))) const SimArgs;
+  return *(const SimArgs*)((ConstSimArgs*)desc + k);
+}
+// One workgroup per window: the base arguments with the window's own fields, stored as desc[k].
+__global__ __launch_bounds__(kWave) void k_fused_desc(SimArgs a, FusedArgs f) {
+  const uint32_t k = blockIdx.x;
+  if (k >= f.n_win || threadIdx.x) return;
+  const FusedWindow& w = f.w[k];
+  a.off = w.off;
+  a.in = w.in;
+  a.verdict = w.verdict;
+  a.emit = w.emit;
+  a.emit_n = w.emit_n;
+  a.dst_cnt = w.dst_cnt;
+  a.t0_ns = w.t0_ns;
+  a.horizon_ns = w.horizon_ns;
+  f.desc[k] = a;
+}
+
+// WINDOW-MAJOR (the default): ticket t is window t / S of the (t mod S)-th source in dispatch
+// order; a ticket of window k > 0 polls its source's completion word until window k - 1 has stored
+// it, and the queue crosses HBM between the windows (the sc1 hand-off above).  Every claimed ticket
+// is held by a resident workgroup and waits only for a lower ticket, so the lowest unfinished ticket
+// can always run: no deadlock; the wait is bounded anyway (kErrHandoff, then the host reports -EIO).
+// Tickets interleave the windows of all sources at a granularity of one source-window, which keeps
+// the launch's tail short (a source-major form, each source's windows back to back with its queue
+// resident in LDS, was bit-exact but slower: DESIGN.md §5.2).
+__global__ __launch_bounds__(kWave, 3) void k_sim_fused(const SimArgs* desc, FusedCtl f) {
+  __shared__ SimLdsT<kHeapCap> lds;
+  const uint32_t total = f.n_win * f.n_src;
+  uint32_t t = 0;
+  if (threadIdx.x == 0) t = atomicAdd(f.ticket, 1u) - f.ticket_base;
+  t = (uint32_t)__builtin_amdgcn_readfirstlane((int)t);
+  while (t < total) {
+    const uint32_t k = t / f.n_src, pos = t - k * f.n_src;
+    const uint32_t s = f.order ? f.order[pos] : pos;
+    // the heaviest sources (first in dispatch order) chain their windows through the launch: their
+    // waves issue first on their SIMDs, so the chain is not the launch's critical path
+    if (pos < f.prio_n) __builtin_amdgcn_s_setprio(3);
+    else __builtin_amdgcn_s_setprio(0);
+    if (k) {
+      const uint32_t need = f.step_base + k;
+      uint32_t late = 0;
+      if (threadIdx.x == 0) {
+        for (uint32_t spin = 0;
+             (int32_t)(__hip_atomic_load(f.done + s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - need) < 0;) {
+          __builtin_amdgcn_s_sleep(2);
+          if (++spin > (1u << 22)) {
+            late = 1;
+            break;
+          }
+        }
+      }
+      if (__builtin_amdgcn_readfirstlane((int)late) && threadIdx.x == 0) {
+        atomicOr(&f.stats[kStErr], (unsigned long long)kErrHandoff);
+        if (f.err_host)
+          __hip_atomic_store(f.err_host, (uint64_t)kErrHandoff, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+      }
+    }
+    const uint32_t next = sim_source<false, kHeapCap, kModeHandoff>(desc_window(desc, k), s, t, lds,
+                                                            f.persistent ? f.ticket : nullptr, f.ticket_base);
+    __asm__ volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every hand-off store written through
+    if (threadIdx.x == 0)
+      __hip_atomic_store(f.done + s, f.step_base + k + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (!f.persistent) break;  // one ticket per workgroup: the dispatcher interleaves other streams' work
+    t = next;
+  }
+}
+
+// Groups of up to kFuseMaxSharded windows (the sharded groups, a cap of 8 or less, short last groups)
+// keep the form that reads the windows' arguments from the kernel-argument segment, whose address
+// costs no register and no load: the same windows through the device buffer ran 1-2 % slower
+// (profiles/LOG.md, "Long fused groups").  No k_fused_desc launch either.
 struct FusedSim {
-  SimArgs w[kFuseMax];  // window k's arguments (tables and state shared, step fields its own)
+  SimArgs w[kFuseMaxSharded];  // window k's arguments (tables and state shared, step fields its own)
 };
 // Window k's arguments read in place in the kernel-argument segment (scalar loads of invariant
 // memory: re-read when needed instead of held in spilled SGPRs).
@@ -1864,15 +1943,7 @@ __device__ __forceinline__ const SimArgs& kernarg_window(uint32_t k) {
   return *(const SimArgs*)ka;
 }
 
-// WINDOW-MAJOR (the default): ticket t is window t / S of the (t mod S)-th source in dispatch
-// order; a ticket of window k > 0 polls its source's completion word until window k - 1 has stored
-// it, and the queue crosses HBM between the windows (the sc1 hand-off above).  Every claimed ticket
-// is held by a resident workgroup and waits only for a lower ticket, so the lowest unfinished ticket
-// can always run: no deadlock; the wait is bounded anyway (kErrHandoff, then the host reports -EIO).
-// Tickets interleave the windows of all sources at a granularity of one source-window, which keeps
-// the launch's tail short (a source-major form, each source's windows back to back with its queue
-// resident in LDS, was bit-exact but slower: DESIGN.md §5.2).
-__global__ __launch_bounds__(kWave, 3) void k_sim_fused(FusedSim fs, FusedArgs f) {
+__global__ __launch_bounds__(kWave, 3) void k_sim_fused8(FusedSim fs, FusedArgs8 f) {
   const SimArgs& a0 = fs.w[0];
   __shared__ SimLdsT<kHeapCap> lds;
   const uint32_t total = f.n_win * a0.n_src;
@@ -1914,6 +1985,7 @@ __global__ __launch_bounds__(kWave, 3) void k_sim_fused(FusedSim fs, FusedArgs f
     t = next;
   }
 }
+
 
 constexpr uint32_t kSparseQ = 4;  // chunks of 64 queued items / ring entries held in registers
 constexpr uint32_t kFifoRounds = 4;  // FIFO sources: items served per step, in rounds of 64
@@ -5108,24 +5180,42 @@ void launch_sim(const SimArgs& a, uint32_t n_wg, hipStream_t st) {
   else hipLaunchKernelGGL(k_sim, dim3(n_wg), dim3(kWave), 0, st, a);  // n_wg = ceil(n_src / kSpw)
 }
 
-void launch_sim_fused(const SimArgs& a, const FusedArgs& f, uint32_t n_wg, hipStream_t st) {
+int launch_sim_fused(const SimArgs& a, const FusedArgs& f, uint32_t n_wg, hipStream_t st) {
   const uint32_t total = f.n_win * a.n_src;  // tickets
-  FusedSim fs;
-  for (uint32_t k = 0; k < kFuseMax; ++k) {
-    fs.w[k] = a;
-    if (k >= f.n_win) continue;
-    const FusedWindow& w = f.w[k];
-    fs.w[k].off = w.off;
-    fs.w[k].in = w.in;
-    fs.w[k].verdict = w.verdict;
-    fs.w[k].emit = w.emit;
-    fs.w[k].emit_n = w.emit_n;
-    fs.w[k].dst_cnt = w.dst_cnt;
-    fs.w[k].t0_ns = w.t0_ns;
-    fs.w[k].horizon_ns = w.horizon_ns;
-  }
+  if (!total || f.n_win > kFuseMax) return -EINVAL;
   const dim3 grid(f.persistent && n_wg < total ? n_wg : total);
-  hipLaunchKernelGGL(k_sim_fused, grid, dim3(kWave), 0, st, fs, f);
+  if (f.n_win <= kFuseMaxSharded) {  // the windows' arguments in the kernel-argument segment
+    FusedSim fs;
+    FusedArgs8 f8{};
+    for (uint32_t k = 0; k < kFuseMaxSharded; ++k) {
+      fs.w[k] = a;
+      if (k >= f.n_win) continue;
+      const FusedWindow& w = f8.w[k] = f.w[k];
+      fs.w[k].off = w.off;
+      fs.w[k].in = w.in;
+      fs.w[k].verdict = w.verdict;
+      fs.w[k].emit = w.emit;
+      fs.w[k].emit_n = w.emit_n;
+      fs.w[k].dst_cnt = w.dst_cnt;
+      fs.w[k].t0_ns = w.t0_ns;
+      fs.w[k].horizon_ns = w.horizon_ns;
+    }
+    f8.n_win = f.n_win;
+    f8.step_base = f.step_base;
+    f8.ticket_base = f.ticket_base;
+    f8.ticket = f.ticket;
+    f8.done = f.done;
+    f8.prio_n = f.prio_n;
+    f8.persistent = f.persistent;
+    hipLaunchKernelGGL(k_sim_fused8, grid, dim3(kWave), 0, st, fs, f8);
+    return 0;
+  }
+  if (!f.desc) return -EINVAL;
+  hipLaunchKernelGGL(k_fused_desc, dim3(f.n_win), dim3(kWave), 0, st, a, f);
+  const FusedCtl c{f.n_win, f.step_base, f.ticket_base, f.prio_n, f.persistent, a.n_src,
+                   f.ticket,  f.done,    a.order,       a.stats,  a.err_host};
+  hipLaunchKernelGGL(k_sim_fused, grid, dim3(kWave), 0, st, (const SimArgs*)f.desc, c);
+  return 0;
 }
 
 uint32_t sim_fused_resident() {

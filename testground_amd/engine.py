@@ -402,7 +402,7 @@ class CABIEngine:
         self._check(self._fn("step")(self._h, n_ticks), "step")
 
     def step_n(self, n_ticks: int, n_steps: int) -> None:
-        """n_steps windows of n_ticks (tgsim_step_n: generated windows run fused, up to eight per launch)."""
+        """n_steps windows of n_ticks (tgsim_step_n: generated windows run fused, up to TGSIM_FUSE per launch)."""
         self._check(self._fn("step_n")(self._h, n_ticks, n_steps), "step_n")
 
     def step_sim(self, n_ticks: int, bounds: Sequence[int], d_out: int, out_cap: int) -> np.ndarray:
