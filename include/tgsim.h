@@ -432,8 +432,9 @@ int64_t tgsim_gossip_times(void* engine, uint32_t peer, uint32_t n, uint32_t* ou
  *            tgsim_gen_ping fails with -EINVAL (tgsim_last_error names the tick), nothing is
  *            generated, and the error stays until the next tgsim_ping_init; the reports stay
  *            readable.
- * Single engine only (it must own every peer): replies are generated at the destination's shard, so
- * a sharded form can follow. */
+ * tgsim_ping_init arms a single engine that owns every peer; tgsim_ping_init_sharded (below) arms one
+ * engine per shard of a run spread over tgsim_comm_*: replies are generated at the destination's
+ * shard from the records it receives, so the sharded form needs no exchange of its own. */
 #define TGSIM_PING_NONE 0xFFFFFFFEu      /* targets[] entry: empty slot */
 typedef struct {
     uint32_t fanout;         /* target slots per peer, 1..64                              */
@@ -476,6 +477,59 @@ int64_t tgsim_ping_report(void* engine, tgsim_ping_summary* out, uint64_t* hist,
 /* The pair rows of peers [peer, peer + n), row-major [n][fanout] (an empty slot: sent 0, received 0);
  * returns the rows written, -ENOSPC when cap < n * fanout. */
 int64_t tgsim_ping_pairs(void* engine, uint32_t peer, uint32_t n, tgsim_ping_pair* out, size_t cap);
+
+/* ---- ping mesh over shards ------------------------------------------------------------------ */
+/* Arms the ping driver on an engine that owns peers [shard_begin, shard_end), which may be every
+ * peer.  `targets` is the WHOLE run's table [n_peers][fanout], the same on every shard: it is
+ * replicated like the peer tables, because a responder's shard validates a request against the
+ * requester's row, which it does not own (4 B x fanout per peer and shard: 32 MB at 1M peers with
+ * fanout 8).  Every field rule, -EINVAL text and -EBUSY rule of tgsim_ping_init holds, less the
+ * ownership test.  (engine, NULL, NULL) disarms, frees the state and drops a generated window of its
+ * own that is still pending (the window of a step the ranks refused, see the late rule);
+ * tgsim_ping_init(engine, NULL, NULL) disarms either form.
+ *
+ * Request, reply, receipt, order and loop are exactly those above.  What differs is where things
+ * happen:
+ *   Requests of peer s are generated by the shard that owns s (tgsim_gen_ping generates the owned
+ *            sources' rows and involves no collective).
+ *   Calendar an entry is made from a delivered request addressed to r at the shard that owns r, where
+ *            the exchange's delivery emits the record; it becomes r's reply there.
+ *   Receipt  a delivered reply addressed to q credits pair (q, k) at q's shard: each shard holds the
+ *            pair rows of its own peers only.
+ *   Counters dup_ignored and corrupt_ignored count at the shard that emits the record;
+ *            pending_replies is that shard's calendar.
+ * While armed through this call the closed steps are accepted: tgsim_comm_step, tgsim_comm_launch /
+ * tgsim_comm_finish and, underneath them, tgsim_step_sim, tgsim_step_sim_launch / _finish / _counts,
+ * tgsim_deliver / tgsim_deliver_async and tgsim_deliver_slotted_async with one window; tgsim_step on
+ * an engine that owns every peer gives the results of the unsharded form.  tgsim_comm_run,
+ * tgsim_step_sim_launch_slotted called directly and tgsim_step_sim_launch_slotted_n stay -EBUSY
+ * (pipelined or fused: they cannot be closed-loop), as do tgsim_submit, tgsim_gen_storm,
+ * tgsim_gossip_init and tgsim_flow_init; one generated window at a time, and none between
+ * tgsim_comm_launch and its tgsim_comm_finish (-EBUSY: the window's receipts come first).
+ *
+ * tgsim_ping_report gives THIS shard's summary and histogram.  Reports merge over the shards field by
+ * field: every field by sum, except min_ns by min and max_ns by max; hist by sum, bin by bin (a shard
+ * without a reply reports the neutral min_ns UINT64_MAX and max_ns 0).  tgsim_comm_ping_report does
+ * that on the device.  tgsim_ping_pairs takes global peer ids inside the shard (-EINVAL, naming both
+ * ranges, otherwise).
+ *
+ * The late rule across ranks.  A late receipt is seen by ONE rank's tgsim_gen_ping: it returns
+ * -EINVAL, generates nothing and changes no state, and the error stays, as above.  Host protocol:
+ * every rank calls tgsim_comm_step / tgsim_comm_launch for every window, even after its own
+ * generation failed.  With more than one rank the launch first agrees on the ranks' fault flags (one
+ * 8-byte max all-reduce on the exchange stream and one host wait per window); when any rank is late,
+ * EVERY rank's call returns -EINVAL, tgsim_last_error names the late rank and the tick, nothing is
+ * simulated, and the error stays on every rank until it re-arms (later calls fail at once, without a
+ * collective).  The reports stay readable.  A calendar overflow (-ENOSPC) is agreed the same way.
+ * With one rank nothing is exchanged for this. */
+int tgsim_ping_init_sharded(void* engine, const tgsim_ping* p, const uint32_t* targets);
+/* The WHOLE run's summary and histogram on every rank (collective, after tgsim_comm_init): each
+ * rank's local report is packed on the device into three runs (sums and histogram bins, min_ns,
+ * max_ns), reduced by three u64 all-reduces (sum, min, max) on the exchange stream and unpacked;
+ * no per-pair table crosses between GPUs or to the host.  Returns n_bins; -EINVAL without a
+ * communicator or when the driver is not armed through tgsim_ping_init_sharded, -ETIMEDOUT as the
+ * other collectives.  With one rank it equals tgsim_ping_report. */
+int64_t tgsim_comm_ping_report(void* engine, tgsim_ping_summary* out, uint64_t* hist, size_t hist_cap);
 
 /* ---- reliable transfers (windowed flows, per-segment ACKs and retransmission timers) --------- */
 /* "Send n_seg segments reliably from a to b" as a closed loop on the device: how

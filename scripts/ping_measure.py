@@ -5,11 +5,16 @@
   run    the device loop alone, for a kernel trace:
            rocprofv3 --kernel-trace --output-format csv -d DIR -o run -- python scripts/ping_measure.py run
   trace  per-kernel device time of the k_ping_* kernels in such a trace, beside their HBM floors
+  sharded  what a sharded window costs on one GPU: the device loop of the single engine (ping_init +
+         step) against the sharded form at one rank on the routed path (TGSIM_COMM_ROUTE1=1:
+         ping_init(sharded=True) + comm_step, the N > 1 step's own kernels, delivered in place), and
+         the time of one comm_ping_report.  One process, no retries: run it under a time limit.
 
 Every link 5 ms, lossless, unlimited; 16 probes per slot, one every 2,500 ticks; windows of 5,000
 ticks: a steady window offers 1.6 M probes and 1.6 M replies."""
 import csv
 import json
+import os
 import statistics
 import sys
 import time
@@ -19,7 +24,7 @@ import numpy as np
 
 sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
 from testground_amd import abi, network as nw, workloads as wl  # noqa: E402
-from testground_amd.engine import Engine  # noqa: E402
+from testground_amd.engine import Engine, comm_id  # noqa: E402
 
 N, FANOUT, WIN, LAT = 100_000, 8, 5_000, 5 * nw.Millisecond
 PING = dict(count=16, interval_ticks=2_500, length=64, start_tick=0, bin_ns=nw.Millisecond, n_bins=32)
@@ -46,6 +51,27 @@ def device_loop():
     return eng.ping_report(), t
 
 
+def routed_loop():
+    """The sharded form at one rank, routed (the environment is read by comm_init)."""
+    os.environ["TGSIM_COMM_ROUTE1"] = "1"
+    eng, t, rep_t = engine(abi.OPT_DISCARD_DELIVERIES), [], []
+    eng.comm_init(comm_id(), 0, 1)
+    eng.ping_init(wl.ping_targets_mesh(N, FANOUT, seed=9), sharded=True, **PING)
+    for w in range(WINDOWS):
+        eng.sync()
+        t0 = time.perf_counter()
+        eng.gen_ping(WIN)
+        eng.comm_step(WIN)
+        eng.sync()
+        t.append(time.perf_counter() - t0)
+    for _ in range(5):
+        eng.sync()
+        t0 = time.perf_counter()
+        rep = eng.comm_ping_report()
+        rep_t.append(time.perf_counter() - t0)
+    return rep, t, rep_t, eng.ping_report()
+
+
 def host_loop():
     eng, t = engine(0), []
     m = wl.PingModel(eng, PING, wl.ping_targets_mesh(N, FANOUT, seed=9))
@@ -70,6 +96,19 @@ def main():
                           "host_ms_per_window": [round(1e3 * x, 1) for x in th],
                           "device_steady_ms": round(1e3 * statistics.median(td[w] for w in STEADY), 3),
                           "host_steady_ms": round(1e3 * statistics.median(th[w] for w in STEADY), 1)}))
+    elif mode == "sharded":
+        dev, td = device_loop()
+        rep, tr, rep_t, local = routed_loop()
+        keys = ("pairs", "sent", "received", "sum_ns", "min_ns", "max_ns", "pairs_all", "pairs_none", "pending_replies")
+        same = all(dev[k] == rep[k] == local[k] for k in keys) and (dev["hist"] == rep["hist"]).all()
+        print(json.dumps({"peers": N, "fanout": FANOUT, "windows": WINDOWS, "reports_agree": bool(same),
+                          "received": int(rep["received"]), "sent": int(rep["sent"]),
+                          "single_ms_per_window": [round(1e3 * x, 3) for x in td],
+                          "routed_ms_per_window": [round(1e3 * x, 3) for x in tr],
+                          "single_steady_ms": round(1e3 * statistics.median(td[w] for w in STEADY), 3),
+                          "routed_steady_ms": round(1e3 * statistics.median(tr[w] for w in STEADY), 3),
+                          "comm_ping_report_ms": [round(1e3 * x, 3) for x in rep_t],
+                          "comm_ping_report_median_ms": round(1e3 * statistics.median(rep_t), 3)}))
     elif mode == "trace":
         per = {}
         for r in csv.DictReader(open(sys.argv[2])):

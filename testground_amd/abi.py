@@ -257,6 +257,7 @@ EXPORTS = [
     "tgsim_gossip_init", "tgsim_gen_gossip", "tgsim_gossip_reached", "tgsim_gossip_spread",
     "tgsim_gossip_times", "tgsim_metrics",
     "tgsim_ping_init", "tgsim_gen_ping", "tgsim_ping_report", "tgsim_ping_pairs",
+    "tgsim_ping_init_sharded", "tgsim_comm_ping_report",
     "tgsim_flow_init", "tgsim_gen_flow", "tgsim_flow_report", "tgsim_flow_rows",
     "tgsim_flow_init_cc", "tgsim_flow_cc_rows", "tgsim_flow_cc_report",
     "tgsim_flow_init_rto", "tgsim_flow_rto_rows", "tgsim_flow_rto_report",
@@ -337,6 +338,8 @@ def declare(lib: C.CDLL, prefix: str) -> None:
     f("gen_ping", C.c_int, vp, C.c_uint32)
     f("ping_report", C.c_int64, vp, C.POINTER(PingSummary), C.c_void_p, C.c_size_t)
     f("ping_pairs", C.c_int64, vp, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t)
+    f("ping_init_sharded", C.c_int, vp, C.POINTER(Ping), C.c_void_p)
+    f("comm_ping_report", C.c_int64, vp, C.POINTER(PingSummary), C.c_void_p, C.c_size_t)
     f("flow_init", C.c_int, vp, C.POINTER(Flow), C.c_void_p, C.c_uint64)
     f("gen_flow", C.c_int, vp, C.c_uint32)
     f("flow_report", C.c_int64, vp, C.POINTER(FlowSummary), C.c_void_p, C.c_size_t)

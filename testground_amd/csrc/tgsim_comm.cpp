@@ -51,6 +51,9 @@ constexpr size_t kRec = sizeof(tgsim_delivery);
 // profiles/r04/grids): turnover (one workgroup per ticket) 31.2-31.3 G pkt/s, 80 % 31.8-32.1, 90 %
 // 34.0-34.4, the whole grid 34.0-34.2.
 constexpr uint32_t kRoutedGridPct = 90;
+// tgsim_comm_ping_report's pinned block: the summary (11 words), the histogram, the sequence word
+constexpr size_t kPingHostWords = sizeof(tgsim_ping_summary) / sizeof(uint64_t) + kPingMaxBins + 1;
+static_assert(sizeof(tgsim_ping_summary) == 11 * sizeof(uint64_t), "k_ping_unpack writes 11 summary words");
 
 // librccl.so.1, loaded once per process (when torch has loaded it already, dlopen returns that
 // same instance, so one process never holds two RCCL runtimes).  The test build of this file
@@ -192,6 +195,12 @@ struct Comm {
   hipEvent_t ev_cnt = nullptr;  // after the last count all-to-all's publish (tells a fault from a slow step)
   uint64_t route1_cap[3] = {};  // TGSIM_COMM_ROUTE1: the capacity-sized chunk of out[j]
   uint64_t exchanged = 0, max_count = 0, slot_cap = 0;
+  // tgsim_comm_ping_report: the packed words on the device (kPingPackWords) and the reduced report in
+  // pinned memory (a tgsim_ping_summary, kPingMaxBins histogram words, the sequence word)
+  DevMem d_prep;
+  uint64_t* h_prep = nullptr;
+  uint64_t* dm_prep = nullptr;
+  uint64_t prep_seq = 0;
   bool launched = false;  // tgsim_comm_launch without its tgsim_comm_finish yet
   bool local = false;     // one rank, not TGSIM_COMM_ROUTE1: the single-shard step
 };
@@ -244,6 +253,8 @@ void comm_free(void* p) {
   for (auto& b : C->out) b.release();
   for (auto& b : C->in) b.release();
   C->d_cnt.release();
+  C->d_prep.release();
+  if (C->h_prep) (void)hipHostFree(C->h_prep);
   for (hipEvent_t e : C->ev_out)
     if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : C->ev_in)
@@ -341,6 +352,22 @@ int allreduce_u64(Comm* C, const void* dev_src, uint64_t* result, ncclRedOp_t op
   return 0;
 }
 
+// The sharded ping driver's late rule across ranks (include/tgsim.h): a late receipt (or a full
+// calendar) is seen by one rank's tgsim_gen_ping; before a window is launched the ranks agree on their
+// fault words with one 8-byte max all-reduce, so that every rank fails the window (nothing is simulated
+// and none waits for a peer that stopped).  The agreed word stays on every rank until it re-arms, and
+// is not exchanged again: every rank learned it in the same collective.  One rank: nothing to exchange.
+int ping_agree(Comm* C) {
+  bool agreed = false;
+  uint64_t word = engine_ping_fault(C->eng, C->rank, &agreed);
+  if (!agreed && C->nranks > 1) {
+    C->h_cnt[0] = word;
+    CHIP(hipMemcpyAsync(C->d_cnt.p, C->h_cnt, sizeof(uint64_t), hipMemcpyHostToDevice, C->xs));
+    CRC(allreduce_u64(C, C->d_cnt.p, &word, ncclMax));
+  }
+  return word ? engine_ping_fail_agreed(C->eng, word) : 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -349,7 +376,6 @@ int tgsim_step_n(void*, uint32_t, uint32_t);
 int tgsim_step_sim_launch(void*, uint32_t, uint32_t, const uint32_t*, void*, size_t);
 int tgsim_step_sim_counts(void*, uint64_t*);
 int tgsim_step_sim_launch_slotted_n(void*, uint32_t, uint32_t, uint32_t, const uint32_t*, void*, uint64_t, void*);
-int tgsim_step_sim_launch_slotted(void*, uint32_t, uint32_t, const uint32_t*, void*, uint64_t, void*);
 int tgsim_deliver_slotted_async(void*, const void*, uint32_t, uint64_t, void*);
 int tgsim_step_sim_release(void*);
 int tgsim_deliver_async(void*, const void*, size_t, void*);
@@ -464,9 +490,11 @@ int tgsim_comm_launch(void* e, uint32_t n_ticks) {
   if (C->timed_out) return -ETIMEDOUT;  // a collective never completed (tgsim_last_error says which)
   if (n_ticks == 0) return -EINVAL;
   if (C->launched) return engine_fail(e, -EBUSY, "comm_launch: the launched window is not finished (tgsim_comm_finish)");
-  if (engine_ping_armed(e)) return engine_fail(e, -EBUSY, "comm_launch: the ping driver is armed (single engine, tgsim_step)");
+  if (engine_ping_armed(e) && !engine_ping_sharded(e))
+    return engine_fail(e, -EBUSY, "comm_launch: the ping driver is armed (single engine, tgsim_step)");
   if (engine_flow_armed(e)) return engine_fail(e, -EBUSY, "comm_launch: the flow driver is armed (single engine, tgsim_step)");
   CHIP(hipSetDevice(C->dev));
+  if (engine_ping_sharded(e)) CRC(ping_agree(C));
   if (C->local) {  // one rank owns every destination: nothing to route or move, so the window
                          // is the single-shard step with its asynchronous local delivery (the count
                          // of routed records is never read back: no host round trip)
@@ -482,8 +510,7 @@ int tgsim_comm_launch(void* e, uint32_t n_ticks) {
                          // from its count header, so the host never waits for the routing
     CRC(grow(C, C->out[j], C->ev_out[j], C->out_busy[j], (static_cast<size_t>(cap) + 1) * kRec));
     if (C->out_busy[j]) CRC(tgsim_wait_event(e, C->ev_out[j]));
-    CRC(tgsim_step_sim_launch_slotted(e, n_ticks, 1, C->bounds, C->out[j].p, static_cast<uint64_t>(cap),
-                                      C->ev_routed[j]));
+    CRC(engine_step_sim_launch_route1(e, n_ticks, C->bounds, C->out[j].p, static_cast<uint64_t>(cap), C->ev_routed[j]));
     C->route1_cap[j] = static_cast<uint64_t>(cap);
     C->launched = true;
     return 0;
@@ -561,7 +588,10 @@ int tgsim_comm_run(void* e, uint32_t n_ticks, uint32_t n_steps, uint32_t fuse, u
   if (C->timed_out) return -ETIMEDOUT;  // a collective never completed (tgsim_last_error says which)
   if (n_ticks == 0 || fuse == 0 || fuse > kFuseMaxSharded) return -EINVAL;
   if (C->launched) return engine_fail(e, -EBUSY, "comm_run: a launched window is not finished (tgsim_comm_finish)");
-  if (engine_ping_armed(e)) return engine_fail(e, -EBUSY, "comm_run: the ping driver is armed (single engine, tgsim_step)");
+  if (engine_ping_armed(e))
+    return engine_fail(e, -EBUSY, engine_ping_sharded(e)
+                                      ? "comm_run: the ping driver is armed (a closed loop: tgsim_comm_step, window by window)"
+                                      : "comm_run: the ping driver is armed (single engine, tgsim_step)");
   if (engine_flow_armed(e)) return engine_fail(e, -EBUSY, "comm_run: the flow driver is armed (single engine, tgsim_step)");
   if (!n_steps) return 0;
   CHIP(hipSetDevice(C->dev));
@@ -652,6 +682,48 @@ int tgsim_comm_barrier(void* e, uint32_t state, uint64_t target) {
   uint64_t sum = 0;
   CRC(allreduce_u64(C, static_cast<const uint64_t*>(table) + state, &sum, ncclSum));
   return sum >= target ? 1 : 0;
+}
+
+int64_t tgsim_comm_ping_report(void* e, tgsim_ping_summary* out, uint64_t* hist, size_t hist_cap) {
+  Comm* C = comm_of(e);
+  if (!C) return e ? engine_fail(e, -EINVAL, "comm_ping_report: no communicator (tgsim_comm_init)") : -EINVAL;
+  if (C->timed_out) return -ETIMEDOUT;  // a collective never completed (tgsim_last_error says which)
+  if (!engine_ping_sharded(e))
+    return engine_fail(e, -EINVAL, "comm_ping_report: the sharded ping driver is not armed (tgsim_ping_init_sharded)");
+  if (!out) return engine_fail(e, -EINVAL, "comm_ping_report: no summary buffer");
+  if (C->launched) return engine_fail(e, -EBUSY, "comm_ping_report: the launched window is not finished (tgsim_comm_finish)");
+  CHIP(hipSetDevice(C->dev));
+  const unsigned long long *res = nullptr, *ctr = nullptr;
+  uint32_t cal_word = 0, nb = 0;
+  CRC(engine_ping_report_dev(e, &res, &ctr, &cal_word, &nb, C->ev_sig));  // k_ping_report's words, on the device
+  if (nb && (!hist || hist_cap < nb))
+    return fail(C, -EINVAL, "comm_ping_report: %zu histogram words for %u bins", hist ? hist_cap : size_t{0}, nb);
+  if (!C->h_prep) {
+    CHIP(hipHostMalloc(reinterpret_cast<void**>(&C->h_prep), kPingHostWords * sizeof(uint64_t),
+                       hipHostMallocCoherent | hipHostMallocMapped));
+    memset(C->h_prep, 0, kPingHostWords * sizeof(uint64_t));
+    CHIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&C->dm_prep), C->h_prep, 0));
+    CHIP(C->d_prep.ensure(kPingPackWords * sizeof(uint64_t)));
+  }
+  // packed as three runs -- sums and histogram bins, min_ns, max_ns -- and reduced in place, one
+  // all-reduce per operator; the unpack publishes the summary and the histogram to pinned memory
+  unsigned long long* pk = reinterpret_cast<unsigned long long*>(C->d_prep.p);
+  const size_t n_sum = kPingPackSums + nb;
+  CHIP(hipStreamWaitEvent(C->xs, C->ev_sig, 0));
+  launch_ping_pack(res, ctr, cal_word, nb, pk, C->xs);
+  CHIP(hipGetLastError());
+  if (C->nranks > 1) {
+    CNCCL(C->R->AllReduce(pk, pk, n_sum, ncclUint64, ncclSum, C->nc, C->xs));
+    CNCCL(C->R->AllReduce(pk + n_sum, pk + n_sum, 1, ncclUint64, ncclMin, C->nc, C->xs));
+    CNCCL(C->R->AllReduce(pk + n_sum + 1, pk + n_sum + 1, 1, ncclUint64, ncclMax, C->nc, C->xs));
+  }
+  launch_ping_unpack(pk, nb, C->dm_prep, ++C->prep_seq, C->xs);
+  CHIP(hipGetLastError());
+  CHIP(hipEventRecord(C->ev_red, C->xs));
+  CRC(wait_word(C, C->h_prep + kPingHostWords - 1, C->prep_seq, C->ev_red, "ping report all-reduce"));
+  memcpy(out, C->h_prep, sizeof *out);
+  for (uint32_t b = 0; b < nb; ++b) hist[b] = C->h_prep[11 + b];
+  return nb;
 }
 
 int tgsim_comm_info(void* e, tgsim_comm_info_t* out) {

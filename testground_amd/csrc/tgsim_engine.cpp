@@ -460,7 +460,15 @@ struct tgsim_engine_s {
   bool ping_late = false;        // sticky until tgsim_ping_init: a calendar entry preceded a generated window
   uint64_t ping_late_tick = 0;
   tgsim_ping ping{};
-  uint64_t ping_pairs = 0;       // non-empty slots
+  uint64_t ping_pairs = 0;       // non-empty slots of the owned peers
+  // tgsim_ping_init_sharded (an engine that may own part of the peers): the closed steps of the exchange
+  // are accepted.  ping_answered: the slots of ANY peer whose target this engine owns, i.e. the pairs
+  // whose requests make calendar entries here (the calendar's growth bound; the unsharded form keeps
+  // its bound of every pair).
+  bool ping_sharded = false;
+  uint64_t ping_answered = 0;
+  uint64_t ping_nospc = 0;       // entries that found the calendar full (sticky, as the device counter is)
+  uint64_t ping_agreed = 0;      // the ranks' agreed fault word (0: none)
   uint32_t ping_cur = 0;         // the calendar buffer being appended to
   uint64_t ping_kept = 0;        // its entries behind the last generation (those not yet due then)
   uint64_t ping_appended = 0;    // entries made since tgsim_ping_init, as of the last generation
@@ -1512,6 +1520,9 @@ void ping_release(Eng* E) {
   E->d_ptmp.release();
   E->ping_on = false;
   E->ping_late = false;
+  E->ping_sharded = false;
+  E->ping_nospc = 0;
+  E->ping_agreed = 0;
 }
 
 PingArgs ping_args(Eng* E, uint64_t win0, uint32_t n_ticks) {
@@ -1525,6 +1536,8 @@ PingArgs ping_args(Eng* E, uint64_t win0, uint32_t n_ticks) {
   a.cal_cap = std::min(E->d_pcal[0].cap, E->d_pcal[1].cap);
   a.cal_cur = E->ping_cur;
   a.n_peers = E->N;
+  a.first = E->o.shard_begin;  // (tgsim_ping_init: 0 and every peer)
+  a.n_own = E->S;
   a.fanout = E->ping.fanout;
   a.count = E->ping.count;
   a.interval = E->ping.interval_ticks;
@@ -1573,6 +1586,8 @@ FlowArgs flow_args(Eng* E, uint64_t win0, uint32_t n_ticks) {
   a.cal_cap = std::min(E->d_pcal[0].cap, E->d_pcal[1].cap);
   a.cal_cur = E->ping_cur;
   a.n_peers = E->N;
+  a.first = 0;  // (the flow driver's engine owns every peer)
+  a.n_own = E->N;
   a.len = E->flow.ack_len;
   a.n_bins = E->flow.n_bins;
   a.tick_ns = E->o.tick_ns;
@@ -2204,6 +2219,52 @@ void engine_shard(void* e, uint32_t* begin, uint32_t* end) {
 int engine_fail(void* e, int code, const char* msg) { return as_eng(e)->fail(code, "%s", msg); }
 void engine_persist_routed(void* e, uint32_t pct) { as_eng(e)->routed_pct = pct; }
 bool engine_ping_armed(void* e) { return as_eng(e)->ping_on; }
+bool engine_ping_sharded(void* e) { return as_eng(e)->ping_on && as_eng(e)->ping_sharded; }
+
+uint64_t engine_ping_fault(void* e, int rank, bool* agreed) {
+  Eng* E = as_eng(e);
+  *agreed = E->ping_agreed != 0;
+  if (E->ping_agreed) return E->ping_agreed;
+  const uint64_t r = static_cast<uint64_t>(rank) & 15u;
+  if (E->ping_nospc) return kPingFaultNospc << 62 | std::min<uint64_t>(E->ping_nospc, (1ull << 50) - 1) << 4 | r;
+  if (E->ping_late) return kPingFaultLate << 62 | E->ping_late_tick << 4 | r;  // (ticks stay below 2^31)
+  return 0;
+}
+
+// The text and code of an agreed fault word (of this or another rank).
+static int ping_fail_word(Eng* E, uint64_t word) {
+  const unsigned long long v = word >> 4 & ((1ull << 50) - 1), r = word & 15u;
+  if (word >> 62 == kPingFaultNospc)
+    return E->fail(-ENOSPC, "ping: %llu replies found the calendar full on rank %llu (tgsim_ping_init_sharded starts again)", v, r);
+  return E->fail(-EINVAL, "ping: a reply due at tick %llu preceded a window on rank %llu (every rank starts again "
+                          "with tgsim_ping_init_sharded)", v, r);
+}
+
+int engine_ping_fail_agreed(void* e, uint64_t word) {
+  Eng* E = as_eng(e);
+  E->ping_agreed = word;
+  if (word >> 62 == kPingFaultLate && !E->ping_late) {  // this rank's own generation fails from now on, too
+    E->ping_late = true;
+    E->ping_late_tick = word >> 4 & 0xFFFFFFFFull;
+  }
+  return ping_fail_word(E, word);
+}
+
+int engine_ping_report_dev(void* e, const unsigned long long** res, const unsigned long long** ctr, uint32_t* cal_word,
+                           uint32_t* n_bins, hipEvent_t ev) {
+  Eng* E = as_eng(e);
+  HIPCHK(hipSetDevice(E->dev));
+  int rc = sync_stream(E);  // the receipts of the last delivery are folded on the delivery stream
+  if (rc) return rc;
+  launch_ping_report(ping_args(E, 0, 0), E->d_pres.p, E->st);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(ev, E->st));
+  *res = E->d_pres.p;
+  *ctr = E->d_pctr.p;
+  *cal_word = E->ping_cur;
+  *n_bins = E->ping.n_bins;
+  return 0;
+}
 bool engine_flow_armed(void* e) { return as_eng(e)->flow_on; }
 const uint64_t* engine_route_counts_dev(void* e) {
   Eng* E = as_eng(e);
@@ -2839,7 +2900,8 @@ static int ping_grow_calendar(Eng* E, uint64_t need, uint64_t live) {
   return 0;
 }
 
-int tgsim_ping_init(void* e, const tgsim_ping* p, const uint32_t* targets) {
+// tgsim_ping_init and tgsim_ping_init_sharded: the same rules, less the ownership test of the first.
+static int ping_arm(void* e, const tgsim_ping* p, const uint32_t* targets, bool sharded) {
   Eng* E = as_eng(e);
   if (!E) return -EINVAL;
   HIPCHK(hipSetDevice(E->dev));
@@ -2847,11 +2909,16 @@ int tgsim_ping_init(void* e, const tgsim_ping* p, const uint32_t* targets) {
     if (targets) return E->fail(-EINVAL, "ping: a target table without parameters");
     int rc = sync_stream(E);
     if (rc) return rc;
-    if (E->ping_on) ping_release(E);  // (an armed flow driver owns the calendar: it stays)
+    if (E->ping_on) {  // (an armed flow driver owns the calendar: it stays)
+      // a window of the sharded form still pending belongs to a step the ranks refused (a late receipt
+      // on another rank): it goes with the driver, or the rank could never generate again
+      if (E->ping_sharded) drop_gen(E);
+      ping_release(E);
+    }
     return 0;
   }
   if (!targets) return E->fail(-EINVAL, "ping: no target table");
-  if (E->S != E->N)
+  if (!sharded && E->S != E->N)
     return E->fail(-EINVAL, "ping: this engine owns peers [%u, %u) of %u (the driver needs one engine for every peer)",
                    E->o.shard_begin, E->o.shard_end, E->N);
   if (p->fanout == 0 || p->fanout > 64) return E->fail(-EINVAL, "ping: fanout %u outside 1..64", p->fanout);
@@ -2869,16 +2936,20 @@ int tgsim_ping_init(void* e, const tgsim_ping* p, const uint32_t* targets) {
                    static_cast<unsigned long long>(E->now_tick));
   if (p->start_tick + static_cast<uint64_t>(p->count) * p->interval_ticks >= (1ull << 31))
     return E->fail(-EINVAL, "ping: the schedule ends beyond tick 2^31");
-  const uint64_t n_slots = static_cast<uint64_t>(E->N) * p->fanout;
-  std::vector<uint32_t> slots(E->N, 0);
-  uint64_t pairs = 0;
+  // n_slots: the whole run's table; own_slots: the owned peers' part of it (the pair table's size)
+  const uint64_t n_slots = static_cast<uint64_t>(E->N) * p->fanout, own_slots = static_cast<uint64_t>(E->S) * p->fanout;
+  const uint32_t b0 = E->o.shard_begin, b1 = E->o.shard_end;
+  std::vector<uint32_t> slots(E->S, 0);
+  uint64_t pairs = 0, answered = 0;
   for (uint64_t i = 0; i < n_slots; ++i) {
     const uint32_t t = targets[i], s = static_cast<uint32_t>(i / p->fanout);
     if (t == TGSIM_PING_NONE) continue;
     if (t == s || (t != TGSIM_EXTERNAL && t >= E->N))
       return E->fail(-EINVAL, "ping: targets[%u][%u] = %u is %s", s, static_cast<uint32_t>(i % p->fanout), t,
                      t == s ? "the peer itself" : "out of range");
-    ++slots[s];
+    answered += t >= b0 && t < b1;
+    if (s < b0 || s >= b1) continue;
+    ++slots[s - b0];
     ++pairs;
   }
   int rc = sync_stream(E);  // a re-init: the last delivery's receipts may still run
@@ -2893,21 +2964,25 @@ int tgsim_ping_init(void* e, const tgsim_ping* p, const uint32_t* targets) {
   ping_release(E);
   E->ping = *p;
   E->ping_pairs = pairs;
+  E->ping_sharded = sharded;
+  // the calendar's growth bound counts one entry per probe of these pairs: sharded, the pairs whose
+  // responder this engine owns (only their requests are delivered here); unsharded, every pair as before
+  E->ping_answered = sharded ? answered : pairs;
   E->ping_cur = 0;
   E->ping_kept = 0;
   E->ping_appended = 0;
   HIPCHK(E->d_ptgt.ensure_exact(n_slots));
-  HIPCHK(E->d_pslots.ensure_exact(E->N));
-  HIPCHK(E->d_pcur.ensure_exact(E->N));
-  HIPCHK(E->d_ppair.ensure_exact(n_slots));
+  HIPCHK(E->d_pslots.ensure_exact(E->S));
+  HIPCHK(E->d_pcur.ensure_exact(E->S));
+  HIPCHK(E->d_ppair.ensure_exact(std::max<uint64_t>(own_slots, 1)));
   HIPCHK(E->d_phist.ensure_exact(static_cast<size_t>(kPingReplicas) * kPingMaxBins));
   HIPCHK(E->d_pctr.ensure_exact(kPingCtrWords));
   HIPCHK(E->d_pres.ensure_exact(8 + kPingMaxBins));
   // one entry per pair to start with: a probe in flight per pair; tgsim_gen_ping grows it for more
-  HIPCHK(E->d_pcal[0].ensure_exact(std::max<uint64_t>(pairs, 1024)));
-  HIPCHK(E->d_pcal[1].ensure_exact(std::max<uint64_t>(pairs, 1024)));
+  HIPCHK(E->d_pcal[0].ensure_exact(std::max<uint64_t>(E->ping_answered, 1024)));
+  HIPCHK(E->d_pcal[1].ensure_exact(std::max<uint64_t>(E->ping_answered, 1024)));
   HIPCHK(hipMemcpy(E->d_ptgt.p, targets, sizeof(uint32_t) * n_slots, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(E->d_pslots.p, slots.data(), sizeof(uint32_t) * E->N, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(E->d_pslots.p, slots.data(), sizeof(uint32_t) * E->S, hipMemcpyHostToDevice));
   launch_ping_init(ping_args(E, 0, 0), E->st);
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(E->st));
@@ -2916,12 +2991,22 @@ int tgsim_ping_init(void* e, const tgsim_ping* p, const uint32_t* targets) {
   return 0;
 }
 
+int tgsim_ping_init(void* e, const tgsim_ping* p, const uint32_t* targets) { return ping_arm(e, p, targets, false); }
+
+int tgsim_ping_init_sharded(void* e, const tgsim_ping* p, const uint32_t* targets) {
+  return ping_arm(e, p, targets, true);
+}
+
 int tgsim_gen_ping(void* e, uint32_t n_ticks) {
   Eng* E = as_eng(e);
   if (!E || n_ticks == 0 || n_ticks > 65536) return -EINVAL;
   if (!E->ping_on) return E->fail(-EINVAL, "ping: the driver is not armed (tgsim_ping_init)");
   if (!E->staged.empty()) return E->fail(-EBUSY, "host packets already pending for the next step");
   if (!E->gen_q.empty()) return E->fail(-EBUSY, "ping: a generated window is pending (one window at a time)");
+  // (sharded: between tgsim_comm_launch and tgsim_comm_finish the window's delivery, and with it its
+  // receipts, is not enqueued yet: ev_ping below would not cover it)
+  if (E->route_n) return E->fail(-EBUSY, "ping: a launched step is not finished (its receipts come first)");
+  if (E->ping_agreed) return ping_fail_word(E, E->ping_agreed);
   if (E->ping_late)
     return E->fail(-EINVAL, "ping: a reply due at tick %llu preceded an earlier window (tgsim_ping_init starts again)",
                    static_cast<unsigned long long>(E->ping_late_tick));
@@ -2953,6 +3038,7 @@ int tgsim_gen_ping(void* e, uint32_t n_ticks) {
   E->ping_kept = cal_n;
   if (c[kPcOverflow]) {
     (void)retire_gen(E, std::move(w));
+    E->ping_nospc = c[kPcOverflow];
     return E->fail(-ENOSPC, "ping: %llu replies found the calendar full", static_cast<unsigned long long>(c[kPcOverflow]));
   }
   if (c[kPcLate] != ~0ull) {  // nothing was written: the calendar and the pair table stay as they are
@@ -2965,7 +3051,7 @@ int tgsim_gen_ping(void* e, uint32_t n_ticks) {
   }
   // the calendar until the next generation: what stays, plus a reply for every probe offered by the
   // end of this window that has none yet
-  const uint64_t offered = E->ping_pairs * a.j_hi;
+  const uint64_t offered = E->ping_answered * a.j_hi;
   rc = ping_grow_calendar(E, cal_n + (offered > E->ping_appended ? offered - E->ping_appended : 0), cal_n);
   if (!rc) rc = E->hip(w.in.ensure(total ? total : 1), "generated window");
   if (!rc) rc = E->hip(E->d_ptmp.ensure(total ? total : 1), "generated window");
@@ -3023,6 +3109,9 @@ int64_t tgsim_ping_pairs(void* e, uint32_t peer, uint32_t n, tgsim_ping_pair* ou
   if (!E->ping_on) return E->fail(-EINVAL, "ping_pairs: the ping driver is not armed (tgsim_ping_init)");
   if (peer > E->N || n > E->N - peer)
     return E->fail(-EINVAL, "ping_pairs: peers [%u, %llu) outside [0, %u)", peer, static_cast<unsigned long long>(peer) + n, E->N);
+  if (peer < E->o.shard_begin || static_cast<uint64_t>(peer) + n > E->o.shard_end)
+    return E->fail(-EINVAL, "ping_pairs: peers [%u, %llu) outside this shard's [%u, %u)", peer,
+                   static_cast<unsigned long long>(peer) + n, E->o.shard_begin, E->o.shard_end);
   const size_t rows = static_cast<size_t>(n) * E->ping.fanout;
   if (cap < rows) return E->fail(-ENOSPC, "ping_pairs: %zu rows for %zu", cap, rows);
   if (rows && !out) return E->fail(-EINVAL, "ping_pairs: no output buffer");
@@ -3031,7 +3120,8 @@ int64_t tgsim_ping_pairs(void* e, uint32_t peer, uint32_t n, tgsim_ping_pair* ou
   if (rc) return rc;
   if (!rows) return 0;
   HIPCHK(E->d_prows.ensure(rows));
-  launch_ping_pairs(ping_args(E, 0, 0), static_cast<uint64_t>(peer) * E->ping.fanout, rows, E->d_prows.p, E->st);
+  launch_ping_pairs(ping_args(E, 0, 0), static_cast<uint64_t>(peer - E->o.shard_begin) * E->ping.fanout, rows, E->d_prows.p,
+                    E->st);
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpyAsync(out, E->d_prows.p, sizeof(tgsim_ping_pair) * rows, hipMemcpyDeviceToHost, E->st));
   HIPCHK(hipStreamSynchronize(E->st));
@@ -3509,7 +3599,8 @@ int tgsim_step_sim_launch(void* e, uint32_t n_ticks, uint32_t n_ranks, const uin
   if (!E || n_ticks == 0 || n_ranks == 0 || n_ranks > 8 || !bounds || (!d_out && out_cap)) return -EINVAL;
   if (bounds[0] != 0 || bounds[n_ranks] != E->N) return E->fail(-EINVAL, "rank bounds must cover [0, n_peers)");
   if (E->route_n == Eng::kRouteSlots) return E->fail(-EBUSY, "two launched steps are not finished yet");
-  if (E->ping_on) return E->fail(-EBUSY, "%s: the ping driver is armed (tgsim_ping_init(engine, NULL, NULL) disarms it)", "step_sim_launch");
+  if (E->ping_on && !E->ping_sharded)
+    return E->fail(-EBUSY, "%s: the ping driver is armed (tgsim_ping_init(engine, NULL, NULL) disarms it)", "step_sim_launch");
   if (E->flow_on) return E->fail(-EBUSY, "%s: the flow driver is armed (tgsim_flow_init(engine, NULL, NULL, 0) disarms it)", "step_sim_launch");
   HIPCHK(hipSetDevice(E->dev));
   int rc = run_sim(E, n_ticks);
@@ -3531,19 +3622,27 @@ int tgsim_step_sim_counts(void* e, uint64_t* counts) {
   return route_finish(E, counts, false);
 }
 
-int tgsim_step_sim_launch_slotted(void* e, uint32_t n_ticks, uint32_t n_ranks, const uint32_t* bounds, void* d_out,
-                                  uint64_t slot_cap, void* routed_event) {
+// route1: the exchange's one-rank routed window (engine_step_sim_launch_route1), a closed step like
+// tgsim_step_sim_launch, which the sharded ping driver accepts; the public call is the pipelined run's.
+static int step_sim_launch_slotted(void* e, uint32_t n_ticks, uint32_t n_ranks, const uint32_t* bounds, void* d_out,
+                                   uint64_t slot_cap, void* routed_event, bool route1) {
   Eng* E = as_eng(e);
   if (!E || n_ticks == 0 || n_ranks == 0 || n_ranks > 8 || !bounds || !d_out || slot_cap == 0) return -EINVAL;
   if (bounds[0] != 0 || bounds[n_ranks] != E->N) return E->fail(-EINVAL, "rank bounds must cover [0, n_peers)");
   if (E->route_n == Eng::kRouteSlots) return E->fail(-EBUSY, "two launched steps are not released yet");
-  if (E->ping_on) return E->fail(-EBUSY, "%s: the ping driver is armed (tgsim_ping_init(engine, NULL, NULL) disarms it)", "step_sim_launch_slotted");
+  if (E->ping_on && !(route1 && E->ping_sharded))
+    return E->fail(-EBUSY, "%s: the ping driver is armed (tgsim_ping_init(engine, NULL, NULL) disarms it)", "step_sim_launch_slotted");
   if (E->flow_on) return E->fail(-EBUSY, "%s: the flow driver is armed (tgsim_flow_init(engine, NULL, NULL, 0) disarms it)", "step_sim_launch_slotted");
   HIPCHK(hipSetDevice(E->dev));
   int rc = run_sim(E, n_ticks);
   if (rc) return rc;
   return route_launch(E, n_ranks, bounds, static_cast<tgsim_delivery*>(d_out), n_ranks * (slot_cap + 1), slot_cap,
                       static_cast<hipEvent_t>(routed_event));
+}
+
+int tgsim_step_sim_launch_slotted(void* e, uint32_t n_ticks, uint32_t n_ranks, const uint32_t* bounds, void* d_out,
+                                  uint64_t slot_cap, void* routed_event) {
+  return step_sim_launch_slotted(e, n_ticks, n_ranks, bounds, d_out, slot_cap, routed_event, false);
 }
 
 int tgsim_step_sim_launch_slotted_n(void* e, uint32_t n_ticks, uint32_t n_win, uint32_t n_ranks,
@@ -3956,3 +4055,12 @@ int64_t tgsim_host_compile_rules(const tgsim_rule* rules, size_t n, uint32_t* ou
 }
 
 }  // extern "C"
+
+namespace tgsim {
+
+int engine_step_sim_launch_route1(void* e, uint32_t n_ticks, const uint32_t* bounds, void* d_out, uint64_t slot_cap,
+                                  void* routed_event) {
+  return step_sim_launch_slotted(e, n_ticks, 1, bounds, d_out, slot_cap, routed_event, true);
+}
+
+}  // namespace tgsim

@@ -337,7 +337,10 @@ struct GossipSpreadArgs {
   uint32_t bin_ticks, bin_rcp, n_bins;  // bin_rcp = fastmod_rcp(bin_ticks); n_bins 0: no histogram
 };
 
-// Ping mesh driver (tgsim_ping_*) of an engine that owns every peer.
+// Ping mesh driver (tgsim_ping_*).  An engine armed through tgsim_ping_init owns every
+// peer; tgsim_ping_init_sharded arms one that owns [first, first + n_own): the target table is the whole
+// run's, everything else (pair table, slot counts, row cursors, the generated window's offsets) is
+// indexed by owned peer.
 constexpr uint32_t kPingMaxBins = 256;
 constexpr uint32_t kPingReplicas = 8;  // RTT histogram tables the workgroups' flushes are spread over
 // A reply waiting for its tick (16 B): made by k_ping_recv from a delivered request, consumed by the
@@ -361,8 +364,8 @@ enum PingCtr {
   kPingCtrWords = 8
 };
 struct PingArgs {
-  const uint32_t* targets;   // [n_peers][fanout]
-  tgsim_ping_pair* pairs;    // [n_peers][fanout]; `sent` is filled in by the readers
+  const uint32_t* targets;   // [n_peers][fanout], the whole run's
+  tgsim_ping_pair* pairs;    // [n_own][fanout]; `sent` is filled in by the readers
   unsigned long long* hist;  // [kPingReplicas][kPingMaxBins]
   unsigned long long* ctr;   // [kPingCtrWords]
   PingCal* cal;              // the calendar being appended to / read
@@ -370,6 +373,7 @@ struct PingArgs {
   uint64_t cal_cap;          // entries either calendar buffer holds
   uint32_t cal_cur;          // 0 / 1: which counter belongs to `cal`
   uint32_t n_peers, fanout, count, interval, len, n_bins;
+  uint32_t first, n_own;     // the owned peers [first, first + n_own); a whole-peer engine: 0, n_peers
   uint64_t start, tick_ns, bin_ns;
   // generation of the window [win0, win0 + n_ticks): its scheduled probes are j_lo <= j < j_hi
   uint64_t win0;
@@ -380,6 +384,11 @@ struct PingArgs {
 // Flow driver (tgsim_flow_*) of an engine that owns every peer.  Its ACK calendar is
 // the ping driver's (PingCal, the kPc* counters, k_ping_count_cal / k_ping_write_cal / k_ping_order):
 // `cal` carries the calendar's buffers and counters, the window and ack_len as `len`.
+constexpr uint32_t kPingResWords = 8;   // pairs sent received sum min max pairs_all pairs_none
+// tgsim_comm_ping_report's packed words: [0, kPingPackSums + n_bins) sums (the summary's nine summed
+// fields in tgsim_ping_summary order, then the histogram), then min_ns, then max_ns.
+constexpr uint32_t kPingPackSums = 9;
+constexpr uint32_t kPingPackWords = kPingPackSums + kPingMaxBins + 2;
 constexpr uint32_t kFlowResWords = 11;  // flows done failed active segs offered retransmits stale fct_sum fct_min fct_max
 struct FlowArgs {
   PingArgs cal;
@@ -435,8 +444,28 @@ int engine_fail(void* engine, int code, const char* msg);
 // Grid of a sharded fused group: 0 = one workgroup per ticket,
 // else a persistent grid of pct % of the resident workgroups.
 void engine_persist_routed(void* engine, uint32_t pct);
-// The ping mesh driver is armed (tgsim_ping_init): the exchange's steps refuse with -EBUSY.
+// The ping mesh driver is armed (tgsim_ping_init): the exchange's steps refuse with -EBUSY ...
 bool engine_ping_armed(void* engine);
+// ... unless it was armed through tgsim_ping_init_sharded (closed windows only: tgsim_comm_run refuses).
+bool engine_ping_sharded(void* engine);
+// The sharded ping driver's sticky fault as one word for the ranks' max all-reduce (0: none):
+// kind << 62 (kPingFaultLate / kPingFaultNospc) | value << 4 (the late tick, or the entries that found
+// the calendar full, clamped to 2^50) | rank.  *agreed: the word is one the ranks agreed on already
+// (engine_ping_fail_agreed), so every rank holds it and none exchanges it again.
+constexpr uint64_t kPingFaultLate = 1, kPingFaultNospc = 2;
+uint64_t engine_ping_fault(void* engine, int rank, bool* agreed);
+// Makes the ranks' agreed fault word this engine's own sticky error (until it re-arms) and fails with
+// it: -EINVAL for a late receipt, -ENOSPC for a full calendar; the text names the rank.
+int engine_ping_fail_agreed(void* engine, uint64_t word);
+// The local report's words on the device for tgsim_comm_ping_report, after k_ping_report on the
+// simulate stream: res = [kPingResWords + n_bins], ctr = the driver's counters (kPc*); cal_word is the
+// counter of the live calendar.  `ev` is recorded behind them.
+int engine_ping_report_dev(void* engine, const unsigned long long** res, const unsigned long long** ctr,
+                           uint32_t* cal_word, uint32_t* n_bins, hipEvent_t ev);
+// The one-rank routed window (TGSIM_COMM_ROUTE1) of tgsim_comm_launch: tgsim_step_sim_launch_slotted
+// with one chunk, which the sharded ping driver accepts (the public call refuses while it is armed).
+int engine_step_sim_launch_route1(void* engine, uint32_t n_ticks, const uint32_t* bounds, void* d_out,
+                                  uint64_t slot_cap, void* routed_event);
 // The same for the flow driver (tgsim_flow_init).
 bool engine_flow_armed(void* engine);
 // Records `ev` on the routing stream after every routing enqueued so far (the exchange of a launched

@@ -3273,11 +3273,12 @@ __global__ __launch_bounds__(256) void k_ping_recv(PingArgs a, const tgsim_deliv
           e[u].requester = r.src;
           e[u].seq = r.seq;
         }
-      } else if (j < a.count && r.dst < a.n_peers && a.targets[(uint64_t)r.dst * a.fanout + k] == r.src) {
+      } else if (j < a.count && r.dst - a.first < a.n_own && a.targets[(uint64_t)r.dst * a.fanout + k] == r.src) {
+        // (an owned requester only: first + n_own <= n_peers, and r.dst below first wraps past n_own)
         const uint64_t t0 = (a.start + (uint64_t)j * a.interval) * a.tick_ns;
         if (r.t_ns >= t0) {
           const uint64_t rtt = r.t_ns - t0;
-          tgsim_ping_pair* p = a.pairs + (uint64_t)r.dst * a.fanout + k;
+          tgsim_ping_pair* p = a.pairs + (uint64_t)(r.dst - a.first) * a.fanout + k;
           atomicAdd(&p->received, 1u);
           atomicAdd(reinterpret_cast<unsigned long long*>(&p->sum_ns), (unsigned long long)rtt);
           atomicMin(reinterpret_cast<unsigned long long*>(&p->min_ns), (unsigned long long)rtt);
@@ -3306,8 +3307,8 @@ __global__ __launch_bounds__(256) void k_ping_recv(PingArgs a, const tgsim_deliv
 // of the source's non-empty slots), which also start the source's row cursor ...
 __global__ __launch_bounds__(256) void k_ping_count_sched(PingArgs a, const uint32_t* __restrict__ n_slots,
                                                           uint64_t* counts, uint32_t* cursor) {
-  const uint32_t s = blockIdx.x * 256 + threadIdx.x;
-  if (s >= a.n_peers) return;
+  const uint32_t s = blockIdx.x * 256 + threadIdx.x;  // (owned source first + s)
+  if (s >= a.n_own) return;
   const uint32_t c = n_slots[s] * (a.j_hi - a.j_lo);
   counts[s] = c;
   cursor[s] = c;
@@ -3320,7 +3321,8 @@ __global__ __launch_bounds__(256) void k_ping_count_cal(PingArgs a, uint64_t* co
   for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256) {
     const PingCal e = a.cal[i];
     if (e.tick < a.win0) atomicMin(&a.ctr[kPcLate], (unsigned long long)e.tick);
-    else if (e.tick < win1 && e.responder < a.n_peers) atomicAdd(reinterpret_cast<unsigned long long*>(&counts[e.responder]), 1ull);
+    else if (e.tick < win1 && e.responder - a.first < a.n_own)  // (an entry of another shard's responder cannot occur)
+      atomicAdd(reinterpret_cast<unsigned long long*>(&counts[e.responder - a.first]), 1ull);
   }
 }
 
@@ -3328,8 +3330,8 @@ __global__ __launch_bounds__(256) void k_ping_count_cal(PingArgs a, uint64_t* co
 // to (j - j_lo) * n_slots + k of the source's row, which is the row's (tick, seq) order already.
 __global__ __launch_bounds__(256) void k_ping_write_sched(PingArgs a, const uint64_t* __restrict__ off, InRec* out) {
   const uint32_t s = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
-  if (s >= a.n_peers) return;
-  const uint32_t tgt = lane < a.fanout ? a.targets[(uint64_t)s * a.fanout + lane] : TGSIM_PING_NONE;
+  if (s >= a.n_own) return;
+  const uint32_t tgt = lane < a.fanout ? a.targets[((uint64_t)a.first + s) * a.fanout + lane] : TGSIM_PING_NONE;
   const uint64_t m = __ballot(tgt != TGSIM_PING_NONE);
   if (tgt == TGSIM_PING_NONE) return;
   const uint32_t ns = (uint32_t)__popcll(m), rank = (uint32_t)__popcll(m & ((1ull << lane) - 1));
@@ -3360,13 +3362,14 @@ __global__ __launch_bounds__(256) void k_ping_write_cal(PingArgs a, const uint64
     if (i < n) {
       e = a.cal[i];
       keep = e.tick >= win1;
-      if (!keep && e.tick >= a.win0 && e.responder < a.n_peers) {
+      const uint32_t ls = e.responder - a.first;  // the responder's row in this shard
+      if (!keep && e.tick >= a.win0 && ls < a.n_own) {
         InRec rec;
         rec.dst = e.requester;
         rec.seq = 0x80000000u | e.seq;
         rec.tick = (uint32_t)(e.tick - a.win0);
         rec.len = a.len;
-        out[off[e.responder] + atomicAdd(&cursor[e.responder], 1u)] = rec;
+        out[off[ls] + atomicAdd(&cursor[ls], 1u)] = rec;
       }
     }
     const uint64_t m = __ballot(keep);
@@ -3433,9 +3436,8 @@ __global__ __launch_bounds__(256) void k_ping_order(const uint64_t* __restrict__
 
 // tgsim_ping_report.  res: [0] pairs [1] sent [2] received [3] sum [4] min [5] max [6] pairs_all
 // [7] pairs_none, then n_bins histogram words.  k_ping_report_init sets the neutral values and folds
-// the histogram replicas; k_ping_report is one pass over the [n_peers][fanout] pair table: a
+// the histogram replicas; k_ping_report is one pass over the shard's [n_own][fanout] pair table: a
 // workgroup reduces in LDS and ends with one set of atomics.
-constexpr uint32_t kPingResWords = 8;
 __device__ __forceinline__ uint64_t wave_min_max_u64(uint64_t v, bool want_max) {  // (every lane takes part)
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
@@ -3462,10 +3464,10 @@ __global__ __launch_bounds__(256) void k_ping_report(PingArgs a, unsigned long l
   __shared__ unsigned long long acc[kPingResWords];
   if (threadIdx.x < kPingResWords) acc[threadIdx.x] = threadIdx.x == 4 ? ~0ull : 0ull;
   __syncthreads();
-  const uint64_t n = (uint64_t)a.n_peers * a.fanout;
+  const uint64_t n = (uint64_t)a.n_own * a.fanout, t0 = (uint64_t)a.first * a.fanout;
   uint64_t pairs = 0, received = 0, sum = 0, mn = ~0ull, mx = 0, all = 0, none = 0;
   for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256) {
-    if (a.targets[i] == TGSIM_PING_NONE) continue;
+    if (a.targets[t0 + i] == TGSIM_PING_NONE) continue;
     const tgsim_ping_pair p = a.pairs[i];
     ++pairs;
     received += p.received;
@@ -3503,7 +3505,7 @@ __global__ __launch_bounds__(256) void k_ping_report(PingArgs a, unsigned long l
 // tgsim_ping_init: the pair table (no reply yet) and the histogram replicas.
 __global__ __launch_bounds__(256) void k_ping_init(PingArgs a) {
   const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i < (uint64_t)a.n_peers * a.fanout) {
+  if (i < (uint64_t)a.n_own * a.fanout) {
     tgsim_ping_pair p;
     p.sent = 0;
     p.received = 0;
@@ -3516,13 +3518,53 @@ __global__ __launch_bounds__(256) void k_ping_init(PingArgs a) {
   if (i < kPingCtrWords) a.ctr[i] = i == kPcLate ? ~0ull : 0ull;
 }
 
-// tgsim_ping_pairs: rows [i0, i0 + n) of the pair table with `sent` filled in (an empty slot: 0).
+// tgsim_ping_pairs: rows [i0, i0 + n) of the shard's pair table with `sent` filled in (an empty slot: 0).
 __global__ __launch_bounds__(256) void k_ping_pairs(PingArgs a, uint64_t i0, uint64_t n, tgsim_ping_pair* out) {
   const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
   tgsim_ping_pair p = a.pairs[i0 + i];
-  p.sent = a.targets[i0 + i] == TGSIM_PING_NONE ? 0u : a.sent;
+  p.sent = a.targets[(uint64_t)a.first * a.fanout + i0 + i] == TGSIM_PING_NONE ? 0u : a.sent;
   out[i] = p;
+}
+
+// tgsim_comm_ping_report: the local report (res: k_ping_report's words and histogram; ctr: the driver's
+// counters) as three runs for the ranks' all-reduces: sums (the summary's summed fields in
+// tgsim_ping_summary order, then the histogram bins), min_ns, max_ns.  A shard without a reply holds the
+// neutral values already (UINT64_MAX, 0).  A few hundred words: one workgroup.
+__global__ __launch_bounds__(256) void k_ping_pack(const unsigned long long* __restrict__ res,
+                                                   const unsigned long long* __restrict__ ctr, uint32_t cal_word,
+                                                   uint32_t n_bins, unsigned long long* __restrict__ out) {
+  const uint32_t i = threadIdx.x;
+  if (i == 0) {
+    out[0] = res[0];  // pairs
+    out[1] = res[1];  // sent
+    out[2] = res[2];  // received
+    out[3] = res[3];  // sum_ns
+    out[4] = res[6];  // pairs_all
+    out[5] = res[7];  // pairs_none
+    out[6] = ctr[kPcDup];
+    out[7] = ctr[kPcCorrupt];
+    out[8] = ctr[cal_word];  // pending_replies
+    out[kPingPackSums + n_bins] = res[4];      // min_ns
+    out[kPingPackSums + n_bins + 1] = res[5];  // max_ns
+  }
+  if (i < n_bins) out[kPingPackSums + i] = res[kPingResWords + i];  // (n_bins <= kPingMaxBins = the workgroup)
+}
+
+// ... and the reduced runs as the tgsim_ping_summary (11 u64 words) followed by the histogram, in the
+// pinned block the host reads, then the sequence word behind a system-scope release (as k_publish_words).
+__global__ __launch_bounds__(256) void k_ping_unpack(const unsigned long long* __restrict__ in, uint32_t n_bins,
+                                                     uint64_t* __restrict__ host, uint64_t seq) {
+  const uint32_t i = threadIdx.x;
+  if (i < 11) {  // pairs sent received sum_ns | min_ns max_ns | pairs_all pairs_none dup corrupt pending
+    const uint32_t w = i < 4 ? i : i < 6 ? kPingPackSums + n_bins + (i - 4) : i - 2;
+    __hip_atomic_store(&host[i], (uint64_t)in[w], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  }
+  if (i < n_bins)
+    __hip_atomic_store(&host[11 + i], (uint64_t)in[kPingPackSums + i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  __threadfence_system();
+  __syncthreads();
+  if (i == 0) __hip_atomic_store(&host[11 + kPingMaxBins], seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -5415,7 +5457,7 @@ uint32_t ping_grid(uint64_t n) { return (uint32_t)std::min<uint64_t>(std::max<ui
 }  // namespace
 
 void launch_ping_init(const PingArgs& a, hipStream_t st) {
-  const uint64_t n = std::max<uint64_t>((uint64_t)a.n_peers * a.fanout, kPingReplicas * kPingMaxBins);
+  const uint64_t n = std::max<uint64_t>((uint64_t)a.n_own * a.fanout, kPingReplicas * kPingMaxBins);
   hipLaunchKernelGGL(k_ping_init, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, a);
 }
 
@@ -5426,21 +5468,21 @@ void launch_ping_recv(const PingArgs& a, const tgsim_delivery* recs, const uint6
 
 void launch_ping_count(const PingArgs& a, const uint32_t* n_slots, uint64_t* counts, uint32_t* cursor,
                        uint64_t cal_bound, hipStream_t st) {
-  hipLaunchKernelGGL(k_ping_count_sched, dim3((a.n_peers + 255) / 256), dim3(256), 0, st, a, n_slots, counts, cursor);
+  hipLaunchKernelGGL(k_ping_count_sched, dim3((a.n_own + 255) / 256), dim3(256), 0, st, a, n_slots, counts, cursor);
   if (cal_bound) hipLaunchKernelGGL(k_ping_count_cal, dim3(ping_grid(cal_bound)), dim3(256), 0, st, a, counts);
 }
 
 void launch_ping_write(const PingArgs& a, const uint64_t* off, uint32_t* cursor, InRec* tmp, InRec* out,
                        uint64_t cal_bound, hipStream_t st) {
-  if (a.j_hi > a.j_lo) hipLaunchKernelGGL(k_ping_write_sched, dim3((a.n_peers + 3) / 4), dim3(256), 0, st, a, off, tmp);
+  if (a.j_hi > a.j_lo) hipLaunchKernelGGL(k_ping_write_sched, dim3((a.n_own + 3) / 4), dim3(256), 0, st, a, off, tmp);
   if (cal_bound) hipLaunchKernelGGL(k_ping_write_cal, dim3(ping_grid(cal_bound)), dim3(256), 0, st, a, off, cursor, tmp);
-  hipLaunchKernelGGL(k_ping_order, dim3((a.n_peers + 3) / 4), dim3(256), 0, st, off, tmp, out, a.n_peers);
+  hipLaunchKernelGGL(k_ping_order, dim3((a.n_own + 3) / 4), dim3(256), 0, st, off, tmp, out, a.n_own);
 }
 
 void launch_ping_report(const PingArgs& a, unsigned long long* res, hipStream_t st) {
   hipLaunchKernelGGL(k_ping_report_init, dim3(1), dim3(256), 0, st, a, res, kPingResWords, 4u);
   // (few workgroups: each ends with eight atomics on the same eight words, which serialize)
-  hipLaunchKernelGGL(k_ping_report, dim3(std::min(ping_grid((uint64_t)a.n_peers * a.fanout), 256u)), dim3(256), 0, st, a, res);
+  hipLaunchKernelGGL(k_ping_report, dim3(std::min(ping_grid((uint64_t)a.n_own * a.fanout), 256u)), dim3(256), 0, st, a, res);
 }
 
 // Flow driver (tgsim_flow_*).
@@ -5481,7 +5523,7 @@ void launch_flow_write(const FlowArgs& f, const uint64_t* off, uint32_t* cursor,
   else if (f.rt) hipLaunchKernelGGL((k_flow_write<false, true>), grid, dim3(256), 0, st, f, off, cursor, tmp);
   else hipLaunchKernelGGL((k_flow_write<false, false>), grid, dim3(256), 0, st, f, off, cursor, tmp);
   if (cal_bound) hipLaunchKernelGGL(k_ping_write_cal, dim3(ping_grid(cal_bound)), dim3(256), 0, st, f.cal, off, cursor, tmp);
-  hipLaunchKernelGGL(k_ping_order, dim3((f.cal.n_peers + 3) / 4), dim3(256), 0, st, off, tmp, out, f.cal.n_peers);
+  hipLaunchKernelGGL(k_ping_order, dim3((f.cal.n_own + 3) / 4), dim3(256), 0, st, off, tmp, out, f.cal.n_own);
 }
 
 void launch_flow_report(const FlowArgs& f, unsigned long long* res, hipStream_t st) {
@@ -5514,6 +5556,15 @@ void launch_flow_fb_report(const FlowArgs& f, unsigned long long* res, hipStream
 
 void launch_ping_pairs(const PingArgs& a, uint64_t i0, uint64_t n, tgsim_ping_pair* out, hipStream_t st) {
   if (n) hipLaunchKernelGGL(k_ping_pairs, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, a, i0, n, out);
+}
+
+void launch_ping_pack(const unsigned long long* res, const unsigned long long* ctr, uint32_t cal_word, uint32_t n_bins,
+                      unsigned long long* out, hipStream_t st) {
+  hipLaunchKernelGGL(k_ping_pack, dim3(1), dim3(256), 0, st, res, ctr, cal_word, n_bins, out);
+}
+
+void launch_ping_unpack(const unsigned long long* in, uint32_t n_bins, uint64_t* host, uint64_t seq, hipStream_t st) {
+  hipLaunchKernelGGL(k_ping_unpack, dim3(1), dim3(256), 0, st, in, n_bins, host, seq);
 }
 
 void launch_gossip(const GossipArgs& g, const tgsim_delivery* recs, uint64_t n, uint64_t* counts,

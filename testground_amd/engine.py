@@ -189,11 +189,14 @@ class CABIEngine:
 
     # -- ping mesh (tgsim_ping_*) ----------------------------------------------------------------
     def ping_init(self, targets=None, count: int = 1, interval_ticks: int = 1, length: int = 64,
-                  start_tick: Optional[int] = None, bin_ns: int = 0, n_bins: int = 0) -> None:
+                  start_tick: Optional[int] = None, bin_ns: int = 0, n_bins: int = 0, sharded: bool = False) -> None:
         """Arms the device ping driver: `targets` is [n_peers, fanout] (a peer id, abi.EXTERNAL or
         abi.PING_NONE per slot); probe j of every slot is offered at start_tick + j * interval_ticks
-        (start_tick None: the engine's current tick).  ping_init(None) disarms it."""
-        fn = self._gossip_fn("ping_init")
+        (start_tick None: the engine's current tick).  ping_init(None) disarms it.  sharded: through
+        tgsim_ping_init_sharded, on an engine that may own part of the peers (`targets` is still the
+        whole run's table); the windows then run through comm_step, the reports and ping_pairs are
+        this shard's, and comm_ping_report gives the whole run's."""
+        fn = self._gossip_fn("ping_init_sharded" if sharded else "ping_init")
         if targets is None:
             self._check(fn(self._h, None, None), "ping_init")
             self._ping = None
@@ -220,12 +223,26 @@ class CABIEngine:
         out["hist"] = hist[:n].copy()
         return out
 
-    def ping_pairs(self, peer: int = 0, n: Optional[int] = None) -> np.ndarray:
-        """[n, fanout] abi.PING_PAIR_DTYPE rows of peers [peer, peer + n) (tgsim_ping_pairs)."""
+    def comm_ping_report(self) -> dict:
+        """ping_report of the whole run on every rank, reduced over the ranks on the device
+        (tgsim_comm_ping_report; collective, sharded ping only)."""
+        s = abi.PingSummary()
+        hist = np.zeros(abi.PING_MAX_BINS, dtype=np.uint64)
+        n = self._check(self._gossip_fn("comm_ping_report")(self._h, C.byref(s), hist.ctypes.data, len(hist)),
+                        "comm_ping_report")
+        out = {k: int(getattr(s, k)) for k in abi.PING_SUMMARY_FIELDS}
+        out["hist"] = hist[:n].copy()
+        return out
+
+    def ping_pairs(self, peer: Optional[int] = None, n: Optional[int] = None) -> np.ndarray:
+        """[n, fanout] abi.PING_PAIR_DTYPE rows of peers [peer, peer + n) (tgsim_ping_pairs); the
+        default is every peer this engine owns."""
         fn = self._gossip_fn("ping_pairs")
         p = getattr(self, "_ping", None)
         fanout = p.fanout if p is not None else 1  # (unarmed: the call says so)
-        n = self.n_peers - peer if n is None else n
+        lo, hi = self.shard
+        peer = lo if peer is None else peer
+        n = max(hi - peer, 0) if n is None else n
         out = np.zeros(n * fanout, dtype=abi.PING_PAIR_DTYPE)
         self._check(fn(self._h, peer, n, out.ctypes.data, len(out)), "ping_pairs")
         return out.reshape(n, fanout)

@@ -371,20 +371,40 @@ def ping_reference(eng, ping: Dict, targets: np.ndarray, n_windows: int, window:
     return out
 
 
-def ping_run(eng, n_windows: int, window: int, collect: bool = False, probe_at=(), before=None) -> Dict:
+def ping_run(eng, n_windows: int, window: int, collect: bool = False, probe_at=(), before=None, step=None) -> Dict:
     """The device loop on an armed engine (Engine.ping_init): n_windows of gen_ping + step.  Nothing
     reaches the host unless asked for: collect keeps each window's (verdicts, deliveries), probe_at
-    the (pairs, report) after those windows."""
+    the (pairs, report) after those windows.  step(window) replaces eng.step (a shard of a run armed
+    with sharded=True: eng.comm_step)."""
+    step = eng.step if step is None else step
     out = {"windows": [], "probes": {}}
     for w in range(n_windows):
         if before is not None:
             before(w)
         eng.gen_ping(window)
-        eng.step(window)
+        step(window)
         if collect:
             out["windows"].append((eng.verdicts(), eng.drain()))
         if w in probe_at:
             out["probes"][w] = (eng.ping_pairs(), eng.ping_report())
+    return out
+
+
+def merge_ping_reports(reports) -> Dict:
+    """The shards' ping reports (Engine.ping_report of every rank) as the whole run's, by the merge
+    rule of include/tgsim.h: every field by sum, except min_ns by min and max_ns by max; hist by sum.
+    For hosts with their own exchange; Engine.comm_ping_report does the same on the device."""
+    reports = list(reports)
+    if not reports:
+        raise ValueError("merge_ping_reports: no report")
+    out = {}
+    for key in abi.PING_SUMMARY_FIELDS:
+        vals = [int(r[key]) for r in reports]
+        out[key] = min(vals) if key == "min_ns" else max(vals) if key == "max_ns" else sum(vals)
+    hists = [np.asarray(r["hist"], dtype=np.uint64) for r in reports]
+    if len({len(h) for h in hists}) != 1:
+        raise ValueError("merge_ping_reports: the reports' histograms differ in length")
+    out["hist"] = np.sum(hists, axis=0, dtype=np.uint64)
     return out
 
 
