@@ -5,7 +5,7 @@
          first HOST_WINDOWS windows only: the model is plain Python)
   run    the device loop alone, for a kernel trace:
            rocprofv3 --kernel-trace --output-format csv -d DIR -o run -- python scripts/flow_measure.py run
-  trace  per-kernel device time of the k_flow_* and shared k_ping_* kernels in such a trace (max_us: the
+  trace  per-kernel device time of the k_flow_* and the calendar's k_cal_* kernels in such a trace (max_us: the
          busy windows, see below), beside the HBM floor of a busy window
   steady the device loop alone: wall time per window and the median over the steady windows (the A/B
          figure: run it with TGSIM_LIB naming another build of the library)
@@ -253,7 +253,7 @@ def main():
         per = {}
         for r in csv.DictReader(open(sys.argv[2])):
             name = r["Kernel_Name"].split("(")[0].split("<")[0].split("::")[-1].split()[-1]  # (void k_flow_write<true, false>(...))
-            if name.startswith(("k_flow_", "k_ping_")) or name in ("k_sim_sparse", "k_sim", "k_sim_list", "k_sim_multi"):
+            if name.startswith(("k_flow_", "k_cal_")) or name in ("k_sim_sparse", "k_sim", "k_sim_list", "k_sim_multi"):
                 per.setdefault(name, []).append((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3)
         flows, w = N * PER_SOURCE, FLOW["window"]
         seg = flows * w  # the windows alternate: a busy window carries 6.4 M segments or their 6.4 M ACKs
@@ -269,7 +269,7 @@ def main():
                   "k_flow_fb": seg * 17 + flows * 2 * 32,
                   "k_flow_rto_report": flows * 32,
                   "k_flow_cc_report": flows * (32 + 32),  # the cc row, and the flow row for its state
-                  "k_ping_count_cal": seg * 16, "k_ping_write_cal": seg * 16 + seg * 16, "k_ping_order": seg * 16 * 2}
+                  "k_cal_count": seg * 16, "k_cal_write": seg * 16 + seg * 16, "k_cal_order": seg * 16 * 2}
         out = {}
         for name, us in sorted(per.items()):
             out[name] = {"calls": len(us), "median_us": round(statistics.median(us), 1), "max_us": round(max(us), 1)}

@@ -4,7 +4,7 @@
          of the same loop driven from the host over the same HIP engine (workloads.ping_reference)
   run    the device loop alone, for a kernel trace:
            rocprofv3 --kernel-trace --output-format csv -d DIR -o run -- python scripts/ping_measure.py run
-  trace  per-kernel device time of the k_ping_* kernels in such a trace, beside their HBM floors
+  trace  per-kernel device time of the k_ping_* and k_cal_* kernels in such a trace, beside their HBM floors
   sharded  what a sharded window costs on one GPU: the device loop of the single engine (ping_init +
          step) against the sharded form at one rank on the routed path (TGSIM_COMM_ROUTE1=1:
          ping_init(sharded=True) + comm_step, the N > 1 step's own kernels, delivered in place), and
@@ -113,11 +113,11 @@ def main():
         per = {}
         for r in csv.DictReader(open(sys.argv[2])):
             name = r["Kernel_Name"].split("(")[0].split("::")[-1]
-            if name.startswith("k_ping_") or name in ("k_sim_sparse", "k_sim", "k_sim_list", "k_sim_multi"):
+            if name.startswith(("k_ping_", "k_cal_")) or name in ("k_sim_sparse", "k_sim", "k_sim_list", "k_sim_multi"):
                 per.setdefault(name, []).append((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3)
         pk = N * FANOUT * 2  # probes (= replies) a steady window offers
-        floors = {"k_ping_recv": 2 * pk * 24 + pk * 16, "k_ping_count_cal": pk * 16, "k_ping_write_sched": pk * 16,
-                  "k_ping_write_cal": pk * 16 + pk * 16, "k_ping_order": 2 * pk * 16 * 2}
+        floors = {"k_ping_recv": 2 * pk * 24 + pk * 16, "k_cal_count": pk * 16, "k_ping_write_sched": pk * 16,
+                  "k_cal_write": pk * 16 + pk * 16, "k_cal_order": 2 * pk * 16 * 2}
         out = {}
         for name, us in sorted(per.items()):
             out[name] = {"calls": len(us), "median_us": round(statistics.median(us), 1), "max_us": round(max(us), 1)}

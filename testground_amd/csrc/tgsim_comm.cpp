@@ -52,7 +52,7 @@ constexpr size_t kRec = sizeof(tgsim_delivery);
 // 34.0-34.4, the whole grid 34.0-34.2.
 constexpr uint32_t kRoutedGridPct = 90;
 // tgsim_comm_ping_report's pinned block: the summary (11 words), the histogram, the sequence word
-constexpr size_t kPingHostWords = sizeof(tgsim_ping_summary) / sizeof(uint64_t) + kPingMaxBins + 1;
+constexpr size_t kPingHostWords = sizeof(tgsim_ping_summary) / sizeof(uint64_t) + kCalMaxBins + 1;
 static_assert(sizeof(tgsim_ping_summary) == 11 * sizeof(uint64_t), "k_ping_unpack writes 11 summary words");
 
 // librccl.so.1, loaded once per process (when torch has loaded it already, dlopen returns that
@@ -196,7 +196,7 @@ struct Comm {
   uint64_t route1_cap[3] = {};  // TGSIM_COMM_ROUTE1: the capacity-sized chunk of out[j]
   uint64_t exchanged = 0, max_count = 0, slot_cap = 0;
   // tgsim_comm_ping_report: the packed words on the device (kPingPackWords) and the reduced report in
-  // pinned memory (a tgsim_ping_summary, kPingMaxBins histogram words, the sequence word)
+  // pinned memory (a tgsim_ping_summary, kCalMaxBins histogram words, the sequence word)
   DevMem d_prep;
   uint64_t* h_prep = nullptr;
   uint64_t* dm_prep = nullptr;

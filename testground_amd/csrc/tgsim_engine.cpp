@@ -455,10 +455,32 @@ struct tgsim_engine_s {
   DevBuf<uint64_t> d_gspread;  // tgsim_gossip_spread's result tables, kSpreadReplicas x 64 x (n_bins + 3) words
   DevBuf<uint32_t> d_gtimes;   // tgsim_gossip_times' rows
 
+  // Reply calendar: the replies or ACKs that delivered requests make, waiting for their
+  // ticks.  One component; the ping and the flow driver hold it in turn (`owner`), never together.
+  // cal_arm / cal_release / cal_args / cal_grow / cal_generate below are its functions.
+  struct ReplyCalendar {
+    enum Owner : uint8_t { kNone, kPing, kFlow };
+    Owner owner = kNone;
+    DevBuf<CalEntry> buf[2];
+    DevBuf<unsigned long long> ctr, hist;  // kCal* counters; histogram replicas
+    DevBuf<unsigned long long> res;        // a report's result words and folded histogram
+    DevBuf<uint32_t> cursor;               // a generated window's row cursors
+    DevBuf<InRec> tmp;                     // a generated window's rows before the order pass
+    uint32_t cur = 0;                      // the buffer being appended to
+    uint64_t kept = 0;                     // its entries behind the last generation (those not yet due then)
+    uint64_t appended = 0;                 // entries made since the holder armed, as of the last generation
+    // sticky faults, until the holder arms again
+    bool late = false;                     // an entry preceded a generated window ...
+    uint64_t late_tick = 0;                // ... due at this tick
+    uint64_t nospc = 0;                    // entries that found the calendar full (as the device counter is)
+    uint64_t agreed = 0;                   // the ranks' agreed fault word (0: none)
+    uint64_t* h_pub = nullptr;             // pinned: the counters as of the last generation, then a sequence word
+    uint64_t* dm_pub = nullptr;
+    hipEvent_t ev_recv = nullptr;          // after the holder's last receipt kernel (delivery stream)
+  } cal;
+
   // ping mesh driver (tgsim_ping_*)
-  bool ping_on = false;
-  bool ping_late = false;        // sticky until tgsim_ping_init: a calendar entry preceded a generated window
-  uint64_t ping_late_tick = 0;
+  bool ping_on() const { return cal.owner == ReplyCalendar::kPing; }
   tgsim_ping ping{};
   uint64_t ping_pairs = 0;       // non-empty slots of the owned peers
   // tgsim_ping_init_sharded (an engine that may own part of the peers): the closed steps of the exchange
@@ -467,26 +489,11 @@ struct tgsim_engine_s {
   // its bound of every pair).
   bool ping_sharded = false;
   uint64_t ping_answered = 0;
-  uint64_t ping_nospc = 0;       // entries that found the calendar full (sticky, as the device counter is)
-  uint64_t ping_agreed = 0;      // the ranks' agreed fault word (0: none)
-  uint32_t ping_cur = 0;         // the calendar buffer being appended to
-  uint64_t ping_kept = 0;        // its entries behind the last generation (those not yet due then)
-  uint64_t ping_appended = 0;    // entries made since tgsim_ping_init, as of the last generation
-  DevBuf<uint32_t> d_ptgt, d_pslots, d_pcur;
+  DevBuf<uint32_t> d_ptgt, d_pslots;
   DevBuf<tgsim_ping_pair> d_ppair, d_prows;
-  DevBuf<unsigned long long> d_phist, d_pctr, d_pres;
-  DevBuf<PingCal> d_pcal[2];
-  DevBuf<InRec> d_ptmp;          // a generated window's rows before the order pass
-  hipEvent_t ev_ping = nullptr;  // after the last k_ping_recv (delivery stream)
-  uint64_t* h_ppub = nullptr;    // pinned: the driver's counters as of the last generation, then a sequence word
-  uint64_t* dm_ppub = nullptr;
 
-  // flow driver (tgsim_flow_*).  Never armed together with ping: its ACK calendar IS
-  // the ping calendar above (d_pcal, d_pctr, d_phist, d_pres, d_pcur, d_ptmp, ping_cur / ping_kept /
-  // ping_appended, h_ppub), grown by ping_grow_calendar.
-  bool flow_on = false;
-  bool flow_late = false;        // sticky until tgsim_flow_init
-  uint64_t flow_late_tick = 0;
+  // flow driver (tgsim_flow_*)
+  bool flow_on() const { return cal.owner == ReplyCalendar::kFlow; }
   tgsim_flow flow{};
   uint64_t n_flows = 0;
   uint64_t flow_offered = 0;     // data packets offered since tgsim_flow_init: each makes at most one calendar entry
@@ -504,9 +511,8 @@ struct tgsim_engine_s {
   bool flow_fb_on = false;       // armed by tgsim_flow_init_fb with an fb
   tgsim_flow_fb flow_fb{};
   DevBuf<tgsim_flow_fb_row> d_ffb;
-  hipEvent_t ev_fb = nullptr;    // after the last k_flow_fb (simulate stream): flow_recv waits for it
+  hipEvent_t ev_fb = nullptr;    // after the last k_flow_fb (simulate stream): the flow receipts wait for it
   DevBuf<uint32_t> d_fsent;
-  hipEvent_t ev_flow = nullptr;  // after the last k_flow_recv_ack (delivery stream)
 
   // per-group traffic matrix (tgsim_groups_init / tgsim_group_matrix)
   bool groups_on = false;
@@ -1514,86 +1520,100 @@ uint32_t ping_probes_before(const tgsim_ping& p, uint64_t t) {
   return static_cast<uint32_t>(std::min<uint64_t>(p.count, (t - p.start_tick - 1) / p.interval_ticks + 1));
 }
 
+// Reply calendar: its buffers released and its state (faults included) cleared; nobody holds it.
+void cal_release(Eng* E) {
+  Eng::ReplyCalendar& c = E->cal;
+  c.buf[0].release(); c.buf[1].release(); c.ctr.release(); c.hist.release(); c.res.release(); c.cursor.release();
+  c.tmp.release();
+  c.owner = Eng::ReplyCalendar::kNone;
+  c.cur = 0;
+  c.kept = c.appended = 0;
+  c.late = false;
+  c.nospc = c.agreed = 0;
+}
+
+// A released calendar made ready for a driver with `rows` generated rows and `entries` entries to start
+// with (the generation grows it); the driver's init kernel resets hist and ctr, then it takes `owner`.
+int cal_arm(Eng* E, size_t rows, uint64_t entries) {
+  Eng::ReplyCalendar& c = E->cal;
+  if (!c.ev_recv) HIPCHK(hipEventCreateWithFlags(&c.ev_recv, hipEventDisableTiming));
+  if (!c.h_pub) {
+    HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&c.h_pub), (kCalPubWords + 1) * sizeof(uint64_t),
+                         hipHostMallocCoherent | hipHostMallocMapped));
+    memset(c.h_pub, 0, (kCalPubWords + 1) * sizeof(uint64_t));
+    HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&c.dm_pub), c.h_pub, 0));
+  }
+  HIPCHK(c.cursor.ensure_exact(rows));
+  HIPCHK(c.hist.ensure_exact(static_cast<size_t>(kCalReplicas) * kCalMaxBins));
+  HIPCHK(c.ctr.ensure_exact(kCalCtrWords));
+  HIPCHK(c.res.ensure_exact(std::max(kPingResWords, kFlowResWords) + kCalMaxBins));
+  HIPCHK(c.buf[0].ensure_exact(std::max<uint64_t>(entries, 1024)));
+  HIPCHK(c.buf[1].ensure_exact(std::max<uint64_t>(entries, 1024)));
+  HIPCHK(hipEventRecord(c.ev_recv, E->dst_st));  // (the first generation waits for it)
+  return 0;
+}
+
+// The calendar's arguments for a driver that owns peers [first, first + n_own), whose replies are `len`
+// bytes long and whose histogram has n_bins bins of bin_ns.
+CalArgs cal_args(Eng* E, uint32_t first, uint32_t n_own, uint32_t len, uint32_t n_bins, uint64_t bin_ns, uint64_t win0,
+                 uint32_t n_ticks) {
+  const Eng::ReplyCalendar& c = E->cal;
+  CalArgs a{};
+  a.hist = c.hist.p;
+  a.ctr = c.ctr.p;
+  a.cal = c.buf[c.cur].p;
+  a.cal_next = c.buf[c.cur ^ 1u].p;
+  a.cal_cap = std::min(c.buf[0].cap, c.buf[1].cap);
+  a.cal_cur = c.cur;
+  a.n_peers = E->N;
+  a.first = first;
+  a.n_own = n_own;
+  a.len = len;
+  a.n_bins = n_bins;
+  a.tick_ns = E->o.tick_ns;
+  a.bin_ns = n_bins ? bin_ns : 1;
+  a.win0 = win0;
+  a.n_ticks = n_ticks;
+  return a;
+}
+
 void ping_release(Eng* E) {
-  E->d_ptgt.release(); E->d_pslots.release(); E->d_pcur.release(); E->d_ppair.release(); E->d_prows.release();
-  E->d_phist.release(); E->d_pctr.release(); E->d_pres.release(); E->d_pcal[0].release(); E->d_pcal[1].release();
-  E->d_ptmp.release();
-  E->ping_on = false;
-  E->ping_late = false;
+  E->d_ptgt.release(); E->d_pslots.release(); E->d_ppair.release(); E->d_prows.release();
   E->ping_sharded = false;
-  E->ping_nospc = 0;
-  E->ping_agreed = 0;
+  cal_release(E);
 }
 
 PingArgs ping_args(Eng* E, uint64_t win0, uint32_t n_ticks) {
   PingArgs a{};
+  // (tgsim_ping_init: the shard is every peer)
+  a.cal = cal_args(E, E->o.shard_begin, E->S, E->ping.len, E->ping.n_bins, E->ping.bin_ns, win0, n_ticks);
   a.targets = E->d_ptgt.p;
   a.pairs = E->d_ppair.p;
-  a.hist = E->d_phist.p;
-  a.ctr = E->d_pctr.p;
-  a.cal = E->d_pcal[E->ping_cur].p;
-  a.cal_next = E->d_pcal[E->ping_cur ^ 1u].p;
-  a.cal_cap = std::min(E->d_pcal[0].cap, E->d_pcal[1].cap);
-  a.cal_cur = E->ping_cur;
-  a.n_peers = E->N;
-  a.first = E->o.shard_begin;  // (tgsim_ping_init: 0 and every peer)
-  a.n_own = E->S;
   a.fanout = E->ping.fanout;
   a.count = E->ping.count;
   a.interval = E->ping.interval_ticks;
-  a.len = E->ping.len;
-  a.n_bins = E->ping.n_bins;
   a.start = E->ping.start_tick;
-  a.tick_ns = E->o.tick_ns;
-  a.bin_ns = E->ping.n_bins ? E->ping.bin_ns : 1;
-  a.win0 = win0;
-  a.n_ticks = n_ticks;
   a.j_lo = ping_probes_before(E->ping, win0);
   a.j_hi = ping_probes_before(E->ping, win0 + n_ticks);
   a.sent = ping_probes_before(E->ping, E->now_tick);
   return a;
 }
 
-// The receipts of one window's delivery-ordered records (off[nd] of them; n bounds the count), behind
-// its per-destination sort on the delivery stream; the next generation waits for ev_ping.
-int ping_recv(Eng* E, const tgsim_delivery* recs, const uint64_t* off, uint32_t nd, uint64_t n, hipStream_t sq) {
-  launch_ping_recv(ping_args(E, 0, 0), recs, off, nd, n, sq);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(E->ev_ping, sq));
-  return 0;
-}
-
-// Flow driver: its own tables, and the calendar it shares with the (disarmed) ping driver.
+// Flow driver: its own tables, and the calendar it holds.
 void flow_release(Eng* E) {
-  ping_release(E);
   E->d_fspec.release(); E->d_frow.release(); E->d_fbits.release(); E->d_fdue.release(); E->d_ffirst.release();
   E->d_fcnt.release(); E->d_fatt.release(); E->d_fcc.release(); E->d_frt.release(); E->d_fsent.release();
   E->d_ffb.release();
   E->flow_fb_on = false;
-  E->flow_on = false;
   E->flow_cc_on = false;
   E->flow_rto_on = false;
-  E->flow_late = false;
+  cal_release(E);
 }
 
 FlowArgs flow_args(Eng* E, uint64_t win0, uint32_t n_ticks) {
   FlowArgs f{};
-  PingArgs& a = f.cal;
-  a.hist = E->d_phist.p;
-  a.ctr = E->d_pctr.p;
-  a.cal = E->d_pcal[E->ping_cur].p;
-  a.cal_next = E->d_pcal[E->ping_cur ^ 1u].p;
-  a.cal_cap = std::min(E->d_pcal[0].cap, E->d_pcal[1].cap);
-  a.cal_cur = E->ping_cur;
-  a.n_peers = E->N;
-  a.first = 0;  // (the flow driver's engine owns every peer)
-  a.n_own = E->N;
-  a.len = E->flow.ack_len;
-  a.n_bins = E->flow.n_bins;
-  a.tick_ns = E->o.tick_ns;
-  a.bin_ns = E->flow.n_bins ? E->flow.bin_ns : 1;
-  a.win0 = win0;
-  a.n_ticks = n_ticks;
+  // (the flow driver's engine owns every peer)
+  f.cal = cal_args(E, 0, E->N, E->flow.ack_len, E->flow.n_bins, E->flow.bin_ns, win0, n_ticks);
   f.spec = E->d_fspec.p;
   f.rows = E->d_frow.p;
   f.bitmap = E->d_fbits.p;
@@ -1620,14 +1640,149 @@ FlowArgs flow_args(Eng* E, uint64_t win0, uint32_t n_ticks) {
   return f;
 }
 
-// The flow receipts of one window's delivery-ordered records, where ping_recv would run; the next
-// generation waits for ev_flow.
-int flow_recv(Eng* E, const tgsim_delivery* recs, const uint64_t* off, uint32_t nd, uint64_t n, hipStream_t sq) {
-  // the window's verdict feedback writes the same rows on the simulate stream, and takes effect first
-  if (E->flow_fb_on) HIPCHK(hipStreamWaitEvent(sq, E->ev_fb, 0));
-  launch_flow_recv(flow_args(E, 0, 0), recs, off, nd, n, sq);
+// The holder's receipts of one window's delivery-ordered records (off[nd] of them; n bounds the count),
+// behind its per-destination sort on the delivery stream; the next generation waits for ev_recv.
+int cal_recv(Eng* E, const tgsim_delivery* recs, const uint64_t* off, uint32_t nd, uint64_t n, hipStream_t sq) {
+  if (E->ping_on()) {
+    launch_ping_recv(ping_args(E, 0, 0), recs, off, nd, n, sq);
+  } else if (E->flow_on()) {
+    // the window's verdict feedback writes the same rows on the simulate stream, and takes effect first
+    if (E->flow_fb_on) HIPCHK(hipStreamWaitEvent(sq, E->ev_fb, 0));
+    launch_flow_recv(flow_args(E, 0, 0), recs, off, nd, n, sq);
+  } else {
+    return 0;
+  }
   HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(E->ev_flow, sq));
+  HIPCHK(hipEventRecord(E->cal.ev_recv, sq));
+  return 0;
+}
+
+// Both calendar buffers at `need` entries or more, the live one's entries kept.
+int cal_grow(Eng* E, uint64_t need, uint64_t live) {
+  Eng::ReplyCalendar& c = E->cal;
+  if (need <= std::min(c.buf[0].cap, c.buf[1].cap)) return 0;
+  HIPCHK(hipStreamSynchronize(E->st));
+  HIPCHK(hipStreamSynchronize(E->dst_st));
+  DevBuf<CalEntry> nb;
+  HIPCHK(nb.ensure(need));
+  if (live) HIPCHK(hipMemcpy(nb.p, c.buf[c.cur].p, sizeof(CalEntry) * live, hipMemcpyDeviceToDevice));
+  c.buf[c.cur].release();
+  c.buf[c.cur] = nb;
+  c.buf[c.cur ^ 1u].release();  // (holds nothing between generations)
+  HIPCHK(c.buf[c.cur ^ 1u].ensure_exact(nb.cap));
+  return 0;
+}
+
+// What the holder supplies to cal_generate: its nouns for the messages and, as callables,
+//   count(cal_bound)    its count pass into d_cnt and the calendar's cursors (with k_cal_count),
+//   write(w, cal_bound) its write pass of window w (with k_cal_write and k_cal_order),
+//   offered(c)          from the published counters c, the entries its offers can have made by the end of
+//                       this window (the growth bound),
+//   own(c)              the records the window schedules by itself (the rest of its rows were entries).
+struct CalNouns {
+  const char* who;      // "ping"
+  const char* entries;  // "replies"
+  const char* entry;    // "reply"
+};
+
+// One generated window [now, now + n_ticks) of the driver that holds the calendar, behind the driver's
+// own preconditions: the count pass, the counters published to the host, the scan, the growth, the
+// write pass, and the calendar's buffers swapped.
+template <typename Count, typename Write, typename Offered, typename Own>
+int cal_generate(Eng* E, uint32_t n_ticks, const CalNouns& nn, Count count, Write write, Offered offered, Own own) {
+  Eng::ReplyCalendar& cal = E->cal;
+  if (cal.late)
+    return E->fail(-EINVAL, "%s: a %s due at tick %llu preceded an earlier window (tgsim_%s_init starts again)", nn.who, nn.entry,
+                   static_cast<unsigned long long>(cal.late_tick), nn.who);
+  const uint64_t win0 = E->now_tick, win1 = win0 + n_ticks;
+  if (win1 >= (1ull << 31)) return E->fail(-EOVERFLOW, "%s: the window ends beyond tick 2^31", nn.who);
+  HIPCHK(hipSetDevice(E->dev));
+  HIPCHK(hipStreamWaitEvent(E->st, cal.ev_recv, 0));  // the last delivery's receipts (delivery stream)
+  Eng::GenWindow w;  // a free window's offsets may still be read by a delivery
+  int rc = take_gen(E, &w);
+  if (rc) return rc;
+  HIPCHK(E->d_cnt.ensure(E->S));
+  count(std::min(cal.buf[0].cap, cal.buf[1].cap));
+  HIPCHK(hipGetLastError());
+  const uint64_t seq = ++E->pub_seq;
+  launch_publish_words(reinterpret_cast<const uint64_t*>(cal.ctr.p), kCalPubWords, cal.dm_pub, seq, E->st);
+  HIPCHK(hipGetLastError());
+  uint64_t total = 0;
+  rc = scan_counts(E, E->d_cnt, w.off, E->d_blk, E->d_tot, E->S, &total);
+  if (!rc) {
+    char what[40];
+    snprintf(what, sizeof what, "%s generation (counters)", nn.who);
+    rc = wait_published(E, &cal.h_pub[kCalPubWords], seq, E->ev_pub, what);
+  }
+  if (rc) {
+    (void)retire_gen(E, std::move(w));
+    return rc;
+  }
+  uint64_t c[kCalPubWords];
+  for (uint32_t i = 0; i < kCalPubWords; ++i) c[i] = __atomic_load_n(&cal.h_pub[i], __ATOMIC_ACQUIRE);
+  const uint64_t cal_n = c[cal.cur];
+  cal.appended += cal_n - cal.kept;  // what the deliveries since the last generation added
+  cal.kept = cal_n;
+  if (c[kCalOverflow]) {
+    (void)retire_gen(E, std::move(w));
+    cal.nospc = c[kCalOverflow];
+    return E->fail(-ENOSPC, "%s: %llu %s found the calendar full", nn.who, static_cast<unsigned long long>(c[kCalOverflow]),
+                   nn.entries);
+  }
+  if (c[kCalLate] != ~0ull) {  // nothing was written: the calendar and the holder's tables stay as they are
+    (void)retire_gen(E, std::move(w));
+    cal.late = true;
+    cal.late_tick = c[kCalLate];
+    return E->fail(-EINVAL, "%s: a %s due at tick %llu precedes the window at tick %llu (a window longer than "
+                            "the lookahead, or a lookahead longer than the minimum netem delay)",
+                   nn.who, nn.entry, static_cast<unsigned long long>(c[kCalLate]), static_cast<unsigned long long>(win0));
+  }
+  // the calendar until the next generation: what stays, plus an entry for every offer made by the end
+  // of this window that has none yet
+  const uint64_t made = offered(c);
+  rc = cal_grow(E, cal_n + (made > cal.appended ? made - cal.appended : 0), cal_n);
+  if (!rc) rc = E->hip(w.in.ensure(total ? total : 1), "generated window");
+  if (!rc) rc = E->hip(cal.tmp.ensure(total ? total : 1), "generated window");
+  if (rc) {
+    (void)retire_gen(E, std::move(w));
+    return rc;
+  }
+  write(w, cal_n);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemsetAsync(cal.ctr.p + cal.cur, 0, sizeof(unsigned long long), E->st));
+  cal.cur ^= 1u;
+  cal.kept = cal_n - (total - own(c));  // less the entries due in this window
+  w.n = total;
+  w.ticks = n_ticks;
+  E->gen_q_ticks += n_ticks;
+  E->gen_q.push_back(std::move(w));
+  return 0;
+}
+
+// The report calls' device part: the streams drained (the last delivery's receipts are folded on the
+// delivery stream), `launch(res)` on the simulate stream, then n_res result words, and the
+// calendar's counters when ctr is given, copied out.
+template <typename Launch>
+int report_read(Eng* E, Launch launch, unsigned long long* res, size_t n_res, unsigned long long* ctr = nullptr) {
+  HIPCHK(hipSetDevice(E->dev));
+  int rc = sync_stream(E);
+  if (rc) return rc;
+  launch(E->cal.res.p);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(res, E->cal.res.p, sizeof(unsigned long long) * n_res, hipMemcpyDeviceToHost, E->st));
+  if (ctr) HIPCHK(hipMemcpyAsync(ctr, E->cal.ctr.p, sizeof(unsigned long long) * kCalCtrWords, hipMemcpyDeviceToHost, E->st));
+  HIPCHK(hipStreamSynchronize(E->st));
+  return 0;
+}
+
+// -EBUSY for `who`, a call that no driver holding the calendar allows beside it, but for `self` (a
+// driver arming again) and, with sharded_ok, the sharded ping driver.
+int driver_busy(Eng* E, const char* who, bool sharded_ok = false,
+                Eng::ReplyCalendar::Owner self = Eng::ReplyCalendar::kNone) {
+  if (E->cal.owner == self) return 0;
+  if (E->ping_on() && !(sharded_ok && E->ping_sharded))
+    return E->fail(-EBUSY, "%s: the ping driver is armed (tgsim_ping_init(engine, NULL, NULL) disarms it)", who);
+  if (E->flow_on()) return E->fail(-EBUSY, "%s: the flow driver is armed (tgsim_flow_init(engine, NULL, NULL, 0) disarms it)", who);
   return 0;
 }
 
@@ -1743,12 +1898,8 @@ int deliver(Eng* E, const tgsim_delivery* in, uint64_t n, hipEvent_t wait, bool 
     launch_metrics_dst(dst, E->d_doff.p, nd, E->d_mdst.p, E->d_mhist.p, sq);
     HIPCHK(hipGetLastError());
   }
-  if (E->ping_on && n_win == 1) {
-    int prc = ping_recv(E, dst, E->d_doff.p, nd, n, sq);
-    if (prc) return prc;
-  }
-  if (E->flow_on && n_win == 1) {
-    int prc = flow_recv(E, dst, E->d_doff.p, nd, n, sq);
+  if (n_win == 1) {
+    int prc = cal_recv(E, dst, E->d_doff.p, nd, n, sq);
     if (prc) return prc;
   }
   if (E->groups_on) {
@@ -1844,14 +1995,8 @@ int deliver_local_from(Eng* E, const EmitRead& emit, uint32_t* emit_n, uint64_t*
     launch_metrics_dst(dst, doff.p, nd, E->d_mdst.p, E->d_mhist.p, sq);
     HIPCHK(hipGetLastError());
   }
-  if (E->ping_on) {
-    int prc = ping_recv(E, dst, doff.p, nd, n, sq);
-    if (prc) return prc;
-  }
-  if (E->flow_on) {
-    int prc = flow_recv(E, dst, doff.p, nd, n, sq);
-    if (prc) return prc;
-  }
+  int prc = cal_recv(E, dst, doff.p, nd, n, sq);
+  if (prc) return prc;
   if (E->groups_on) {
     launch_group_dst(group_args(E), dst, doff.p, nd, nd, n, need_n ? n : n_in, sq);
     HIPCHK(hipGetLastError());
@@ -1885,7 +2030,7 @@ int deliver_local(Eng* E) {
 // dense windows on an engine that owns every peer, no host packets, no per-window diagnostics.
 bool fusable(Eng* E, uint32_t n_ticks, uint32_t g, bool routed = false) {
   if (g < 2 || (E->S != E->N && !routed) || !E->staged.empty() || E->gen_q.size() < g || E->metrics_on ||
-      E->gossip_on || E->ping_on || E->flow_on || E->groups_on || E->sparse_mode == 1 || kSpw != 1)
+      E->gossip_on || E->ping_on() || E->flow_on() || E->groups_on || E->sparse_mode == 1 || kSpw != 1)
     return false;
   for (uint32_t i = 0; i < g; ++i)
     if (E->gen_q[i].ticks != n_ticks || E->gen_q[i].n < 64ull * E->S) return false;  // sparse windows
@@ -2206,6 +2351,53 @@ int step_fused(Eng* E, uint32_t n_ticks, uint32_t g, const GroupRoute* gr = null
 
 Eng* as_eng(void* e) { return static_cast<Eng*>(e); }
 
+// The flow driver's optional parts, for the readers below: the flag that arms one (null: the driver
+// itself) and the text of the call that finds it missing.
+struct FlowPart {
+  bool Eng::*on;
+  const char* missing;
+};
+const FlowPart kFlowBase{nullptr, "the flow driver is not armed (tgsim_flow_init)"},
+    kFlowCc{&Eng::flow_cc_on, "congestion control is not armed (tgsim_flow_init_cc)"},
+    kFlowRto{&Eng::flow_rto_on, "the RTT estimator is not armed (tgsim_flow_init_rto)"},
+    kFlowFb{&Eng::flow_fb_on, "verdict feedback is not armed (tgsim_flow_init_fb)"};
+int flow_part_armed(Eng* E, const char* who, const FlowPart& part) {
+  if (E->flow_on() && (!part.on || E->*part.on)) return 0;
+  return E->fail(-EINVAL, "%s: %s", who, part.missing);
+}
+
+// tgsim_flow*_rows: rows [first, first + n) of one of the per-flow tables.
+template <typename Row>
+int64_t flow_rows_read(void* e, const char* who, const FlowPart& part, DevBuf<Row> Eng::*tab, uint64_t first, uint64_t n,
+                              Row* out, size_t cap) {
+  Eng* E = as_eng(e);
+  if (!E) return -EINVAL;
+  if (int rc = flow_part_armed(E, who, part)) return rc;
+  if (first > E->n_flows || n > E->n_flows - first)
+    return E->fail(-EINVAL, "%s: flows [%llu, %llu) outside [0, %llu)", who, static_cast<unsigned long long>(first),
+                   static_cast<unsigned long long>(first + n), static_cast<unsigned long long>(E->n_flows));
+  if (cap < n) return E->fail(-ENOSPC, "%s: %zu rows for %llu", who, cap, static_cast<unsigned long long>(n));
+  if (n && !out) return E->fail(-EINVAL, "%s: no output buffer", who);
+  HIPCHK(hipSetDevice(E->dev));
+  int rc = sync_stream(E);
+  if (rc) return rc;
+  if (!n) return 0;
+  HIPCHK(hipMemcpyAsync(out, (E->*tab).p + first, sizeof(Row) * n, hipMemcpyDeviceToHost, E->st));
+  HIPCHK(hipStreamSynchronize(E->st));
+  return static_cast<int64_t>(n);
+}
+
+// tgsim_flow_{cc,rto,fb}_report: the part's N result words of `launch` into res, behind the tests.
+template <size_t N, typename Launch>
+int flow_part_report(void* e, const char* who, const FlowPart& part, const void* out, Launch launch,
+                            unsigned long long (&res)[N]) {
+  Eng* E = as_eng(e);
+  if (!E) return -EINVAL;
+  if (int rc = flow_part_armed(E, who, part)) return rc;
+  if (!out) return E->fail(-EINVAL, "%s: no summary buffer", who);
+  return report_read(E, [&](unsigned long long* d) { launch(flow_args(E, 0, 0), d, E->st); }, res, N);
+}
+
 }  // namespace
 
 namespace tgsim {
@@ -2218,16 +2410,17 @@ void engine_shard(void* e, uint32_t* begin, uint32_t* end) {
 }
 int engine_fail(void* e, int code, const char* msg) { return as_eng(e)->fail(code, "%s", msg); }
 void engine_persist_routed(void* e, uint32_t pct) { as_eng(e)->routed_pct = pct; }
-bool engine_ping_armed(void* e) { return as_eng(e)->ping_on; }
-bool engine_ping_sharded(void* e) { return as_eng(e)->ping_on && as_eng(e)->ping_sharded; }
+bool engine_ping_armed(void* e) { return as_eng(e)->ping_on(); }
+bool engine_ping_sharded(void* e) { return as_eng(e)->ping_on() && as_eng(e)->ping_sharded; }
 
 uint64_t engine_ping_fault(void* e, int rank, bool* agreed) {
   Eng* E = as_eng(e);
-  *agreed = E->ping_agreed != 0;
-  if (E->ping_agreed) return E->ping_agreed;
+  const Eng::ReplyCalendar& c = E->cal;  // (the faults of the calendar the sharded ping driver holds)
+  *agreed = c.agreed != 0;
+  if (c.agreed) return c.agreed;
   const uint64_t r = static_cast<uint64_t>(rank) & 15u;
-  if (E->ping_nospc) return kPingFaultNospc << 62 | std::min<uint64_t>(E->ping_nospc, (1ull << 50) - 1) << 4 | r;
-  if (E->ping_late) return kPingFaultLate << 62 | E->ping_late_tick << 4 | r;  // (ticks stay below 2^31)
+  if (c.nospc) return kPingFaultNospc << 62 | std::min<uint64_t>(c.nospc, (1ull << 50) - 1) << 4 | r;
+  if (c.late) return kPingFaultLate << 62 | c.late_tick << 4 | r;  // (ticks stay below 2^31)
   return 0;
 }
 
@@ -2242,10 +2435,10 @@ static int ping_fail_word(Eng* E, uint64_t word) {
 
 int engine_ping_fail_agreed(void* e, uint64_t word) {
   Eng* E = as_eng(e);
-  E->ping_agreed = word;
-  if (word >> 62 == kPingFaultLate && !E->ping_late) {  // this rank's own generation fails from now on, too
-    E->ping_late = true;
-    E->ping_late_tick = word >> 4 & 0xFFFFFFFFull;
+  E->cal.agreed = word;
+  if (word >> 62 == kPingFaultLate && !E->cal.late) {  // this rank's own generation fails from now on, too
+    E->cal.late = true;
+    E->cal.late_tick = word >> 4 & 0xFFFFFFFFull;
   }
   return ping_fail_word(E, word);
 }
@@ -2256,16 +2449,16 @@ int engine_ping_report_dev(void* e, const unsigned long long** res, const unsign
   HIPCHK(hipSetDevice(E->dev));
   int rc = sync_stream(E);  // the receipts of the last delivery are folded on the delivery stream
   if (rc) return rc;
-  launch_ping_report(ping_args(E, 0, 0), E->d_pres.p, E->st);
+  launch_ping_report(ping_args(E, 0, 0), E->cal.res.p, E->st);
   HIPCHK(hipGetLastError());
   HIPCHK(hipEventRecord(ev, E->st));
-  *res = E->d_pres.p;
-  *ctr = E->d_pctr.p;
-  *cal_word = E->ping_cur;
+  *res = E->cal.res.p;
+  *ctr = E->cal.ctr.p;
+  *cal_word = E->cal.cur;
   *n_bins = E->ping.n_bins;
   return 0;
 }
-bool engine_flow_armed(void* e) { return as_eng(e)->flow_on; }
+bool engine_flow_armed(void* e) { return as_eng(e)->flow_on(); }
 const uint64_t* engine_route_counts_dev(void* e) {
   Eng* E = as_eng(e);
   return E->route_n && E->d_rsend.p ? E->d_rsend.p + 16 * E->route_head : nullptr;
@@ -2543,11 +2736,11 @@ void tgsim_destroy(void* e) {
   if (E->h_err) (void)hipHostFree(E->h_err);
   if (E->h_xerr) (void)hipHostFree(E->h_xerr);
   if (E->h_work) (void)hipHostFree(E->h_work);
-  flow_release(E);  // (and the ping driver's state)
+  ping_release(E);
+  flow_release(E);
   groups_release(E);
-  if (E->h_ppub) (void)hipHostFree(E->h_ppub);
-  if (E->ev_ping) (void)hipEventDestroy(E->ev_ping);
-  if (E->ev_flow) (void)hipEventDestroy(E->ev_flow);
+  if (E->cal.h_pub) (void)hipHostFree(E->cal.h_pub);
+  if (E->cal.ev_recv) (void)hipEventDestroy(E->cal.ev_recv);
   if (E->ev_fb) (void)hipEventDestroy(E->ev_fb);
   if (E->h_gerr) (void)hipHostFree(E->h_gerr);
   if (E->h_pub) (void)hipHostFree(E->h_pub);
@@ -2629,8 +2822,7 @@ int tgsim_submit(void* e, const tgsim_pkt* pkts, size_t n) {
   Eng* E = as_eng(e);
   if (!E || (!pkts && n)) return -EINVAL;
   if (!E->gen_q.empty()) return E->fail(-EBUSY, "generated traffic already pending for the next step");
-  if (E->ping_on) return E->fail(-EBUSY, "%s: the ping driver is armed (tgsim_ping_init(engine, NULL, NULL) disarms it)", "submit");
-  if (E->flow_on) return E->fail(-EBUSY, "%s: the flow driver is armed (tgsim_flow_init(engine, NULL, NULL, 0) disarms it)", "submit");
+  if (int brc = driver_busy(E, "submit")) return brc;
   for (size_t i = 0; i < n; ++i) {
     if (pkts[i].src < E->o.shard_begin || pkts[i].src >= E->o.shard_end)
       return E->fail(-EINVAL, "packet %zu: src %u not owned by this shard", i, pkts[i].src);
@@ -2646,8 +2838,7 @@ int tgsim_gen_storm(void* e, double lambda, uint32_t n_ticks) {
   Eng* E = as_eng(e);
   if (!E || !(lambda >= 0.0) || lambda > 4.0 || n_ticks == 0 || n_ticks > 65536) return -EINVAL;
   if (!E->staged.empty()) return E->fail(-EBUSY, "host packets already pending for the next step");
-  if (E->ping_on) return E->fail(-EBUSY, "%s: the ping driver is armed (tgsim_ping_init(engine, NULL, NULL) disarms it)", "gen_storm");
-  if (E->flow_on) return E->fail(-EBUSY, "%s: the flow driver is armed (tgsim_flow_init(engine, NULL, NULL, 0) disarms it)", "gen_storm");
+  if (int brc = driver_busy(E, "gen_storm")) return brc;
   HIPCHK(hipSetDevice(E->dev));
   GenArgsHost g;
   double p = std::exp(-lambda), F = p;
@@ -2690,8 +2881,7 @@ int tgsim_gossip_init(void* e, const tgsim_gossip* g) {
   if (!E || !g || g->n_floods == 0 || g->n_floods > 64 || g->degree == 0 || g->degree > 64 ||
       g->msg_len == 0 || g->msg_len > 65535 || E->N < 2)
     return -EINVAL;
-  if (E->ping_on) return E->fail(-EBUSY, "%s: the ping driver is armed (tgsim_ping_init(engine, NULL, NULL) disarms it)", "gossip_init");
-  if (E->flow_on) return E->fail(-EBUSY, "%s: the flow driver is armed (tgsim_flow_init(engine, NULL, NULL, 0) disarms it)", "gossip_init");
+  if (int brc = driver_busy(E, "gossip_init")) return brc;
   if (g->start_tick < E->now_tick + E->gen_q_ticks) return E->fail(-EINVAL, "gossip: start tick in the past");
   // receipts and flood starts are 32-bit ticks that saturate at 0xFFFFFFFE (0xFFFFFFFF: no receipt)
   if (g->start_tick + static_cast<uint64_t>(g->n_floods - 1) * g->start_gap_ticks > 0xFFFFFFFEull)
@@ -2884,22 +3074,6 @@ int64_t tgsim_gossip_times(void* e, uint32_t peer, uint32_t n, uint32_t* out, si
 }
 
 // Ping mesh driver (include/tgsim.h).
-// Both calendar buffers at `need` entries or more, the live one's entries kept.
-static int ping_grow_calendar(Eng* E, uint64_t need, uint64_t live) {
-  if (need <= std::min(E->d_pcal[0].cap, E->d_pcal[1].cap)) return 0;
-  HIPCHK(hipStreamSynchronize(E->st));
-  HIPCHK(hipStreamSynchronize(E->dst_st));
-  DevBuf<PingCal> nb;
-  HIPCHK(nb.ensure(need));
-  if (live)
-    HIPCHK(hipMemcpy(nb.p, E->d_pcal[E->ping_cur].p, sizeof(PingCal) * live, hipMemcpyDeviceToDevice));
-  E->d_pcal[E->ping_cur].release();
-  E->d_pcal[E->ping_cur] = nb;
-  E->d_pcal[E->ping_cur ^ 1u].release();  // (holds nothing between generations)
-  HIPCHK(E->d_pcal[E->ping_cur ^ 1u].ensure_exact(nb.cap));
-  return 0;
-}
-
 // tgsim_ping_init and tgsim_ping_init_sharded: the same rules, less the ownership test of the first.
 static int ping_arm(void* e, const tgsim_ping* p, const uint32_t* targets, bool sharded) {
   Eng* E = as_eng(e);
@@ -2909,7 +3083,7 @@ static int ping_arm(void* e, const tgsim_ping* p, const uint32_t* targets, bool 
     if (targets) return E->fail(-EINVAL, "ping: a target table without parameters");
     int rc = sync_stream(E);
     if (rc) return rc;
-    if (E->ping_on) {  // (an armed flow driver owns the calendar: it stays)
+    if (E->ping_on()) {  // (the calendar's owner: an armed flow driver holds it, and stays)
       // a window of the sharded form still pending belongs to a step the ranks refused (a late receipt
       // on another rank): it goes with the driver, or the rank could never generate again
       if (E->ping_sharded) drop_gen(E);
@@ -2925,10 +3099,10 @@ static int ping_arm(void* e, const tgsim_ping* p, const uint32_t* targets, bool 
   if (p->count == 0 || p->count > 65535) return E->fail(-EINVAL, "ping: count %u outside 1..65535", p->count);
   if (p->interval_ticks == 0) return E->fail(-EINVAL, "ping: interval_ticks 0");
   if (p->len == 0 || p->len > 65535) return E->fail(-EINVAL, "ping: len %u outside 1..65535", p->len);
-  if (p->n_bins > kPingMaxBins) return E->fail(-EINVAL, "ping: n_bins %u above %u", p->n_bins, kPingMaxBins);
+  if (p->n_bins > kCalMaxBins) return E->fail(-EINVAL, "ping: n_bins %u above %u", p->n_bins, kCalMaxBins);
   if (p->n_bins && p->bin_ns == 0) return E->fail(-EINVAL, "ping: bin_ns 0 with %u bins", p->n_bins);
   if (E->gossip_on) return E->fail(-EBUSY, "ping: the gossip driver is armed");
-  if (E->flow_on) return E->fail(-EBUSY, "ping: the flow driver is armed");
+  if (E->flow_on()) return E->fail(-EBUSY, "ping: the flow driver is armed");
   if (!E->staged.empty()) return E->fail(-EBUSY, "ping: host packets are pending for the next step");
   if (!E->gen_q.empty() || E->route_n) return E->fail(-EBUSY, "ping: generated windows or launched steps are pending");
   if (p->start_tick < E->now_tick)
@@ -2954,13 +3128,6 @@ static int ping_arm(void* e, const tgsim_ping* p, const uint32_t* targets, bool 
   }
   int rc = sync_stream(E);  // a re-init: the last delivery's receipts may still run
   if (rc) return rc;
-  if (!E->ev_ping) HIPCHK(hipEventCreateWithFlags(&E->ev_ping, hipEventDisableTiming));
-  if (!E->h_ppub) {
-    HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&E->h_ppub), (kPingPubWords + 1) * sizeof(uint64_t),
-                         hipHostMallocCoherent | hipHostMallocMapped));
-    memset(E->h_ppub, 0, (kPingPubWords + 1) * sizeof(uint64_t));
-    HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&E->dm_ppub), E->h_ppub, 0));
-  }
   ping_release(E);
   E->ping = *p;
   E->ping_pairs = pairs;
@@ -2968,26 +3135,18 @@ static int ping_arm(void* e, const tgsim_ping* p, const uint32_t* targets, bool 
   // the calendar's growth bound counts one entry per probe of these pairs: sharded, the pairs whose
   // responder this engine owns (only their requests are delivered here); unsharded, every pair as before
   E->ping_answered = sharded ? answered : pairs;
-  E->ping_cur = 0;
-  E->ping_kept = 0;
-  E->ping_appended = 0;
   HIPCHK(E->d_ptgt.ensure_exact(n_slots));
   HIPCHK(E->d_pslots.ensure_exact(E->S));
-  HIPCHK(E->d_pcur.ensure_exact(E->S));
   HIPCHK(E->d_ppair.ensure_exact(std::max<uint64_t>(own_slots, 1)));
-  HIPCHK(E->d_phist.ensure_exact(static_cast<size_t>(kPingReplicas) * kPingMaxBins));
-  HIPCHK(E->d_pctr.ensure_exact(kPingCtrWords));
-  HIPCHK(E->d_pres.ensure_exact(8 + kPingMaxBins));
   // one entry per pair to start with: a probe in flight per pair; tgsim_gen_ping grows it for more
-  HIPCHK(E->d_pcal[0].ensure_exact(std::max<uint64_t>(E->ping_answered, 1024)));
-  HIPCHK(E->d_pcal[1].ensure_exact(std::max<uint64_t>(E->ping_answered, 1024)));
+  rc = cal_arm(E, E->S, E->ping_answered);
+  if (rc) return rc;
   HIPCHK(hipMemcpy(E->d_ptgt.p, targets, sizeof(uint32_t) * n_slots, hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(E->d_pslots.p, slots.data(), sizeof(uint32_t) * E->S, hipMemcpyHostToDevice));
   launch_ping_init(ping_args(E, 0, 0), E->st);
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(E->st));
-  HIPCHK(hipEventRecord(E->ev_ping, E->dst_st));
-  E->ping_on = true;
+  E->cal.owner = Eng::ReplyCalendar::kPing;
   return 0;
 }
 
@@ -3000,94 +3159,38 @@ int tgsim_ping_init_sharded(void* e, const tgsim_ping* p, const uint32_t* target
 int tgsim_gen_ping(void* e, uint32_t n_ticks) {
   Eng* E = as_eng(e);
   if (!E || n_ticks == 0 || n_ticks > 65536) return -EINVAL;
-  if (!E->ping_on) return E->fail(-EINVAL, "ping: the driver is not armed (tgsim_ping_init)");
+  if (!E->ping_on()) return E->fail(-EINVAL, "ping: the driver is not armed (tgsim_ping_init)");
   if (!E->staged.empty()) return E->fail(-EBUSY, "host packets already pending for the next step");
   if (!E->gen_q.empty()) return E->fail(-EBUSY, "ping: a generated window is pending (one window at a time)");
   // (sharded: between tgsim_comm_launch and tgsim_comm_finish the window's delivery, and with it its
-  // receipts, is not enqueued yet: ev_ping below would not cover it)
+  // receipts, is not enqueued yet: the calendar's ev_recv would not cover it)
   if (E->route_n) return E->fail(-EBUSY, "ping: a launched step is not finished (its receipts come first)");
-  if (E->ping_agreed) return ping_fail_word(E, E->ping_agreed);
-  if (E->ping_late)
-    return E->fail(-EINVAL, "ping: a reply due at tick %llu preceded an earlier window (tgsim_ping_init starts again)",
-                   static_cast<unsigned long long>(E->ping_late_tick));
-  const uint64_t win0 = E->now_tick, win1 = win0 + n_ticks;
-  if (win1 >= (1ull << 31)) return E->fail(-EOVERFLOW, "ping: the window ends beyond tick 2^31");
-  HIPCHK(hipSetDevice(E->dev));
-  HIPCHK(hipStreamWaitEvent(E->st, E->ev_ping, 0));  // the last delivery's receipts (delivery stream)
-  PingArgs a = ping_args(E, win0, n_ticks);
-  Eng::GenWindow w;  // a free window's offsets may still be read by a delivery
-  int rc = take_gen(E, &w);
-  if (rc) return rc;
-  HIPCHK(E->d_cnt.ensure(E->S));
-  launch_ping_count(a, E->d_pslots.p, E->d_cnt.p, E->d_pcur.p, a.cal_cap, E->st);
-  HIPCHK(hipGetLastError());
-  const uint64_t seq = ++E->pub_seq;
-  launch_publish_words(reinterpret_cast<const uint64_t*>(E->d_pctr.p), kPingPubWords, E->dm_ppub, seq, E->st);
-  HIPCHK(hipGetLastError());
-  uint64_t total = 0;
-  rc = scan_counts(E, E->d_cnt, w.off, E->d_blk, E->d_tot, E->S, &total);
-  if (!rc) rc = wait_published(E, &E->h_ppub[kPingPubWords], seq, E->ev_pub, "ping generation (counters)");
-  if (rc) {
-    (void)retire_gen(E, std::move(w));
-    return rc;
-  }
-  uint64_t c[kPingPubWords];
-  for (uint32_t i = 0; i < kPingPubWords; ++i) c[i] = __atomic_load_n(&E->h_ppub[i], __ATOMIC_ACQUIRE);
-  const uint64_t cal_n = c[E->ping_cur];
-  E->ping_appended += cal_n - E->ping_kept;  // what the deliveries since the last generation added
-  E->ping_kept = cal_n;
-  if (c[kPcOverflow]) {
-    (void)retire_gen(E, std::move(w));
-    E->ping_nospc = c[kPcOverflow];
-    return E->fail(-ENOSPC, "ping: %llu replies found the calendar full", static_cast<unsigned long long>(c[kPcOverflow]));
-  }
-  if (c[kPcLate] != ~0ull) {  // nothing was written: the calendar and the pair table stay as they are
-    (void)retire_gen(E, std::move(w));
-    E->ping_late = true;
-    E->ping_late_tick = c[kPcLate];
-    return E->fail(-EINVAL, "ping: a reply due at tick %llu precedes the window at tick %llu (a window longer than "
-                            "the lookahead, or a lookahead longer than the minimum netem delay)",
-                   static_cast<unsigned long long>(c[kPcLate]), static_cast<unsigned long long>(win0));
-  }
-  // the calendar until the next generation: what stays, plus a reply for every probe offered by the
-  // end of this window that has none yet
-  const uint64_t offered = E->ping_answered * a.j_hi;
-  rc = ping_grow_calendar(E, cal_n + (offered > E->ping_appended ? offered - E->ping_appended : 0), cal_n);
-  if (!rc) rc = E->hip(w.in.ensure(total ? total : 1), "generated window");
-  if (!rc) rc = E->hip(E->d_ptmp.ensure(total ? total : 1), "generated window");
-  if (rc) {
-    (void)retire_gen(E, std::move(w));
-    return rc;
-  }
-  a = ping_args(E, win0, n_ticks);
-  launch_ping_write(a, w.off.p, E->d_pcur.p, E->d_ptmp.p, w.in.p, cal_n, E->st);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipMemsetAsync(E->d_pctr.p + E->ping_cur, 0, sizeof(unsigned long long), E->st));
-  E->ping_cur ^= 1u;
-  E->ping_kept = cal_n - (total - E->ping_pairs * (a.j_hi - a.j_lo));  // less the replies due in this window
-  w.n = total;
-  w.ticks = n_ticks;
-  E->gen_q_ticks += n_ticks;
-  E->gen_q.push_back(std::move(w));
-  return 0;
+  if (E->cal.agreed) return ping_fail_word(E, E->cal.agreed);
+  const uint32_t j_lo = ping_probes_before(E->ping, E->now_tick), j_hi = ping_probes_before(E->ping, E->now_tick + n_ticks);
+  return cal_generate(
+      E, n_ticks, CalNouns{"ping", "replies", "reply"},
+      [&](uint64_t cal_bound) {
+        launch_ping_count(ping_args(E, E->now_tick, n_ticks), E->d_pslots.p, E->d_cnt.p, E->cal.cursor.p, cal_bound, E->st);
+      },
+      [&](Eng::GenWindow& w, uint64_t cal_bound) {
+        launch_ping_write(ping_args(E, E->now_tick, n_ticks), w.off.p, E->cal.cursor.p, E->cal.tmp.p, w.in.p, cal_bound, E->st);
+      },
+      // a reply for every probe offered by the end of this window
+      [&](const uint64_t*) { return E->ping_answered * j_hi; },
+      [&](const uint64_t*) { return E->ping_pairs * (j_hi - j_lo); });
 }
 
 int64_t tgsim_ping_report(void* e, tgsim_ping_summary* out, uint64_t* hist, size_t hist_cap) {
   Eng* E = as_eng(e);
   if (!E) return -EINVAL;
-  if (!E->ping_on) return E->fail(-EINVAL, "ping_report: the ping driver is not armed (tgsim_ping_init)");
+  if (!E->ping_on()) return E->fail(-EINVAL, "ping_report: the ping driver is not armed (tgsim_ping_init)");
   if (!out) return E->fail(-EINVAL, "ping_report: no summary buffer");
   const uint32_t nb = E->ping.n_bins;
   if (nb && (!hist || hist_cap < nb)) return E->fail(-EINVAL, "ping_report: %zu histogram words for %u bins", hist ? hist_cap : size_t{0}, nb);
-  HIPCHK(hipSetDevice(E->dev));
-  int rc = sync_stream(E);  // the receipts of the last delivery are folded on the delivery stream
+  unsigned long long res[kPingResWords + kCalMaxBins], ctr[kCalCtrWords];
+  int rc = report_read(E, [&](unsigned long long* d) { launch_ping_report(ping_args(E, 0, 0), d, E->st); }, res,
+                       kPingResWords + nb, ctr);
   if (rc) return rc;
-  launch_ping_report(ping_args(E, 0, 0), E->d_pres.p, E->st);
-  HIPCHK(hipGetLastError());
-  unsigned long long res[8 + kPingMaxBins], ctr[kPingCtrWords];
-  HIPCHK(hipMemcpyAsync(res, E->d_pres.p, sizeof(unsigned long long) * (8 + nb), hipMemcpyDeviceToHost, E->st));
-  HIPCHK(hipMemcpyAsync(ctr, E->d_pctr.p, sizeof ctr, hipMemcpyDeviceToHost, E->st));
-  HIPCHK(hipStreamSynchronize(E->st));
   out->pairs = res[0];
   out->sent = res[1];
   out->received = res[2];
@@ -3096,17 +3199,17 @@ int64_t tgsim_ping_report(void* e, tgsim_ping_summary* out, uint64_t* hist, size
   out->max_ns = res[5];
   out->pairs_all = res[6];
   out->pairs_none = res[7];
-  out->dup_ignored = ctr[kPcDup];
-  out->corrupt_ignored = ctr[kPcCorrupt];
-  out->pending_replies = ctr[E->ping_cur];
-  for (uint32_t b = 0; b < nb; ++b) hist[b] = res[8 + b];
+  out->dup_ignored = ctr[kCalDup];
+  out->corrupt_ignored = ctr[kCalCorrupt];
+  out->pending_replies = ctr[E->cal.cur];
+  for (uint32_t b = 0; b < nb; ++b) hist[b] = res[kPingResWords + b];
   return nb;
 }
 
 int64_t tgsim_ping_pairs(void* e, uint32_t peer, uint32_t n, tgsim_ping_pair* out, size_t cap) {
   Eng* E = as_eng(e);
   if (!E) return -EINVAL;
-  if (!E->ping_on) return E->fail(-EINVAL, "ping_pairs: the ping driver is not armed (tgsim_ping_init)");
+  if (!E->ping_on()) return E->fail(-EINVAL, "ping_pairs: the ping driver is not armed (tgsim_ping_init)");
   if (peer > E->N || n > E->N - peer)
     return E->fail(-EINVAL, "ping_pairs: peers [%u, %llu) outside [0, %u)", peer, static_cast<unsigned long long>(peer) + n, E->N);
   if (peer < E->o.shard_begin || static_cast<uint64_t>(peer) + n > E->o.shard_end)
@@ -3152,7 +3255,7 @@ int tgsim_flow_init_fb(void* e, const tgsim_flow* p, const tgsim_flow_cc* cc, co
     if (flows || n_flows) return E->fail(-EINVAL, "flow: a flow table without parameters");
     int rc = sync_stream(E);
     if (rc) return rc;
-    if (E->flow_on) flow_release(E);
+    if (E->flow_on()) flow_release(E);
     return 0;
   }
   if (!flows || !n_flows) return E->fail(-EINVAL, "flow: no flow table");
@@ -3164,7 +3267,7 @@ int tgsim_flow_init_fb(void* e, const tgsim_flow* p, const tgsim_flow_cc* cc, co
   if (p->window == 0 || p->window > 64) return E->fail(-EINVAL, "flow: window %u outside 1..64", p->window);
   if (p->rto_ticks == 0 || p->rto_ticks >= (1u << 31)) return E->fail(-EINVAL, "flow: rto_ticks %u outside 1..2^31-1", p->rto_ticks);
   if (p->max_attempts == 0 || p->max_attempts > 16) return E->fail(-EINVAL, "flow: max_attempts %u outside 1..16", p->max_attempts);
-  if (p->n_bins > kPingMaxBins) return E->fail(-EINVAL, "flow: n_bins %u above %u", p->n_bins, kPingMaxBins);
+  if (p->n_bins > kCalMaxBins) return E->fail(-EINVAL, "flow: n_bins %u above %u", p->n_bins, kCalMaxBins);
   if (p->n_bins && p->bin_ns == 0) return E->fail(-EINVAL, "flow: bin_ns 0 with %u bins", p->n_bins);
   if (cc) {
     if (cc->init_cwnd == 0 || cc->init_cwnd > p->window)
@@ -3188,7 +3291,7 @@ int tgsim_flow_init_fb(void* e, const tgsim_flow* p, const tgsim_flow_cc* cc, co
     return E->fail(-EINVAL, "flow: %llu flows for %u peers (at most %u per source)", static_cast<unsigned long long>(n_flows), E->N,
                    TGSIM_FLOW_SLOTS);
   if (E->gossip_on) return E->fail(-EBUSY, "flow: the gossip driver is armed");
-  if (E->ping_on) return E->fail(-EBUSY, "flow: the ping driver is armed (tgsim_ping_init(engine, NULL, NULL) disarms it)");
+  if (int brc = driver_busy(E, "flow", false, Eng::ReplyCalendar::kFlow)) return brc;
   if (!E->staged.empty()) return E->fail(-EBUSY, "flow: host packets are pending for the next step");
   if (!E->gen_q.empty() || E->route_n) return E->fail(-EBUSY, "flow: generated windows or launched steps are pending");
   std::vector<uint32_t> first(E->N, 0), cnt(E->N, 0);
@@ -3215,14 +3318,7 @@ int tgsim_flow_init_fb(void* e, const tgsim_flow* p, const tgsim_flow_cc* cc, co
   }
   int rc = sync_stream(E);  // a re-init: the last delivery's receipts may still run
   if (rc) return rc;
-  if (!E->ev_flow) HIPCHK(hipEventCreateWithFlags(&E->ev_flow, hipEventDisableTiming));
   if (fb && !E->ev_fb) HIPCHK(hipEventCreateWithFlags(&E->ev_fb, hipEventDisableTiming));
-  if (!E->h_ppub) {
-    HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&E->h_ppub), (kPingPubWords + 1) * sizeof(uint64_t),
-                         hipHostMallocCoherent | hipHostMallocMapped));
-    memset(E->h_ppub, 0, (kPingPubWords + 1) * sizeof(uint64_t));
-    HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&E->dm_ppub), E->h_ppub, 0));
-  }
   flow_release(E);
   E->flow = *p;
   E->n_flows = n_flows;
@@ -3242,9 +3338,6 @@ int tgsim_flow_init_fb(void* e, const tgsim_flow* p, const tgsim_flow_cc* cc, co
     HIPCHK(E->d_ffb.ensure_exact(n_flows));
     HIPCHK(hipEventRecord(E->ev_fb, E->st));  // (flow_recv waits for it even behind a window that offered nothing)
   }
-  E->ping_cur = 0;
-  E->ping_kept = 0;
-  E->ping_appended = 0;
   HIPCHK(E->d_fspec.ensure_exact(n_flows));
   HIPCHK(E->d_frow.ensure_exact(n_flows));
   HIPCHK(E->d_fbits.ensure_exact(n_flows));
@@ -3252,28 +3345,23 @@ int tgsim_flow_init_fb(void* e, const tgsim_flow* p, const tgsim_flow_cc* cc, co
   HIPCHK(E->d_fatt.ensure_exact(n_flows * p->window));
   HIPCHK(E->d_ffirst.ensure_exact(E->N));
   HIPCHK(E->d_fcnt.ensure_exact(E->N));
-  HIPCHK(E->d_pcur.ensure_exact(E->N));
-  HIPCHK(E->d_phist.ensure_exact(static_cast<size_t>(kPingReplicas) * kPingMaxBins));
-  HIPCHK(E->d_pctr.ensure_exact(kPingCtrWords));
-  HIPCHK(E->d_pres.ensure_exact(kFlowResWords + kPingMaxBins));
   // an ACK per segment in flight to start with; tgsim_gen_flow grows it for retransmissions
-  HIPCHK(E->d_pcal[0].ensure_exact(std::max<uint64_t>(in_flight, 1024)));
-  HIPCHK(E->d_pcal[1].ensure_exact(std::max<uint64_t>(in_flight, 1024)));
+  rc = cal_arm(E, E->N, in_flight);
+  if (rc) return rc;
   HIPCHK(hipMemcpy(E->d_fspec.p, flows, sizeof(tgsim_flow_spec) * n_flows, hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(E->d_ffirst.p, first.data(), sizeof(uint32_t) * E->N, hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(E->d_fcnt.p, cnt.data(), sizeof(uint32_t) * E->N, hipMemcpyHostToDevice));
   launch_flow_init(flow_args(E, 0, 0), E->st);
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(E->st));
-  HIPCHK(hipEventRecord(E->ev_flow, E->dst_st));
-  E->flow_on = true;
+  E->cal.owner = Eng::ReplyCalendar::kFlow;
   return 0;
 }
 
 int tgsim_gen_flow(void* e, uint32_t n_ticks) {
   Eng* E = as_eng(e);
   if (!E || n_ticks == 0 || n_ticks > 65536) return -EINVAL;
-  if (!E->flow_on) return E->fail(-EINVAL, "flow: the driver is not armed (tgsim_flow_init)");
+  if (!E->flow_on()) return E->fail(-EINVAL, "flow: the driver is not armed (tgsim_flow_init)");
   if (E->flow_rto_on && n_ticks > E->flow_rto.min_rto_ticks)
     return E->fail(-EINVAL, "flow: a window of %u ticks is longer than min_rto_ticks %u (a segment is offered at most once per window)",
                    n_ticks, E->flow_rto.min_rto_ticks);
@@ -3282,87 +3370,30 @@ int tgsim_gen_flow(void* e, uint32_t n_ticks) {
                    n_ticks, E->flow.rto_ticks);
   if (!E->staged.empty()) return E->fail(-EBUSY, "host packets already pending for the next step");
   if (!E->gen_q.empty()) return E->fail(-EBUSY, "flow: a generated window is pending (one window at a time)");
-  if (E->flow_late)
-    return E->fail(-EINVAL, "flow: a receipt due at tick %llu preceded an earlier window (tgsim_flow_init starts again)",
-                   static_cast<unsigned long long>(E->flow_late_tick));
-  const uint64_t win0 = E->now_tick, win1 = win0 + n_ticks;
-  if (win1 >= (1ull << 31)) return E->fail(-EOVERFLOW, "flow: the window ends beyond tick 2^31");
-  HIPCHK(hipSetDevice(E->dev));
-  HIPCHK(hipStreamWaitEvent(E->st, E->ev_flow, 0));  // the last delivery's receipts (delivery stream)
-  FlowArgs f = flow_args(E, win0, n_ticks);
-  Eng::GenWindow w;  // a free window's offsets may still be read by a delivery
-  int rc = take_gen(E, &w);
-  if (rc) return rc;
-  HIPCHK(E->d_cnt.ensure(E->S));
-  launch_flow_count(f, E->d_cnt.p, E->d_pcur.p, f.cal.cal_cap, E->st);
-  HIPCHK(hipGetLastError());
-  const uint64_t seq = ++E->pub_seq;
-  launch_publish_words(reinterpret_cast<const uint64_t*>(E->d_pctr.p), kPingPubWords, E->dm_ppub, seq, E->st);
-  HIPCHK(hipGetLastError());
-  uint64_t total = 0;
-  rc = scan_counts(E, E->d_cnt, w.off, E->d_blk, E->d_tot, E->S, &total);
-  if (!rc) rc = wait_published(E, &E->h_ppub[kPingPubWords], seq, E->ev_pub, "flow generation (counters)");
-  if (rc) {
-    (void)retire_gen(E, std::move(w));
-    return rc;
-  }
-  uint64_t c[kPingPubWords];
-  for (uint32_t i = 0; i < kPingPubWords; ++i) c[i] = __atomic_load_n(&E->h_ppub[i], __ATOMIC_ACQUIRE);
-  const uint64_t cal_n = c[E->ping_cur];
-  E->ping_appended += cal_n - E->ping_kept;  // what the deliveries since the last generation added
-  E->ping_kept = cal_n;
-  if (c[kPcOverflow]) {
-    (void)retire_gen(E, std::move(w));
-    return E->fail(-ENOSPC, "flow: %llu ACKs found the calendar full", static_cast<unsigned long long>(c[kPcOverflow]));
-  }
-  if (c[kPcLate] != ~0ull) {  // nothing was written: the calendar and every flow stay as they are
-    (void)retire_gen(E, std::move(w));
-    E->flow_late = true;
-    E->flow_late_tick = c[kPcLate];
-    return E->fail(-EINVAL, "flow: a receipt due at tick %llu precedes the window at tick %llu (a window longer than "
-                            "the lookahead, or a lookahead longer than the minimum netem delay)",
-                   static_cast<unsigned long long>(c[kPcLate]), static_cast<unsigned long long>(win0));
-  }
-  // the calendar until the next generation: what stays, plus an ACK for every data packet offered by
-  // the end of this window that has none yet
-  const uint64_t offers = c[kPcOffers];
-  E->flow_offered += offers;
-  rc = ping_grow_calendar(E, cal_n + (E->flow_offered > E->ping_appended ? E->flow_offered - E->ping_appended : 0), cal_n);
-  if (!rc) rc = E->hip(w.in.ensure(total ? total : 1), "generated window");
-  if (!rc) rc = E->hip(E->d_ptmp.ensure(total ? total : 1), "generated window");
-  if (rc) {
-    (void)retire_gen(E, std::move(w));
-    return rc;
-  }
-  f = flow_args(E, win0, n_ticks);
-  launch_flow_write(f, w.off.p, E->d_pcur.p, E->d_ptmp.p, w.in.p, cal_n, E->st);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipMemsetAsync(E->d_pctr.p + E->ping_cur, 0, sizeof(unsigned long long), E->st));
-  E->ping_cur ^= 1u;
-  E->ping_kept = cal_n - (total - offers);  // less the ACKs due in this window
-  w.n = total;
-  w.ticks = n_ticks;
-  E->gen_q_ticks += n_ticks;
-  E->gen_q.push_back(std::move(w));
-  return 0;
+  return cal_generate(
+      E, n_ticks, CalNouns{"flow", "ACKs", "receipt"},
+      [&](uint64_t cal_bound) {
+        launch_flow_count(flow_args(E, E->now_tick, n_ticks), E->d_cnt.p, E->cal.cursor.p, cal_bound, E->st);
+      },
+      [&](Eng::GenWindow& w, uint64_t cal_bound) {
+        launch_flow_write(flow_args(E, E->now_tick, n_ticks), w.off.p, E->cal.cursor.p, E->cal.tmp.p, w.in.p, cal_bound, E->st);
+      },
+      // an ACK for every data packet offered by the end of this window
+      [&](const uint64_t* c) { return E->flow_offered += c[kCalOffers]; },
+      [&](const uint64_t* c) { return c[kCalOffers]; });
 }
 
 int64_t tgsim_flow_report(void* e, tgsim_flow_summary* out, uint64_t* hist, size_t hist_cap) {
   Eng* E = as_eng(e);
   if (!E) return -EINVAL;
-  if (!E->flow_on) return E->fail(-EINVAL, "flow_report: the flow driver is not armed (tgsim_flow_init)");
+  if (!E->flow_on()) return E->fail(-EINVAL, "flow_report: the flow driver is not armed (tgsim_flow_init)");
   if (!out) return E->fail(-EINVAL, "flow_report: no summary buffer");
   const uint32_t nb = E->flow.n_bins;
   if (nb && (!hist || hist_cap < nb)) return E->fail(-EINVAL, "flow_report: %zu histogram words for %u bins", hist ? hist_cap : size_t{0}, nb);
-  HIPCHK(hipSetDevice(E->dev));
-  int rc = sync_stream(E);  // the receipts of the last delivery are folded on the delivery stream
+  unsigned long long res[kFlowResWords + kCalMaxBins], ctr[kCalCtrWords];
+  int rc = report_read(E, [&](unsigned long long* d) { launch_flow_report(flow_args(E, 0, 0), d, E->st); }, res,
+                       kFlowResWords + nb, ctr);
   if (rc) return rc;
-  launch_flow_report(flow_args(E, 0, 0), E->d_pres.p, E->st);
-  HIPCHK(hipGetLastError());
-  unsigned long long res[kFlowResWords + kPingMaxBins], ctr[kPingCtrWords];
-  HIPCHK(hipMemcpyAsync(res, E->d_pres.p, sizeof(unsigned long long) * (kFlowResWords + nb), hipMemcpyDeviceToHost, E->st));
-  HIPCHK(hipMemcpyAsync(ctr, E->d_pctr.p, sizeof ctr, hipMemcpyDeviceToHost, E->st));
-  HIPCHK(hipStreamSynchronize(E->st));
   out->flows = res[0];
   out->done = res[1];
   out->failed = res[2];
@@ -3372,9 +3403,9 @@ int64_t tgsim_flow_report(void* e, tgsim_flow_summary* out, uint64_t* hist, size
   out->data_offered = res[5];
   out->retransmits = res[6];
   out->stale_acks = res[7];
-  out->dup_ignored = ctr[kPcDup];
-  out->corrupt_ignored = ctr[kPcCorrupt];
-  out->pending_acks = ctr[E->ping_cur];
+  out->dup_ignored = ctr[kCalDup];
+  out->corrupt_ignored = ctr[kCalCorrupt];
+  out->pending_acks = ctr[E->cal.cur];
   out->fct_sum_ns = res[8];
   out->fct_min_ns = res[9];
   out->fct_max_ns = res[10];
@@ -3383,54 +3414,22 @@ int64_t tgsim_flow_report(void* e, tgsim_flow_summary* out, uint64_t* hist, size
 }
 
 int64_t tgsim_flow_rows(void* e, uint64_t first, uint64_t n, tgsim_flow_row* out, size_t cap) {
-  Eng* E = as_eng(e);
-  if (!E) return -EINVAL;
-  if (!E->flow_on) return E->fail(-EINVAL, "flow_rows: the flow driver is not armed (tgsim_flow_init)");
-  if (first > E->n_flows || n > E->n_flows - first)
-    return E->fail(-EINVAL, "flow_rows: flows [%llu, %llu) outside [0, %llu)", static_cast<unsigned long long>(first),
-                   static_cast<unsigned long long>(first + n), static_cast<unsigned long long>(E->n_flows));
-  if (cap < n) return E->fail(-ENOSPC, "flow_rows: %zu rows for %llu", cap, static_cast<unsigned long long>(n));
-  if (n && !out) return E->fail(-EINVAL, "flow_rows: no output buffer");
-  HIPCHK(hipSetDevice(E->dev));
-  int rc = sync_stream(E);
-  if (rc) return rc;
-  if (!n) return 0;
-  HIPCHK(hipMemcpyAsync(out, E->d_frow.p + first, sizeof(tgsim_flow_row) * n, hipMemcpyDeviceToHost, E->st));
-  HIPCHK(hipStreamSynchronize(E->st));
-  return static_cast<int64_t>(n);
+  return flow_rows_read(e, "flow_rows", kFlowBase, &Eng::d_frow, first, n, out, cap);
 }
-
 int64_t tgsim_flow_cc_rows(void* e, uint64_t first, uint64_t n, tgsim_flow_cc_row* out, size_t cap) {
-  Eng* E = as_eng(e);
-  if (!E) return -EINVAL;
-  if (!E->flow_on || !E->flow_cc_on) return E->fail(-EINVAL, "flow_cc_rows: congestion control is not armed (tgsim_flow_init_cc)");
-  if (first > E->n_flows || n > E->n_flows - first)
-    return E->fail(-EINVAL, "flow_cc_rows: flows [%llu, %llu) outside [0, %llu)", static_cast<unsigned long long>(first),
-                   static_cast<unsigned long long>(first + n), static_cast<unsigned long long>(E->n_flows));
-  if (cap < n) return E->fail(-ENOSPC, "flow_cc_rows: %zu rows for %llu", cap, static_cast<unsigned long long>(n));
-  if (n && !out) return E->fail(-EINVAL, "flow_cc_rows: no output buffer");
-  HIPCHK(hipSetDevice(E->dev));
-  int rc = sync_stream(E);
-  if (rc) return rc;
-  if (!n) return 0;
-  HIPCHK(hipMemcpyAsync(out, E->d_fcc.p + first, sizeof(tgsim_flow_cc_row) * n, hipMemcpyDeviceToHost, E->st));
-  HIPCHK(hipStreamSynchronize(E->st));
-  return static_cast<int64_t>(n);
+  return flow_rows_read(e, "flow_cc_rows", kFlowCc, &Eng::d_fcc, first, n, out, cap);
+}
+int64_t tgsim_flow_rto_rows(void* e, uint64_t first, uint64_t n, tgsim_flow_rto_row* out, size_t cap) {
+  return flow_rows_read(e, "flow_rto_rows", kFlowRto, &Eng::d_frt, first, n, out, cap);
+}
+int64_t tgsim_flow_fb_rows(void* e, uint64_t first, uint64_t n, tgsim_flow_fb_row* out, size_t cap) {
+  return flow_rows_read(e, "flow_fb_rows", kFlowFb, &Eng::d_ffb, first, n, out, cap);
 }
 
 int tgsim_flow_cc_report(void* e, tgsim_flow_cc_summary* out) {
-  Eng* E = as_eng(e);
-  if (!E) return -EINVAL;
-  if (!E->flow_on || !E->flow_cc_on) return E->fail(-EINVAL, "flow_cc_report: congestion control is not armed (tgsim_flow_init_cc)");
-  if (!out) return E->fail(-EINVAL, "flow_cc_report: no summary buffer");
-  HIPCHK(hipSetDevice(E->dev));
-  int rc = sync_stream(E);  // the receipts of the last delivery are folded on the delivery stream
-  if (rc) return rc;
-  launch_flow_cc_report(flow_args(E, 0, 0), E->d_pres.p, E->st);
-  HIPCHK(hipGetLastError());
   unsigned long long res[kFlowCcResWords];
-  HIPCHK(hipMemcpyAsync(res, E->d_pres.p, sizeof res, hipMemcpyDeviceToHost, E->st));
-  HIPCHK(hipStreamSynchronize(E->st));
+  int rc = flow_part_report(e, "flow_cc_report", kFlowCc, out, launch_flow_cc_report, res);
+  if (rc) return rc;
   *out = tgsim_flow_cc_summary{};
   out->loss_events = res[0];
   out->fast_retransmits = res[1];
@@ -3442,37 +3441,10 @@ int tgsim_flow_cc_report(void* e, tgsim_flow_cc_summary* out) {
   return 0;
 }
 
-int64_t tgsim_flow_rto_rows(void* e, uint64_t first, uint64_t n, tgsim_flow_rto_row* out, size_t cap) {
-  Eng* E = as_eng(e);
-  if (!E) return -EINVAL;
-  if (!E->flow_on || !E->flow_rto_on) return E->fail(-EINVAL, "flow_rto_rows: the RTT estimator is not armed (tgsim_flow_init_rto)");
-  if (first > E->n_flows || n > E->n_flows - first)
-    return E->fail(-EINVAL, "flow_rto_rows: flows [%llu, %llu) outside [0, %llu)", static_cast<unsigned long long>(first),
-                   static_cast<unsigned long long>(first + n), static_cast<unsigned long long>(E->n_flows));
-  if (cap < n) return E->fail(-ENOSPC, "flow_rto_rows: %zu rows for %llu", cap, static_cast<unsigned long long>(n));
-  if (n && !out) return E->fail(-EINVAL, "flow_rto_rows: no output buffer");
-  HIPCHK(hipSetDevice(E->dev));
-  int rc = sync_stream(E);
-  if (rc) return rc;
-  if (!n) return 0;
-  HIPCHK(hipMemcpyAsync(out, E->d_frt.p + first, sizeof(tgsim_flow_rto_row) * n, hipMemcpyDeviceToHost, E->st));
-  HIPCHK(hipStreamSynchronize(E->st));
-  return static_cast<int64_t>(n);
-}
-
 int tgsim_flow_rto_report(void* e, tgsim_flow_rto_summary* out) {
-  Eng* E = as_eng(e);
-  if (!E) return -EINVAL;
-  if (!E->flow_on || !E->flow_rto_on) return E->fail(-EINVAL, "flow_rto_report: the RTT estimator is not armed (tgsim_flow_init_rto)");
-  if (!out) return E->fail(-EINVAL, "flow_rto_report: no summary buffer");
-  HIPCHK(hipSetDevice(E->dev));
-  int rc = sync_stream(E);  // the receipts of the last delivery are folded on the delivery stream
-  if (rc) return rc;
-  launch_flow_rto_report(flow_args(E, 0, 0), E->d_pres.p, E->st);
-  HIPCHK(hipGetLastError());
   unsigned long long res[kFlowRtoResWords];
-  HIPCHK(hipMemcpyAsync(res, E->d_pres.p, sizeof res, hipMemcpyDeviceToHost, E->st));
-  HIPCHK(hipStreamSynchronize(E->st));
+  int rc = flow_part_report(e, "flow_rto_report", kFlowRto, out, launch_flow_rto_report, res);
+  if (rc) return rc;
   out->samples = res[0];
   out->sampled_flows = res[1];
   out->srtt_sum = res[2];
@@ -3484,37 +3456,10 @@ int tgsim_flow_rto_report(void* e, tgsim_flow_rto_summary* out) {
   return 0;
 }
 
-int64_t tgsim_flow_fb_rows(void* e, uint64_t first, uint64_t n, tgsim_flow_fb_row* out, size_t cap) {
-  Eng* E = as_eng(e);
-  if (!E) return -EINVAL;
-  if (!E->flow_on || !E->flow_fb_on) return E->fail(-EINVAL, "flow_fb_rows: verdict feedback is not armed (tgsim_flow_init_fb)");
-  if (first > E->n_flows || n > E->n_flows - first)
-    return E->fail(-EINVAL, "flow_fb_rows: flows [%llu, %llu) outside [0, %llu)", static_cast<unsigned long long>(first),
-                   static_cast<unsigned long long>(first + n), static_cast<unsigned long long>(E->n_flows));
-  if (cap < n) return E->fail(-ENOSPC, "flow_fb_rows: %zu rows for %llu", cap, static_cast<unsigned long long>(n));
-  if (n && !out) return E->fail(-EINVAL, "flow_fb_rows: no output buffer");
-  HIPCHK(hipSetDevice(E->dev));
-  int rc = sync_stream(E);
-  if (rc) return rc;
-  if (!n) return 0;
-  HIPCHK(hipMemcpyAsync(out, E->d_ffb.p + first, sizeof(tgsim_flow_fb_row) * n, hipMemcpyDeviceToHost, E->st));
-  HIPCHK(hipStreamSynchronize(E->st));
-  return static_cast<int64_t>(n);
-}
-
 int tgsim_flow_fb_report(void* e, tgsim_flow_fb_summary* out) {
-  Eng* E = as_eng(e);
-  if (!E) return -EINVAL;
-  if (!E->flow_on || !E->flow_fb_on) return E->fail(-EINVAL, "flow_fb_report: verdict feedback is not armed (tgsim_flow_init_fb)");
-  if (!out) return E->fail(-EINVAL, "flow_fb_report: no summary buffer");
-  HIPCHK(hipSetDevice(E->dev));
-  int rc = sync_stream(E);  // the last window's fold runs on the simulate stream, its receipts on the delivery stream
-  if (rc) return rc;
-  launch_flow_fb_report(flow_args(E, 0, 0), E->d_pres.p, E->st);
-  HIPCHK(hipGetLastError());
   unsigned long long res[kFlowFbResWords];
-  HIPCHK(hipMemcpyAsync(res, E->d_pres.p, sizeof res, hipMemcpyDeviceToHost, E->st));
-  HIPCHK(hipStreamSynchronize(E->st));
+  int rc = flow_part_report(e, "flow_fb_report", kFlowFb, out, launch_flow_fb_report, res);
+  if (rc) return rc;
   *out = tgsim_flow_fb_summary{};
   out->scheduled = res[0];
   out->lost = res[1];
@@ -3599,9 +3544,7 @@ int tgsim_step_sim_launch(void* e, uint32_t n_ticks, uint32_t n_ranks, const uin
   if (!E || n_ticks == 0 || n_ranks == 0 || n_ranks > 8 || !bounds || (!d_out && out_cap)) return -EINVAL;
   if (bounds[0] != 0 || bounds[n_ranks] != E->N) return E->fail(-EINVAL, "rank bounds must cover [0, n_peers)");
   if (E->route_n == Eng::kRouteSlots) return E->fail(-EBUSY, "two launched steps are not finished yet");
-  if (E->ping_on && !E->ping_sharded)
-    return E->fail(-EBUSY, "%s: the ping driver is armed (tgsim_ping_init(engine, NULL, NULL) disarms it)", "step_sim_launch");
-  if (E->flow_on) return E->fail(-EBUSY, "%s: the flow driver is armed (tgsim_flow_init(engine, NULL, NULL, 0) disarms it)", "step_sim_launch");
+  if (int brc = driver_busy(E, "step_sim_launch", true)) return brc;
   HIPCHK(hipSetDevice(E->dev));
   int rc = run_sim(E, n_ticks);
   if (rc) return rc;
@@ -3630,9 +3573,7 @@ static int step_sim_launch_slotted(void* e, uint32_t n_ticks, uint32_t n_ranks, 
   if (!E || n_ticks == 0 || n_ranks == 0 || n_ranks > 8 || !bounds || !d_out || slot_cap == 0) return -EINVAL;
   if (bounds[0] != 0 || bounds[n_ranks] != E->N) return E->fail(-EINVAL, "rank bounds must cover [0, n_peers)");
   if (E->route_n == Eng::kRouteSlots) return E->fail(-EBUSY, "two launched steps are not released yet");
-  if (E->ping_on && !(route1 && E->ping_sharded))
-    return E->fail(-EBUSY, "%s: the ping driver is armed (tgsim_ping_init(engine, NULL, NULL) disarms it)", "step_sim_launch_slotted");
-  if (E->flow_on) return E->fail(-EBUSY, "%s: the flow driver is armed (tgsim_flow_init(engine, NULL, NULL, 0) disarms it)", "step_sim_launch_slotted");
+  if (int brc = driver_busy(E, "step_sim_launch_slotted", route1)) return brc;
   HIPCHK(hipSetDevice(E->dev));
   int rc = run_sim(E, n_ticks);
   if (rc) return rc;
@@ -3655,8 +3596,7 @@ int tgsim_step_sim_launch_slotted_n(void* e, uint32_t n_ticks, uint32_t n_win, u
     return tgsim_step_sim_launch_slotted(e, n_ticks, n_ranks, bounds, d_out, slot_cap, routed_event);
   if (bounds[0] != 0 || bounds[n_ranks] != E->N) return E->fail(-EINVAL, "rank bounds must cover [0, n_peers)");
   if (E->route_n == Eng::kRouteSlots) return E->fail(-EBUSY, "two launched steps are not released yet");
-  if (E->ping_on) return E->fail(-EBUSY, "%s: the ping driver is armed (tgsim_ping_init(engine, NULL, NULL) disarms it)", "step_sim_launch_slotted_n");
-  if (E->flow_on) return E->fail(-EBUSY, "%s: the flow driver is armed (tgsim_flow_init(engine, NULL, NULL, 0) disarms it)", "step_sim_launch_slotted_n");
+  if (int brc = driver_busy(E, "step_sim_launch_slotted_n")) return brc;
   HIPCHK(hipSetDevice(E->dev));
   if (!fusable(E, n_ticks, n_win, true))
     return E->fail(-EINVAL, "step_sim_launch_slotted_n: the next %u windows are not generated dense windows of %u ticks",

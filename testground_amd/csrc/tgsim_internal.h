@@ -337,61 +337,61 @@ struct GossipSpreadArgs {
   uint32_t bin_ticks, bin_rcp, n_bins;  // bin_rcp = fastmod_rcp(bin_ticks); n_bins 0: no histogram
 };
 
-// Ping mesh driver (tgsim_ping_*, DESIGN.md §5.6).  An engine armed through tgsim_ping_init owns every
-// peer; tgsim_ping_init_sharded arms one that owns [first, first + n_own): the target table is the whole
-// run's, everything else (pair table, slot counts, row cursors, the generated window's offsets) is
-// indexed by owned peer.
-constexpr uint32_t kPingMaxBins = 256;
-constexpr uint32_t kPingReplicas = 8;  // RTT histogram tables the workgroups' flushes are spread over
-// A reply waiting for its tick (16 B): made by k_ping_recv from a delivered request, consumed by the
-// generation of the window that holds its tick.
-struct alignas(16) PingCal {
+// Reply calendar: the replies (ping) or ACKs (flow) that delivered requests make, each
+// waiting for the window that holds its tick.  The ping and the flow driver hold it in turn.
+constexpr uint32_t kCalMaxBins = 256;
+constexpr uint32_t kCalReplicas = 8;  // histogram tables the workgroups' flushes are spread over
+// An entry (16 B): made by the holder's receipt kernel from a delivered request.
+struct alignas(16) CalEntry {
   uint32_t tick;       // absolute tick at which `responder` offers the reply
   uint32_t responder;  // the request's destination
   uint32_t requester;  // the request's source
   uint32_t seq;        // the request's sequence number
 };
-static_assert(sizeof(PingCal) == 16, "PingCal must stay 16 B");
-// The driver's counters (u64 words in device memory; the first kPingPubWords are published to the
-// host at every generation).
-enum PingCtr {
-  kPcCal0 = 0, kPcCal1 = 1,  // entries in calendar buffer 0 / 1
-  kPcDup = 2, kPcCorrupt = 3,  // records ignored for TGSIM_FLAG_DUP / TGSIM_FLAG_CORRUPT
-  kPcLate = 4,      // the earliest calendar tick that preceded a generated window (all-ones: none)
-  kPcOverflow = 5,  // entries that found the calendar full (never written)
-  kPcOffers = 6,    // flow driver: data packets the window being generated offers (count pass)
-  kPingPubWords = 7,
-  kPingCtrWords = 8
+static_assert(sizeof(CalEntry) == 16, "CalEntry must stay 16 B");
+// Its u64 counters in device memory (the first kCalPubWords reach the host at every generation).
+enum CalCtr {
+  kCalBuf0 = 0, kCalBuf1 = 1,  // entries in calendar buffer 0 / 1
+  kCalDup = 2, kCalCorrupt = 3,  // records ignored for TGSIM_FLAG_DUP / TGSIM_FLAG_CORRUPT
+  kCalLate = 4,      // the earliest calendar tick that preceded a generated window (all-ones: none)
+  kCalOverflow = 5,  // entries that found the calendar full (never written)
+  kCalOffers = 6,    // flow driver: data packets the window being generated offers (count pass)
+  kCalPubWords = 7, kCalCtrWords = 8
 };
+// What the k_cal_* kernels and the holder's histogram flushes need; either driver's first member.
+struct CalArgs {
+  unsigned long long* hist;  // [kCalReplicas][kCalMaxBins]
+  unsigned long long* ctr;   // [kCalCtrWords]
+  CalEntry* cal;             // the calendar being appended to / read
+  CalEntry* cal_next;        // generation: the entries not yet due move here
+  uint64_t cal_cap;          // entries either calendar buffer holds
+  uint32_t cal_cur, n_peers;  // cal_cur 0 / 1: which counter belongs to `cal`
+  uint32_t first, n_own;     // the owned peers [first, first + n_own); a whole-peer engine: 0, n_peers
+  uint32_t len, n_bins;      // bytes of a reply; histogram bins (0: none)
+  uint64_t tick_ns, bin_ns, win0;  // generation of the window [win0, win0 + n_ticks)
+  uint32_t n_ticks;
+};
+// Ping mesh driver (tgsim_ping_*, DESIGN.md §5.6).  An engine armed through tgsim_ping_init owns every
+// peer; tgsim_ping_init_sharded arms one that owns [first, first + n_own): the target table is the whole
+// run's, everything else (pair table, slot counts, row cursors, the generated window's offsets) is
+// indexed by owned peer.
 struct PingArgs {
+  CalArgs cal;
   const uint32_t* targets;   // [n_peers][fanout], the whole run's
   tgsim_ping_pair* pairs;    // [n_own][fanout]; `sent` is filled in by the readers
-  unsigned long long* hist;  // [kPingReplicas][kPingMaxBins]
-  unsigned long long* ctr;   // [kPingCtrWords]
-  PingCal* cal;              // the calendar being appended to / read
-  PingCal* cal_next;         // generation: the entries not yet due move here
-  uint64_t cal_cap;          // entries either calendar buffer holds
-  uint32_t cal_cur;          // 0 / 1: which counter belongs to `cal`
-  uint32_t n_peers, fanout, count, interval, len, n_bins;
-  uint32_t first, n_own;     // the owned peers [first, first + n_own); a whole-peer engine: 0, n_peers
-  uint64_t start, tick_ns, bin_ns;
-  // generation of the window [win0, win0 + n_ticks): its scheduled probes are j_lo <= j < j_hi
-  uint64_t win0;
-  uint32_t n_ticks, j_lo, j_hi;
-  uint32_t sent;             // reports: probes per slot offered so far
+  uint64_t start;
+  uint32_t fanout, count, interval;
+  uint32_t j_lo, j_hi, sent;  // the window's scheduled probes j_lo <= j < j_hi; reports: probes per slot so far
 };
-
-// Flow driver (tgsim_flow_*) of an engine that owns every peer.  Its ACK calendar is
-// the ping driver's (PingCal, the kPc* counters, k_ping_count_cal / k_ping_write_cal / k_ping_order):
-// `cal` carries the calendar's buffers and counters, the window and ack_len as `len`.
 constexpr uint32_t kPingResWords = 8;   // pairs sent received sum min max pairs_all pairs_none
 // tgsim_comm_ping_report's packed words: [0, kPingPackSums + n_bins) sums (the summary's nine summed
 // fields in tgsim_ping_summary order, then the histogram), then min_ns, then max_ns.
 constexpr uint32_t kPingPackSums = 9;
-constexpr uint32_t kPingPackWords = kPingPackSums + kPingMaxBins + 2;
+constexpr uint32_t kPingPackWords = kPingPackSums + kCalMaxBins + 2;
+// Flow driver (tgsim_flow_*) of an engine that owns every peer; its ACKs are `cal`'s entries.
 constexpr uint32_t kFlowResWords = 11;  // flows done failed active segs offered retransmits stale fct_sum fct_min fct_max
 struct FlowArgs {
-  PingArgs cal;
+  CalArgs cal;
   const tgsim_flow_spec* spec;  // [n_flows], sorted by src
   tgsim_flow_row* rows;         // [n_flows]
   uint64_t* bitmap;             // [n_flows] acknowledged segments of [base, base + 64)
@@ -458,7 +458,7 @@ uint64_t engine_ping_fault(void* engine, int rank, bool* agreed);
 // it: -EINVAL for a late receipt, -ENOSPC for a full calendar; the text names the rank.
 int engine_ping_fail_agreed(void* engine, uint64_t word);
 // The local report's words on the device for tgsim_comm_ping_report, after k_ping_report on the
-// simulate stream: res = [kPingResWords + n_bins], ctr = the driver's counters (kPc*); cal_word is the
+// simulate stream: res = [kPingResWords + n_bins], ctr = the driver's counters (kCal*); cal_word is the
 // counter of the live calendar.  `ev` is recorded behind them.
 int engine_ping_report_dev(void* engine, const unsigned long long** res, const unsigned long long** ctr,
                            uint32_t* cal_word, uint32_t* n_bins, hipEvent_t ev);

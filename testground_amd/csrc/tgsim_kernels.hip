@@ -14,6 +14,7 @@
 //                  by (t, src, seq, clone-first).
 #include <errno.h>
 #include <stdlib.h>
+#include <type_traits>
 #include "tgsim_fastmod.h"
 #include "tgsim_launch.h"
 
@@ -3195,21 +3196,21 @@ __global__ __launch_bounds__(256) void k_gossip_times(const uint32_t* __restrict
 // k_ping_recv: one pass over a window's delivery-ordered records (n = off[n_dst], read here: the host
 // knows only a bound).  A request becomes a calendar entry; a reply credits its pair (a pair sees at
 // most `count` of these atomics in a whole run) and the workgroup's RTT histogram in LDS, flushed to
-// replica blockIdx mod kPingReplicas.  A workgroup takes tiles of 1,024 records and claims the
+// replica blockIdx mod kCalReplicas.  A workgroup takes tiles of 1,024 records and claims the
 // calendar slots of a tile with ONE atomic (wave scan, then the four wave totals through LDS): adds
 // to one address serialize at ~12 ns each, and one per wavefront (50,000 a window at 100,000 peers,
 // fanout 8) made this pass 1.25 ms long; one per tile makes it 3,100.
-constexpr uint32_t kPingRecvItems = 4;
+constexpr uint32_t kCalTileItems = 4;
 // The calendar append of one tile, shared by the ping and the flow receipts (every thread of the
 // 256-thread workgroup calls it, once per tile): the tile's entries take consecutive slots behind
 // ONE claim.  w_cnt[4] and s_base are the workgroup's LDS scratch.
-__device__ __forceinline__ void cal_append_tile(const PingArgs& a, const PingCal (&e)[kPingRecvItems],
-                                                const bool (&request)[kPingRecvItems], uint32_t* w_cnt,
+__device__ __forceinline__ void cal_append_tile(const CalArgs& a, const CalEntry (&e)[kCalTileItems],
+                                                const bool (&request)[kCalTileItems], uint32_t* w_cnt,
                                                 unsigned long long* s_base) {
   const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
   uint32_t c = 0;
 #pragma unroll
-  for (uint32_t u = 0; u < kPingRecvItems; ++u) c += request[u] ? 1u : 0u;
+  for (uint32_t u = 0; u < kCalTileItems; ++u) c += request[u] ? 1u : 0u;
   const uint32_t incl = (uint32_t)scan_sum_i32((int32_t)c);
   const uint32_t w_tot = readlane32(incl, kWave - 1);
   if (lane == 0) w_cnt[wv] = w_tot;
@@ -3220,7 +3221,7 @@ __device__ __forceinline__ void cal_append_tile(const PingArgs& a, const PingCal
     if (tot) {
       at = atomicAdd(&a.ctr[a.cal_cur], (unsigned long long)tot);
       if (at + tot > a.cal_cap) {  // (the host sizes the calendar for every probe in flight)
-        atomicAdd(&a.ctr[kPcOverflow], (unsigned long long)tot);
+        atomicAdd(&a.ctr[kCalOverflow], (unsigned long long)tot);
         atomicAdd(&a.ctr[a.cal_cur], 0ull - tot);
         at = ~0ull;
       }
@@ -3232,57 +3233,58 @@ __device__ __forceinline__ void cal_append_tile(const PingArgs& a, const PingCal
     uint64_t pos = *s_base + (incl - c);
     for (uint32_t w = 0; w < wv; ++w) pos += w_cnt[w];
 #pragma unroll
-    for (uint32_t u = 0; u < kPingRecvItems; ++u)
+    for (uint32_t u = 0; u < kCalTileItems; ++u)
       if (request[u]) a.cal[pos++] = e[u];
   }
   __syncthreads();  // (w_cnt and s_base are the next tile's)
 }
 
-__global__ __launch_bounds__(256) void k_ping_recv(PingArgs a, const tgsim_delivery* __restrict__ recs,
+__global__ __launch_bounds__(256) void k_ping_recv(PingArgs p, const tgsim_delivery* __restrict__ recs,
                                                    const uint64_t* __restrict__ off, uint32_t n_dst, uint64_t n_bound) {
-  __shared__ uint32_t hist[kPingMaxBins];
+  __shared__ uint32_t hist[kCalMaxBins];
+  const CalArgs& a = p.cal;
   __shared__ uint32_t w_cnt[4];
   __shared__ unsigned long long s_base;
   for (uint32_t i = threadIdx.x; i < a.n_bins; i += 256) hist[i] = 0u;
   __syncthreads();
   const uint64_t n = off[n_dst] < n_bound ? off[n_dst] : n_bound;  // (never past the buffer the bound sized)
   const uint32_t lane = threadIdx.x & 63u;
-  const uint64_t tile = 256 * kPingRecvItems;
-  const uint32_t n_req = a.count * a.fanout;  // (count <= 65535, fanout <= 64)
+  const uint64_t tile = 256 * kCalTileItems;
+  const uint32_t n_req = p.count * p.fanout;  // (count <= 65535, fanout <= 64)
   uint32_t dups = 0, cors = 0;
   for (uint64_t base = blockIdx.x * tile; base < n; base += gridDim.x * tile) {  // (uniform in the workgroup)
-    PingCal e[kPingRecvItems];
-    bool request[kPingRecvItems];
+    CalEntry e[kCalTileItems];
+    bool request[kCalTileItems];
 #pragma unroll
-    for (uint32_t u = 0; u < kPingRecvItems; ++u) {
+    for (uint32_t u = 0; u < kCalTileItems; ++u) {
       const uint64_t i = base + u * 256 + threadIdx.x;
       request[u] = false;
-      e[u] = PingCal{};
+      e[u] = CalEntry{};
       if (i >= n) continue;
       const tgsim_delivery r = recs[i];
-      const uint32_t q = r.seq & 0x7FFFFFFFu, k = q % a.fanout, j = q / a.fanout;
+      const uint32_t q = r.seq & 0x7FFFFFFFu, k = q % p.fanout, j = q / p.fanout;
       if (r.flags & TGSIM_FLAG_DUP) {
         ++dups;
       } else if (r.flags & TGSIM_FLAG_CORRUPT) {
         ++cors;
       } else if (!(r.seq >> 31)) {
-        if (q < n_req && r.src < a.n_peers && a.targets[(uint64_t)r.src * a.fanout + k] == r.dst) {
+        if (q < n_req && r.src < a.n_peers && p.targets[(uint64_t)r.src * p.fanout + k] == r.dst) {
           request[u] = true;
           e[u].tick = (uint32_t)(r.t_ns / a.tick_ns + 1);
           e[u].responder = r.dst;
           e[u].requester = r.src;
           e[u].seq = r.seq;
         }
-      } else if (j < a.count && r.dst - a.first < a.n_own && a.targets[(uint64_t)r.dst * a.fanout + k] == r.src) {
+      } else if (j < p.count && r.dst - a.first < a.n_own && p.targets[(uint64_t)r.dst * p.fanout + k] == r.src) {
         // (an owned requester only: first + n_own <= n_peers, and r.dst below first wraps past n_own)
-        const uint64_t t0 = (a.start + (uint64_t)j * a.interval) * a.tick_ns;
+        const uint64_t t0 = (p.start + (uint64_t)j * p.interval) * a.tick_ns;
         if (r.t_ns >= t0) {
           const uint64_t rtt = r.t_ns - t0;
-          tgsim_ping_pair* p = a.pairs + (uint64_t)(r.dst - a.first) * a.fanout + k;
-          atomicAdd(&p->received, 1u);
-          atomicAdd(reinterpret_cast<unsigned long long*>(&p->sum_ns), (unsigned long long)rtt);
-          atomicMin(reinterpret_cast<unsigned long long*>(&p->min_ns), (unsigned long long)rtt);
-          atomicMax(reinterpret_cast<unsigned long long*>(&p->max_ns), (unsigned long long)rtt);
+          tgsim_ping_pair* pr = p.pairs + (uint64_t)(r.dst - a.first) * p.fanout + k;
+          atomicAdd(&pr->received, 1u);
+          atomicAdd(reinterpret_cast<unsigned long long*>(&pr->sum_ns), (unsigned long long)rtt);
+          atomicMin(reinterpret_cast<unsigned long long*>(&pr->min_ns), (unsigned long long)rtt);
+          atomicMax(reinterpret_cast<unsigned long long*>(&pr->max_ns), (unsigned long long)rtt);
           if (a.n_bins) {
             const uint64_t b = rtt / a.bin_ns;
             atomicAdd(&hist[b < a.n_bins ? (uint32_t)b : a.n_bins - 1], 1u);
@@ -3294,11 +3296,11 @@ __global__ __launch_bounds__(256) void k_ping_recv(PingArgs a, const tgsim_deliv
   }
   const uint64_t td = wave_sum(dups), tc = wave_sum(cors);
   if (lane == 0) {
-    if (td) atomicAdd(&a.ctr[kPcDup], (unsigned long long)td);
-    if (tc) atomicAdd(&a.ctr[kPcCorrupt], (unsigned long long)tc);
+    if (td) atomicAdd(&a.ctr[kCalDup], (unsigned long long)td);
+    if (tc) atomicAdd(&a.ctr[kCalCorrupt], (unsigned long long)tc);
   }
   __syncthreads();
-  unsigned long long* rep = a.hist + (uint64_t)(blockIdx.x % kPingReplicas) * kPingMaxBins;
+  unsigned long long* rep = a.hist + (uint64_t)(blockIdx.x % kCalReplicas) * kCalMaxBins;
   for (uint32_t i = threadIdx.x; i < a.n_bins; i += 256)
     if (hist[i]) atomicAdd(&rep[i], (unsigned long long)hist[i]);
 }
@@ -3308,19 +3310,19 @@ __global__ __launch_bounds__(256) void k_ping_recv(PingArgs a, const tgsim_deliv
 __global__ __launch_bounds__(256) void k_ping_count_sched(PingArgs a, const uint32_t* __restrict__ n_slots,
                                                           uint64_t* counts, uint32_t* cursor) {
   const uint32_t s = blockIdx.x * 256 + threadIdx.x;  // (owned source first + s)
-  if (s >= a.n_own) return;
+  if (s >= a.cal.n_own) return;
   const uint32_t c = n_slots[s] * (a.j_hi - a.j_lo);
   counts[s] = c;
   cursor[s] = c;
 }
 
 // ... and the calendar entries due in it, counted on their responder; an entry before the window is a
-// late receipt (kPcLate keeps the earliest such tick).
-__global__ __launch_bounds__(256) void k_ping_count_cal(PingArgs a, uint64_t* counts) {
+// late receipt (kCalLate keeps the earliest such tick).
+__global__ __launch_bounds__(256) void k_cal_count(CalArgs a, uint64_t* counts) {
   const uint64_t n = a.ctr[a.cal_cur], win1 = a.win0 + a.n_ticks;
   for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256) {
-    const PingCal e = a.cal[i];
-    if (e.tick < a.win0) atomicMin(&a.ctr[kPcLate], (unsigned long long)e.tick);
+    const CalEntry e = a.cal[i];
+    if (e.tick < a.win0) atomicMin(&a.ctr[kCalLate], (unsigned long long)e.tick);
     else if (e.tick < win1 && e.responder - a.first < a.n_own)  // (an entry of another shard's responder cannot occur)
       atomicAdd(reinterpret_cast<unsigned long long*>(&counts[e.responder - a.first]), 1ull);
   }
@@ -3330,8 +3332,8 @@ __global__ __launch_bounds__(256) void k_ping_count_cal(PingArgs a, uint64_t* co
 // to (j - j_lo) * n_slots + k of the source's row, which is the row's (tick, seq) order already.
 __global__ __launch_bounds__(256) void k_ping_write_sched(PingArgs a, const uint64_t* __restrict__ off, InRec* out) {
   const uint32_t s = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
-  if (s >= a.n_own) return;
-  const uint32_t tgt = lane < a.fanout ? a.targets[((uint64_t)a.first + s) * a.fanout + lane] : TGSIM_PING_NONE;
+  if (s >= a.cal.n_own) return;
+  const uint32_t tgt = lane < a.fanout ? a.targets[((uint64_t)a.cal.first + s) * a.fanout + lane] : TGSIM_PING_NONE;
   const uint64_t m = __ballot(tgt != TGSIM_PING_NONE);
   if (tgt == TGSIM_PING_NONE) return;
   const uint32_t ns = (uint32_t)__popcll(m), rank = (uint32_t)__popcll(m & ((1ull << lane) - 1));
@@ -3340,8 +3342,8 @@ __global__ __launch_bounds__(256) void k_ping_write_sched(PingArgs a, const uint
     InRec rec;
     rec.dst = tgt;
     rec.seq = j * a.fanout + lane;
-    rec.tick = (uint32_t)(a.start + (uint64_t)j * a.interval - a.win0);
-    rec.len = a.len;
+    rec.tick = (uint32_t)(a.start + (uint64_t)j * a.interval - a.cal.win0);
+    rec.len = a.cal.len;
     out[o + (uint64_t)(j - a.j_lo) * ns + rank] = rec;
   }
 }
@@ -3349,7 +3351,7 @@ __global__ __launch_bounds__(256) void k_ping_write_sched(PingArgs a, const uint
 // The calendar: an entry due in the window becomes a reply behind its responder's scheduled probes
 // (the cursor; the order pass sorts the row), an entry not yet due moves to the other buffer (one
 // atomic per workgroup and 256 entries, as in k_ping_recv).  Runs only when no entry is late.
-__global__ __launch_bounds__(256) void k_ping_write_cal(PingArgs a, const uint64_t* __restrict__ off, uint32_t* cursor,
+__global__ __launch_bounds__(256) void k_cal_write(CalArgs a, const uint64_t* __restrict__ off, uint32_t* cursor,
                                                         InRec* out) {
   __shared__ uint32_t w_cnt[4];
   __shared__ unsigned long long s_base;
@@ -3358,7 +3360,7 @@ __global__ __launch_bounds__(256) void k_ping_write_cal(PingArgs a, const uint64
   for (uint64_t base = (uint64_t)blockIdx.x * 256; base < n; base += (uint64_t)gridDim.x * 256) {
     const uint64_t i = base + threadIdx.x;
     bool keep = false;
-    PingCal e{};
+    CalEntry e{};
     if (i < n) {
       e = a.cal[i];
       keep = e.tick >= win1;
@@ -3393,7 +3395,7 @@ __global__ __launch_bounds__(256) void k_ping_write_cal(PingArgs a, const uint64
 // entry, the entries before it (the keys are distinct; the index breaks a tie all the same, so the
 // ranks are a permutation).  A row of up to 64 entries is compared in LDS, one entry per lane; a longer
 // one (a hot responder) against the row in memory, a broadcast load per comparison.
-__global__ __launch_bounds__(256) void k_ping_order(const uint64_t* __restrict__ off, const InRec* __restrict__ in,
+__global__ __launch_bounds__(256) void k_cal_order(const uint64_t* __restrict__ off, const InRec* __restrict__ in,
                                                     InRec* __restrict__ out, uint32_t n_src) {
   __shared__ uint64_t k_hi[4][kWave];
   __shared__ uint32_t k_lo[4][kWave];
@@ -3435,9 +3437,9 @@ __global__ __launch_bounds__(256) void k_ping_order(const uint64_t* __restrict__
 }
 
 // tgsim_ping_report.  res: [0] pairs [1] sent [2] received [3] sum [4] min [5] max [6] pairs_all
-// [7] pairs_none, then n_bins histogram words.  k_ping_report_init sets the neutral values and folds
-// the histogram replicas; k_ping_report is one pass over the shard's [n_own][fanout] pair table: a
-// workgroup reduces in LDS and ends with one set of atomics.
+// [7] pairs_none, then n_bins histogram words.  k_cal_report_init sets the neutral values and folds
+// the histogram replicas; k_ping_report is one pass over the shard's [n_own][fanout] pair table, closed
+// by report_commit below.
 __device__ __forceinline__ uint64_t wave_min_max_u64(uint64_t v, bool want_max) {  // (every lane takes part)
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
@@ -3448,64 +3450,77 @@ __device__ __forceinline__ uint64_t wave_min_max_u64(uint64_t v, bool want_max) 
   }
   return v;
 }
-// (n_words result words ahead of the histogram, word min_word a minimum: the flow report's too)
-__global__ __launch_bounds__(256) void k_ping_report_init(PingArgs a, unsigned long long* res, uint32_t n_words,
-                                                          uint32_t min_word) {
+// (n_words result words ahead of the n_bins histogram words to fold, word min_word a minimum)
+__global__ __launch_bounds__(256) void k_cal_report_init(CalArgs a, unsigned long long* res, uint32_t n_words,
+                                                         uint32_t min_word, uint32_t n_bins) {
   const uint32_t i = threadIdx.x;
   if (i < n_words) res[i] = i == min_word ? ~0ull : 0ull;
-  if (i < a.n_bins) {
+  if (i < n_bins) {
     unsigned long long v = 0;
-    for (uint32_t r = 0; r < kPingReplicas; ++r) v += a.hist[(uint64_t)r * kPingMaxBins + i];
+    for (uint32_t r = 0; r < kCalReplicas; ++r) v += a.hist[(uint64_t)r * kCalMaxBins + i];
     res[n_words + i] = v;
   }
 }
 
-__global__ __launch_bounds__(256) void k_ping_report(PingArgs a, unsigned long long* res) {
-  __shared__ unsigned long long acc[kPingResWords];
-  if (threadIdx.x < kPingResWords) acc[threadIdx.x] = threadIdx.x == 4 ? ~0ull : 0ull;
+// The report kernels' epilogue (every thread of the 256-thread workgroup calls it once, behind its
+// grid-stride loop): v holds the thread's N partial words; bit w of MIN / MAX makes word w a minimum /
+// a maximum, every other word is a sum.  Wave reduction, accumulation in LDS, then one atomic per
+// word into res, which the launcher initialised to the neutral values (0; all-ones for a minimum).
+// A word the workgroup leaves neutral is not committed: adding 0, the minimum with all-ones and the
+// maximum with 0 each return res[w] as it was, so skipping them is the same result whichever rule a
+// kernel had of its own (a workgroup that saw no row, a word that stayed zero).
+template <uint32_t N, uint32_t MIN, uint32_t MAX>
+__device__ __forceinline__ void report_commit(const uint64_t (&v)[N], unsigned long long* res) {
+  __shared__ unsigned long long acc[N];
+  if (threadIdx.x < N) acc[threadIdx.x] = (MIN >> threadIdx.x & 1u) ? ~0ull : 0ull;
   __syncthreads();
-  const uint64_t n = (uint64_t)a.n_own * a.fanout, t0 = (uint64_t)a.first * a.fanout;
-  uint64_t pairs = 0, received = 0, sum = 0, mn = ~0ull, mx = 0, all = 0, none = 0;
+#pragma unroll
+  for (uint32_t w = 0; w < N; ++w) {
+    constexpr uint32_t one = 1u;
+    const bool mn = MIN & (one << w), mx = MAX & (one << w);
+    const uint64_t t = mn ? wave_min_max_u64(v[w], false) : mx ? wave_min_max_u64(v[w], true) : wave_sum(v[w]);
+    if ((threadIdx.x & 63u) == 0) {
+      if (mn) atomicMin(&acc[w], (unsigned long long)t);
+      else if (mx) atomicMax(&acc[w], (unsigned long long)t);
+      else atomicAdd(&acc[w], (unsigned long long)t);
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x < N) {
+    const uint32_t w = threadIdx.x;
+    const unsigned long long x = acc[w];
+    if (MIN >> w & 1u) {
+      if (x != ~0ull) atomicMin(&res[w], x);
+    } else if (x) {
+      if (MAX >> w & 1u) atomicMax(&res[w], x);
+      else atomicAdd(&res[w], x);
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void k_ping_report(PingArgs a, unsigned long long* res) {
+  const uint64_t n = (uint64_t)a.cal.n_own * a.fanout, t0 = (uint64_t)a.cal.first * a.fanout;
+  uint64_t v[kPingResWords] = {};
+  v[4] = ~0ull;
   for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256) {
     if (a.targets[t0 + i] == TGSIM_PING_NONE) continue;
     const tgsim_ping_pair p = a.pairs[i];
-    ++pairs;
-    received += p.received;
-    sum += p.sum_ns;
-    mn = p.min_ns < mn ? p.min_ns : mn;
-    mx = p.max_ns > mx ? p.max_ns : mx;
-    all += a.sent && p.received == a.sent;
-    none += a.sent && p.received == 0;
+    ++v[0];
+    v[2] += p.received;
+    v[3] += p.sum_ns;
+    v[4] = p.min_ns < v[4] ? p.min_ns : v[4];
+    v[5] = p.max_ns > v[5] ? p.max_ns : v[5];
+    v[6] += a.sent && p.received == a.sent;
+    v[7] += a.sent && p.received == 0;
   }
-  const uint64_t t_pairs = wave_sum(pairs), t_recv = wave_sum(received), t_sum = wave_sum(sum), t_all = wave_sum(all),
-                 t_none = wave_sum(none);
-  const uint64_t t_mn = wave_min_max_u64(mn, false), t_mx = wave_min_max_u64(mx, true);
-  if ((threadIdx.x & 63u) == 0) {
-    atomicAdd(&acc[0], (unsigned long long)t_pairs);
-    atomicAdd(&acc[2], (unsigned long long)t_recv);
-    atomicAdd(&acc[3], (unsigned long long)t_sum);
-    atomicMin(&acc[4], (unsigned long long)t_mn);
-    atomicMax(&acc[5], (unsigned long long)t_mx);
-    atomicAdd(&acc[6], (unsigned long long)t_all);
-    atomicAdd(&acc[7], (unsigned long long)t_none);
-  }
-  __syncthreads();
-  if (threadIdx.x == 0 && acc[0]) {
-    atomicAdd(&res[0], acc[0]);
-    atomicAdd(&res[1], acc[0] * a.sent);
-    atomicAdd(&res[2], acc[2]);
-    atomicAdd(&res[3], acc[3]);
-    atomicMin(&res[4], acc[4]);
-    atomicMax(&res[5], acc[5]);
-    atomicAdd(&res[6], acc[6]);
-    atomicAdd(&res[7], acc[7]);
-  }
+  v[1] = v[0] * a.sent;  // (every pair has been offered `sent` probes)
+  report_commit<kPingResWords, 1u << 4, 1u << 5>(v, res);
 }
 
 // tgsim_ping_init: the pair table (no reply yet) and the histogram replicas.
 __global__ __launch_bounds__(256) void k_ping_init(PingArgs a) {
   const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i < (uint64_t)a.n_own * a.fanout) {
+  if (i < (uint64_t)a.cal.n_own * a.fanout) {
     tgsim_ping_pair p;
     p.sent = 0;
     p.received = 0;
@@ -3514,8 +3529,8 @@ __global__ __launch_bounds__(256) void k_ping_init(PingArgs a) {
     p.max_ns = 0;
     a.pairs[i] = p;
   }
-  if (i < kPingReplicas * kPingMaxBins) a.hist[i] = 0ull;
-  if (i < kPingCtrWords) a.ctr[i] = i == kPcLate ? ~0ull : 0ull;
+  if (i < kCalReplicas * kCalMaxBins) a.cal.hist[i] = 0ull;
+  if (i < kCalCtrWords) a.cal.ctr[i] = i == kCalLate ? ~0ull : 0ull;
 }
 
 // tgsim_ping_pairs: rows [i0, i0 + n) of the shard's pair table with `sent` filled in (an empty slot: 0).
@@ -3523,7 +3538,7 @@ __global__ __launch_bounds__(256) void k_ping_pairs(PingArgs a, uint64_t i0, uin
   const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
   tgsim_ping_pair p = a.pairs[i0 + i];
-  p.sent = a.targets[(uint64_t)a.first * a.fanout + i0 + i] == TGSIM_PING_NONE ? 0u : a.sent;
+  p.sent = a.targets[(uint64_t)a.cal.first * a.fanout + i0 + i] == TGSIM_PING_NONE ? 0u : a.sent;
   out[i] = p;
 }
 
@@ -3542,13 +3557,13 @@ __global__ __launch_bounds__(256) void k_ping_pack(const unsigned long long* __r
     out[3] = res[3];  // sum_ns
     out[4] = res[6];  // pairs_all
     out[5] = res[7];  // pairs_none
-    out[6] = ctr[kPcDup];
-    out[7] = ctr[kPcCorrupt];
+    out[6] = ctr[kCalDup];
+    out[7] = ctr[kCalCorrupt];
     out[8] = ctr[cal_word];  // pending_replies
     out[kPingPackSums + n_bins] = res[4];      // min_ns
     out[kPingPackSums + n_bins + 1] = res[5];  // max_ns
   }
-  if (i < n_bins) out[kPingPackSums + i] = res[kPingResWords + i];  // (n_bins <= kPingMaxBins = the workgroup)
+  if (i < n_bins) out[kPingPackSums + i] = res[kPingResWords + i];  // (n_bins <= kCalMaxBins = the workgroup)
 }
 
 // ... and the reduced runs as the tgsim_ping_summary (11 u64 words) followed by the histogram, in the
@@ -3564,13 +3579,13 @@ __global__ __launch_bounds__(256) void k_ping_unpack(const unsigned long long* _
     __hip_atomic_store(&host[11 + i], (uint64_t)in[kPingPackSums + i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
   __threadfence_system();
   __syncthreads();
-  if (i == 0) __hip_atomic_store(&host[11 + kPingMaxBins], seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+  if (i == 0) __hip_atomic_store(&host[11 + kCalMaxBins], seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
 // ---------------------------------------------------------------------------------------------
 // Flow driver (tgsim_flow_*): windowed transfers with per-segment ACKs and timers.
-// The ACK calendar is the ping driver's: cal_append_tile here, k_ping_count_cal / k_ping_write_cal /
-// k_ping_order in the generation, with f.cal as their arguments.
+// Its ACKs wait in the reply calendar it holds: cal_append_tile here, k_cal_count / k_cal_write /
+// k_cal_order in the generation, with f.cal as their arguments.
 __device__ __forceinline__ uint32_t flow_slot(uint32_t seq) { return seq >> 23 & 15u; }
 __device__ __forceinline__ uint32_t flow_seg(uint32_t seq) { return seq & 0x7FFFFFu; }
 
@@ -3581,18 +3596,18 @@ __global__ __launch_bounds__(256) void k_flow_recv_data(FlowArgs f, const tgsim_
                                                         const uint64_t* __restrict__ off, uint32_t n_dst, uint64_t n_bound) {
   __shared__ uint32_t w_cnt[4];
   __shared__ unsigned long long s_base;
-  const PingArgs& a = f.cal;
+  const CalArgs& a = f.cal;
   const uint64_t n = off[n_dst] < n_bound ? off[n_dst] : n_bound;
-  const uint64_t tile = 256 * kPingRecvItems;
+  const uint64_t tile = 256 * kCalTileItems;
   uint32_t dups = 0, cors = 0;
   for (uint64_t base = blockIdx.x * tile; base < n; base += gridDim.x * tile) {  // (uniform in the workgroup)
-    PingCal e[kPingRecvItems];
-    bool request[kPingRecvItems];
+    CalEntry e[kCalTileItems];
+    bool request[kCalTileItems];
 #pragma unroll
-    for (uint32_t u = 0; u < kPingRecvItems; ++u) {
+    for (uint32_t u = 0; u < kCalTileItems; ++u) {
       const uint64_t i = base + u * 256 + threadIdx.x;
       request[u] = false;
-      e[u] = PingCal{};
+      e[u] = CalEntry{};
       if (i >= n) continue;
       const tgsim_delivery r = recs[i];
       if (r.flags & TGSIM_FLAG_DUP) {
@@ -3614,8 +3629,8 @@ __global__ __launch_bounds__(256) void k_flow_recv_data(FlowArgs f, const tgsim_
   }
   const uint64_t td = wave_sum(dups), tc = wave_sum(cors);
   if ((threadIdx.x & 63u) == 0) {
-    if (td) atomicAdd(&a.ctr[kPcDup], (unsigned long long)td);
-    if (tc) atomicAdd(&a.ctr[kPcCorrupt], (unsigned long long)tc);
+    if (td) atomicAdd(&a.ctr[kCalDup], (unsigned long long)td);
+    if (tc) atomicAdd(&a.ctr[kCalCorrupt], (unsigned long long)tc);
   }
 }
 
@@ -3663,13 +3678,13 @@ __device__ __forceinline__ void flow_rto_sample(tgsim_flow_rto_row& q, uint32_t 
 // the ACKs take effect in: the lane walks its source's range and applies its own slot's ACKs (the
 // lanes of one source's flows are neighbours and read the same records).  Loops: the off[] range, and
 // at most `window` released (CC: and marked) segments per ACK.  A finished flow's FCT goes to the
-// workgroup's LDS histogram, flushed to replica blockIdx mod kPingReplicas.  RTO: a non-stale ACK of
+// workgroup's LDS histogram, flushed to replica blockIdx mod kCalReplicas.  RTO: a non-stale ACK of
 // attempt 0 is a sample, taken before anything else uses the ACK.
 template <bool CC, bool RTO>
 __global__ __launch_bounds__(256) void k_flow_recv_ack(FlowArgs f, const tgsim_delivery* __restrict__ recs,
                                                        const uint64_t* __restrict__ off, uint64_t n_bound) {
-  __shared__ uint32_t hist[kPingMaxBins];
-  const PingArgs& a = f.cal;
+  __shared__ uint32_t hist[kCalMaxBins];
+  const CalArgs& a = f.cal;
   for (uint32_t i = threadIdx.x; i < a.n_bins; i += 256) hist[i] = 0u;
   __syncthreads();
   const uint64_t fl = (uint64_t)blockIdx.x * 256 + threadIdx.x;
@@ -3785,7 +3800,7 @@ __global__ __launch_bounds__(256) void k_flow_recv_ack(FlowArgs f, const tgsim_d
     }
   }
   __syncthreads();
-  unsigned long long* rep = a.hist + (uint64_t)(blockIdx.x % kPingReplicas) * kPingMaxBins;
+  unsigned long long* rep = a.hist + (uint64_t)(blockIdx.x % kCalReplicas) * kCalMaxBins;
   for (uint32_t i = threadIdx.x; i < a.n_bins; i += 256)
     if (hist[i]) atomicAdd(&rep[i], (unsigned long long)hist[i]);
 }
@@ -3838,8 +3853,8 @@ __global__ __launch_bounds__(256) void k_flow_count(FlowArgs f, uint64_t* counts
   }
   const uint64_t tot = wave_sum(d.n), late = wave_min_max_u64(d.late == ~0u ? ~0ull : d.late, false);
   if ((threadIdx.x & 63u) == 0) {
-    if (tot) atomicAdd(&f.cal.ctr[kPcOffers], (unsigned long long)tot);
-    if (late != ~0ull) atomicMin(&f.cal.ctr[kPcLate], (unsigned long long)late);
+    if (tot) atomicAdd(&f.cal.ctr[kCalOffers], (unsigned long long)tot);
+    if (late != ~0ull) atomicMin(&f.cal.ctr[kCalLate], (unsigned long long)late);
   }
 }
 
@@ -3949,16 +3964,13 @@ __global__ __launch_bounds__(256) void k_flow_init(FlowArgs f) {
     }
     if (f.fb) f.fb[i] = tgsim_flow_fb_row{};
   }
-  if (i < kPingReplicas * kPingMaxBins) f.cal.hist[i] = 0ull;
-  if (i < kPingCtrWords) f.cal.ctr[i] = i == kPcLate ? ~0ull : 0ull;
+  if (i < kCalReplicas * kCalMaxBins) f.cal.hist[i] = 0ull;
+  if (i < kCalCtrWords) f.cal.ctr[i] = i == kCalLate ? ~0ull : 0ull;
 }
 
 // tgsim_flow_cc_report, as k_flow_report below: loss_events, fast_retransmits, timeouts over every
 // flow; the count, sum, minimum and maximum of cwnd over the ACTIVE ones.
 __global__ __launch_bounds__(256) void k_flow_cc_report(FlowArgs f, unsigned long long* res) {
-  __shared__ unsigned long long acc[kFlowCcResWords];
-  if (threadIdx.x < kFlowCcResWords) acc[threadIdx.x] = threadIdx.x == 5 ? ~0ull : 0ull;
-  __syncthreads();
   uint64_t v[kFlowCcResWords] = {};
   v[5] = ~0ull;
   for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < f.n_flows; i += (uint64_t)gridDim.x * 256) {
@@ -3973,31 +3985,13 @@ __global__ __launch_bounds__(256) void k_flow_cc_report(FlowArgs f, unsigned lon
       v[6] = c.cwnd > v[6] ? c.cwnd : v[6];
     }
   }
-#pragma unroll
-  for (uint32_t w = 0; w < kFlowCcResWords; ++w) {
-    const uint64_t t = w == 5 ? wave_min_max_u64(v[w], false) : w == 6 ? wave_min_max_u64(v[w], true) : wave_sum(v[w]);
-    if ((threadIdx.x & 63u) == 0) {
-      if (w == 5) atomicMin(&acc[w], (unsigned long long)t);
-      else if (w == 6) atomicMax(&acc[w], (unsigned long long)t);
-      else atomicAdd(&acc[w], (unsigned long long)t);
-    }
-  }
-  __syncthreads();
-  if (threadIdx.x < kFlowCcResWords) {
-    const uint32_t w = threadIdx.x;
-    if (w == 5) atomicMin(&res[w], acc[w]);
-    else if (w == 6) atomicMax(&res[w], acc[w]);
-    else atomicAdd(&res[w], acc[w]);
-  }
+  report_commit<kFlowCcResWords, 1u << 5, 1u << 6>(v, res);
 }
 
 // tgsim_flow_rto_report, as k_flow_cc_report: samples over every flow; the count, and the sum, minimum
 // and maximum of srtt8 >> 3 and of rto, over the flows with a sample.  The two minima travel
 // complemented (words 3 and 6 hold the maximum of ~x), so res starts as zeros.
 __global__ __launch_bounds__(256) void k_flow_rto_report(FlowArgs f, unsigned long long* res) {
-  __shared__ unsigned long long acc[kFlowRtoResWords];
-  if (threadIdx.x < kFlowRtoResWords) acc[threadIdx.x] = 0ull;
-  __syncthreads();
   uint64_t v[kFlowRtoResWords] = {};
   for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < f.n_flows; i += (uint64_t)gridDim.x * 256) {
     const tgsim_flow_rto_row q = f.rt[i];
@@ -4012,21 +4006,7 @@ __global__ __launch_bounds__(256) void k_flow_rto_report(FlowArgs f, unsigned lo
     v[6] = nrto > v[6] ? nrto : v[6];
     v[7] = q.rto > v[7] ? q.rto : v[7];
   }
-#pragma unroll
-  for (uint32_t w = 0; w < kFlowRtoResWords; ++w) {
-    const bool is_max = w == 3 || w == 4 || w == 6 || w == 7;
-    const uint64_t t = is_max ? wave_min_max_u64(v[w], true) : wave_sum(v[w]);
-    if ((threadIdx.x & 63u) == 0) {
-      if (is_max) atomicMax(&acc[w], (unsigned long long)t);
-      else atomicAdd(&acc[w], (unsigned long long)t);
-    }
-  }
-  __syncthreads();
-  if (threadIdx.x < kFlowRtoResWords && acc[1]) {
-    const uint32_t w = threadIdx.x;
-    if (w == 3 || w == 4 || w == 6 || w == 7) atomicMax(&res[w], acc[w]);
-    else atomicAdd(&res[w], acc[w]);
-  }
+  report_commit<kFlowRtoResWords, 0u, 1u << 3 | 1u << 4 | 1u << 6 | 1u << 7>(v, res);
 }
 
 // Verdict feedback (tgsim_flow_init_fb), behind a window's simulate kernel: one lane
@@ -4091,9 +4071,6 @@ __global__ __launch_bounds__(256) void k_flow_fb(FlowArgs f, const uint64_t* __r
 // tgsim_flow_fb_report, as k_flow_report below: the five counters and the flows with a refusal over
 // every flow, and the FAILED flows by cause (word 6: the timer; words 7..10: verdict 1..4).
 __global__ __launch_bounds__(256) void k_flow_fb_report(FlowArgs f, unsigned long long* res) {
-  __shared__ unsigned long long acc[kFlowFbResWords];
-  if (threadIdx.x < kFlowFbResWords) acc[threadIdx.x] = 0ull;
-  __syncthreads();
   uint64_t v[kFlowFbResWords] = {};
   for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < f.n_flows; i += (uint64_t)gridDim.x * 256) {
     const tgsim_flow_fb_row q = f.fb[i];
@@ -4109,21 +4086,12 @@ __global__ __launch_bounds__(256) void k_flow_fb_report(FlowArgs f, unsigned lon
       for (uint32_t k = 0; k < 4; ++k) v[7 + k] += q.fail_verdict == 1 + k;
     }
   }
-#pragma unroll
-  for (uint32_t w = 0; w < kFlowFbResWords; ++w) {
-    const uint64_t t = wave_sum(v[w]);
-    if ((threadIdx.x & 63u) == 0 && t) atomicAdd(&acc[w], (unsigned long long)t);
-  }
-  __syncthreads();
-  if (threadIdx.x < kFlowFbResWords && acc[threadIdx.x]) atomicAdd(&res[threadIdx.x], acc[threadIdx.x]);
+  report_commit<kFlowFbResWords, 0u, 0u>(v, res);
 }
 
 // tgsim_flow_report: one pass over the rows; a workgroup reduces in LDS and ends with one set of
-// atomics (at most 256 workgroups).  res: kFlowResWords words, then the histogram k_ping_report_init folded.
+// atomics (at most 256 workgroups).  res: kFlowResWords words, then the histogram k_cal_report_init folded.
 __global__ __launch_bounds__(256) void k_flow_report(FlowArgs f, unsigned long long* res) {
-  __shared__ unsigned long long acc[kFlowResWords];
-  if (threadIdx.x < kFlowResWords) acc[threadIdx.x] = threadIdx.x == 9 ? ~0ull : 0ull;
-  __syncthreads();
   uint64_t v[kFlowResWords] = {};
   v[9] = ~0ull;
   for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < f.n_flows; i += (uint64_t)gridDim.x * 256) {
@@ -4143,22 +4111,7 @@ __global__ __launch_bounds__(256) void k_flow_report(FlowArgs f, unsigned long l
       v[10] = fct > v[10] ? fct : v[10];
     }
   }
-#pragma unroll
-  for (uint32_t w = 0; w < kFlowResWords; ++w) {
-    const uint64_t t = w == 9 ? wave_min_max_u64(v[w], false) : w == 10 ? wave_min_max_u64(v[w], true) : wave_sum(v[w]);
-    if ((threadIdx.x & 63u) == 0) {
-      if (w == 9) atomicMin(&acc[w], (unsigned long long)t);
-      else if (w == 10) atomicMax(&acc[w], (unsigned long long)t);
-      else atomicAdd(&acc[w], (unsigned long long)t);
-    }
-  }
-  __syncthreads();
-  if (threadIdx.x < kFlowResWords && acc[0]) {
-    const uint32_t w = threadIdx.x;
-    if (w == 9) atomicMin(&res[w], acc[w]);
-    else if (w == 10) atomicMax(&res[w], acc[w]);
-    else atomicAdd(&res[w], acc[w]);
-  }
+  report_commit<kFlowResWords, 1u << 9, 1u << 10>(v, res);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -5453,94 +5406,107 @@ void launch_gossip_times(const uint32_t* first, const uint64_t* fwd, uint32_t s0
 
 namespace {
 // Workgroups of a grid-stride pass over up to n items (the exact count is read on the device).
-uint32_t ping_grid(uint64_t n) { return (uint32_t)std::min<uint64_t>(std::max<uint64_t>((n + 255) / 256, 1), 2048); }
+uint32_t cal_grid(uint64_t n) { return (uint32_t)std::min<uint64_t>(std::max<uint64_t>((n + 255) / 256, 1), 2048); }
+// (few workgroups in a report pass: each ends with a set of atomics on the same words, which serialize)
+dim3 report_grid(uint64_t n) { return dim3(std::min(cal_grid(n), 256u)); }
+
+// The calendar's part of a generation: the due entries counted on their responders; the due entries
+// into the rows behind the cursors and the others into the next buffer, then the row order.
+void launch_cal_count(const CalArgs& a, uint64_t* counts, uint64_t cal_bound, hipStream_t st) {
+  if (cal_bound) hipLaunchKernelGGL(k_cal_count, dim3(cal_grid(cal_bound)), dim3(256), 0, st, a, counts);
+}
+void launch_cal_write(const CalArgs& a, const uint64_t* off, uint32_t* cursor, InRec* tmp, InRec* out,
+                      uint64_t cal_bound, hipStream_t st) {
+  if (cal_bound) hipLaunchKernelGGL(k_cal_write, dim3(cal_grid(cal_bound)), dim3(256), 0, st, a, off, cursor, tmp);
+  hipLaunchKernelGGL(k_cal_order, dim3((a.n_own + 3) / 4), dim3(256), 0, st, off, tmp, out, a.n_own);
+}
+
+// The flow kernels' <CC, RTO> instantiation for the tables f arms: fn(std::bool_constant<CC>, std::bool_constant<RTO>).
+template <typename Fn>
+void flow_dispatch(const FlowArgs& f, Fn&& fn) {
+  if (f.cc && f.rt) fn(std::true_type{}, std::true_type{});
+  else if (f.cc) fn(std::true_type{}, std::false_type{});
+  else if (f.rt) fn(std::false_type{}, std::true_type{});
+  else fn(std::false_type{}, std::false_type{});
+}
 }  // namespace
 
 void launch_ping_init(const PingArgs& a, hipStream_t st) {
-  const uint64_t n = std::max<uint64_t>((uint64_t)a.n_own * a.fanout, kPingReplicas * kPingMaxBins);
+  const uint64_t n = std::max<uint64_t>((uint64_t)a.cal.n_own * a.fanout, kCalReplicas * kCalMaxBins);
   hipLaunchKernelGGL(k_ping_init, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, a);
 }
 
 void launch_ping_recv(const PingArgs& a, const tgsim_delivery* recs, const uint64_t* off, uint32_t n_dst,
                       uint64_t n_bound, hipStream_t st) {
-  hipLaunchKernelGGL(k_ping_recv, dim3(ping_grid(n_bound)), dim3(256), 0, st, a, recs, off, n_dst, n_bound);
+  hipLaunchKernelGGL(k_ping_recv, dim3(cal_grid(n_bound)), dim3(256), 0, st, a, recs, off, n_dst, n_bound);
 }
 
 void launch_ping_count(const PingArgs& a, const uint32_t* n_slots, uint64_t* counts, uint32_t* cursor,
                        uint64_t cal_bound, hipStream_t st) {
-  hipLaunchKernelGGL(k_ping_count_sched, dim3((a.n_own + 255) / 256), dim3(256), 0, st, a, n_slots, counts, cursor);
-  if (cal_bound) hipLaunchKernelGGL(k_ping_count_cal, dim3(ping_grid(cal_bound)), dim3(256), 0, st, a, counts);
+  hipLaunchKernelGGL(k_ping_count_sched, dim3((a.cal.n_own + 255) / 256), dim3(256), 0, st, a, n_slots, counts, cursor);
+  launch_cal_count(a.cal, counts, cal_bound, st);
 }
 
 void launch_ping_write(const PingArgs& a, const uint64_t* off, uint32_t* cursor, InRec* tmp, InRec* out,
                        uint64_t cal_bound, hipStream_t st) {
-  if (a.j_hi > a.j_lo) hipLaunchKernelGGL(k_ping_write_sched, dim3((a.n_own + 3) / 4), dim3(256), 0, st, a, off, tmp);
-  if (cal_bound) hipLaunchKernelGGL(k_ping_write_cal, dim3(ping_grid(cal_bound)), dim3(256), 0, st, a, off, cursor, tmp);
-  hipLaunchKernelGGL(k_ping_order, dim3((a.n_own + 3) / 4), dim3(256), 0, st, off, tmp, out, a.n_own);
+  if (a.j_hi > a.j_lo) hipLaunchKernelGGL(k_ping_write_sched, dim3((a.cal.n_own + 3) / 4), dim3(256), 0, st, a, off, tmp);
+  launch_cal_write(a.cal, off, cursor, tmp, out, cal_bound, st);
 }
 
 void launch_ping_report(const PingArgs& a, unsigned long long* res, hipStream_t st) {
-  hipLaunchKernelGGL(k_ping_report_init, dim3(1), dim3(256), 0, st, a, res, kPingResWords, 4u);
-  // (few workgroups: each ends with eight atomics on the same eight words, which serialize)
-  hipLaunchKernelGGL(k_ping_report, dim3(std::min(ping_grid((uint64_t)a.n_own * a.fanout), 256u)), dim3(256), 0, st, a, res);
+  hipLaunchKernelGGL(k_cal_report_init, dim3(1), dim3(256), 0, st, a.cal, res, kPingResWords, 4u, a.cal.n_bins);
+  hipLaunchKernelGGL(k_ping_report, report_grid((uint64_t)a.cal.n_own * a.fanout), dim3(256), 0, st, a, res);
 }
 
 // Flow driver (tgsim_flow_*).
 void launch_flow_init(const FlowArgs& f, hipStream_t st) {
-  const uint64_t n = std::max<uint64_t>(f.n_flows, (uint64_t)kPingReplicas * kPingMaxBins);
-  const dim3 grid((uint32_t)((n + 255) / 256));
-  if (f.cc && f.rt) hipLaunchKernelGGL((k_flow_init<true, true>), grid, dim3(256), 0, st, f);
-  else if (f.cc) hipLaunchKernelGGL((k_flow_init<true, false>), grid, dim3(256), 0, st, f);
-  else if (f.rt) hipLaunchKernelGGL((k_flow_init<false, true>), grid, dim3(256), 0, st, f);
-  else hipLaunchKernelGGL((k_flow_init<false, false>), grid, dim3(256), 0, st, f);
+  const uint64_t n = std::max<uint64_t>(f.n_flows, (uint64_t)kCalReplicas * kCalMaxBins);
+  flow_dispatch(f, [&](auto cc, auto rto) {
+    hipLaunchKernelGGL((k_flow_init<cc.value, rto.value>), dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, f);
+  });
 }
 
 void launch_flow_recv(const FlowArgs& f, const tgsim_delivery* recs, const uint64_t* off, uint32_t n_dst,
                       uint64_t n_bound, hipStream_t st) {
-  hipLaunchKernelGGL(k_flow_recv_data, dim3(ping_grid(n_bound)), dim3(256), 0, st, f, recs, off, n_dst, n_bound);
-  const dim3 grid((uint32_t)((f.n_flows + 255) / 256));
-  if (f.cc && f.rt) hipLaunchKernelGGL((k_flow_recv_ack<true, true>), grid, dim3(256), 0, st, f, recs, off, n_bound);
-  else if (f.cc) hipLaunchKernelGGL((k_flow_recv_ack<true, false>), grid, dim3(256), 0, st, f, recs, off, n_bound);
-  else if (f.rt) hipLaunchKernelGGL((k_flow_recv_ack<false, true>), grid, dim3(256), 0, st, f, recs, off, n_bound);
-  else hipLaunchKernelGGL((k_flow_recv_ack<false, false>), grid, dim3(256), 0, st, f, recs, off, n_bound);
+  hipLaunchKernelGGL(k_flow_recv_data, dim3(cal_grid(n_bound)), dim3(256), 0, st, f, recs, off, n_dst, n_bound);
+  flow_dispatch(f, [&](auto cc, auto rto) {
+    hipLaunchKernelGGL((k_flow_recv_ack<cc.value, rto.value>), dim3((uint32_t)((f.n_flows + 255) / 256)), dim3(256), 0, st,
+                       f, recs, off, n_bound);
+  });
 }
 
 void launch_flow_count(const FlowArgs& f, uint64_t* counts, uint32_t* cursor, uint64_t cal_bound, hipStream_t st) {
   (void)hipMemsetAsync(counts, 0, sizeof(uint64_t) * f.cal.n_peers, st);
   (void)hipMemsetAsync(cursor, 0, sizeof(uint32_t) * f.cal.n_peers, st);
-  (void)hipMemsetAsync(f.cal.ctr + kPcOffers, 0, sizeof(unsigned long long), st);
+  (void)hipMemsetAsync(f.cal.ctr + kCalOffers, 0, sizeof(unsigned long long), st);
   const dim3 grid((uint32_t)((f.n_flows + 255) / 256));
   if (f.cc) hipLaunchKernelGGL(k_flow_count<true>, grid, dim3(256), 0, st, f, counts);
   else hipLaunchKernelGGL(k_flow_count<false>, grid, dim3(256), 0, st, f, counts);
-  if (cal_bound) hipLaunchKernelGGL(k_ping_count_cal, dim3(ping_grid(cal_bound)), dim3(256), 0, st, f.cal, counts);
+  launch_cal_count(f.cal, counts, cal_bound, st);
 }
 
 void launch_flow_write(const FlowArgs& f, const uint64_t* off, uint32_t* cursor, InRec* tmp, InRec* out,
                        uint64_t cal_bound, hipStream_t st) {
-  const dim3 grid((uint32_t)((f.n_flows + 255) / 256));
-  if (f.cc && f.rt) hipLaunchKernelGGL((k_flow_write<true, true>), grid, dim3(256), 0, st, f, off, cursor, tmp);
-  else if (f.cc) hipLaunchKernelGGL((k_flow_write<true, false>), grid, dim3(256), 0, st, f, off, cursor, tmp);
-  else if (f.rt) hipLaunchKernelGGL((k_flow_write<false, true>), grid, dim3(256), 0, st, f, off, cursor, tmp);
-  else hipLaunchKernelGGL((k_flow_write<false, false>), grid, dim3(256), 0, st, f, off, cursor, tmp);
-  if (cal_bound) hipLaunchKernelGGL(k_ping_write_cal, dim3(ping_grid(cal_bound)), dim3(256), 0, st, f.cal, off, cursor, tmp);
-  hipLaunchKernelGGL(k_ping_order, dim3((f.cal.n_own + 3) / 4), dim3(256), 0, st, off, tmp, out, f.cal.n_own);
+  flow_dispatch(f, [&](auto cc, auto rto) {
+    hipLaunchKernelGGL((k_flow_write<cc.value, rto.value>), dim3((uint32_t)((f.n_flows + 255) / 256)), dim3(256), 0, st, f,
+                       off, cursor, tmp);
+  });
+  launch_cal_write(f.cal, off, cursor, tmp, out, cal_bound, st);
 }
 
 void launch_flow_report(const FlowArgs& f, unsigned long long* res, hipStream_t st) {
-  hipLaunchKernelGGL(k_ping_report_init, dim3(1), dim3(256), 0, st, f.cal, res, kFlowResWords, 9u);
-  hipLaunchKernelGGL(k_flow_report, dim3(std::min(ping_grid(f.n_flows), 256u)), dim3(256), 0, st, f, res);
+  hipLaunchKernelGGL(k_cal_report_init, dim3(1), dim3(256), 0, st, f.cal, res, kFlowResWords, 9u, f.cal.n_bins);
+  hipLaunchKernelGGL(k_flow_report, report_grid(f.n_flows), dim3(256), 0, st, f, res);
 }
 
 void launch_flow_cc_report(const FlowArgs& f, unsigned long long* res, hipStream_t st) {
-  PingArgs words_only = f.cal;  // (no histogram to fold)
-  words_only.n_bins = 0;
-  hipLaunchKernelGGL(k_ping_report_init, dim3(1), dim3(256), 0, st, words_only, res, kFlowCcResWords, 5u);
-  hipLaunchKernelGGL(k_flow_cc_report, dim3(std::min(ping_grid(f.n_flows), 256u)), dim3(256), 0, st, f, res);
+  hipLaunchKernelGGL(k_cal_report_init, dim3(1), dim3(256), 0, st, f.cal, res, kFlowCcResWords, 5u, 0u);  // (no histogram)
+  hipLaunchKernelGGL(k_flow_cc_report, report_grid(f.n_flows), dim3(256), 0, st, f, res);
 }
 
 void launch_flow_rto_report(const FlowArgs& f, unsigned long long* res, hipStream_t st) {
   (void)hipMemsetAsync(res, 0, sizeof(unsigned long long) * kFlowRtoResWords, st);
-  hipLaunchKernelGGL(k_flow_rto_report, dim3(std::min(ping_grid(f.n_flows), 256u)), dim3(256), 0, st, f, res);
+  hipLaunchKernelGGL(k_flow_rto_report, report_grid(f.n_flows), dim3(256), 0, st, f, res);
 }
 
 void launch_flow_fb(const FlowArgs& f, const uint64_t* off, const InRec* in, const uint8_t* verdict, uint64_t n_in,
@@ -5551,7 +5517,7 @@ void launch_flow_fb(const FlowArgs& f, const uint64_t* off, const InRec* in, con
 
 void launch_flow_fb_report(const FlowArgs& f, unsigned long long* res, hipStream_t st) {
   (void)hipMemsetAsync(res, 0, sizeof(unsigned long long) * kFlowFbResWords, st);
-  hipLaunchKernelGGL(k_flow_fb_report, dim3(std::min(ping_grid(f.n_flows), 256u)), dim3(256), 0, st, f, res);
+  hipLaunchKernelGGL(k_flow_fb_report, report_grid(f.n_flows), dim3(256), 0, st, f, res);
 }
 
 void launch_ping_pairs(const PingArgs& a, uint64_t i0, uint64_t n, tgsim_ping_pair* out, hipStream_t st) {

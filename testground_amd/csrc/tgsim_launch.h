@@ -86,13 +86,13 @@ void launch_ping_report(const PingArgs& a, unsigned long long* res, hipStream_t 
 void launch_ping_pairs(const PingArgs& a, uint64_t i0, uint64_t n, tgsim_ping_pair* out, hipStream_t st);
 // tgsim_comm_ping_report: the local report's words packed into the sum / min / max runs the ranks
 // all-reduce (out: kPingPackWords), and the reduced runs published to the host as a tgsim_ping_summary,
-// the histogram at word 11 and the sequence word at 11 + kPingMaxBins.
+// the histogram at word 11 and the sequence word at 11 + kCalMaxBins.
 void launch_ping_pack(const unsigned long long* res, const unsigned long long* ctr, uint32_t cal_word, uint32_t n_bins,
                       unsigned long long* out, hipStream_t st);
 void launch_ping_unpack(const unsigned long long* in, uint32_t n_bins, uint64_t* host, uint64_t seq, hipStream_t st);
-// Flow driver (tgsim_flow_*), on the ping driver's calendar (f.cal).  _init: rows, timers, histogram
+// Flow driver (tgsim_flow_*), on the reply calendar it holds (f.cal).  _init: rows, timers, histogram
 // replicas, counters.  _recv: the data leg (calendar entries, ignored records), then the ACK leg (a
-// lane per flow).  _count: clears counts, cursor and kPcOffers, counts the flows' offers per source
+// lane per flow).  _count: clears counts, cursor and kCalOffers, counts the flows' offers per source
 // and the due calendar entries.  _write: offers, due ACKs and the kept calendar entries, then the row
 // order.  _report: res = kFlowResWords summary words + n_bins histogram words.
 void launch_flow_init(const FlowArgs& f, hipStream_t st);

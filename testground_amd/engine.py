@@ -264,102 +264,64 @@ class CABIEngine:
         feedback: per-flow verdict counters (flow_fb_rows, flow_fb_report), and a flow whose data
         offer is refused with a verdict in fail_mask (bits 1 << abi.V_*, within abi.FLOW_FB_REFUSALS)
         fails at that offer's tick."""
-        self.flow_fb_armed = False
-        if fb is not None and flows is not None:
-            return self._flow_init_fb(flows, abi.Flow(seg_len, ack_len, window, rto_ticks, max_attempts, n_bins, bin_ns), cc, rto, fb)
-        if rto is not None and flows is not None:
-            return self._flow_init_rto(flows, abi.Flow(seg_len, ack_len, window, rto_ticks, max_attempts, n_bins, bin_ns), cc, rto)
-        fn = self._gossip_fn("flow_init" if cc is None or flows is None else "flow_init_cc")
-        self.flow_cc_armed = self.flow_rto_armed = False
+        self.flow_cc_armed = self.flow_rto_armed = self.flow_fb_armed = False
         if flows is None:
-            self._check(fn(self._h, None, None, 0), "flow_init")
+            self._check(self._gossip_fn("flow_init")(self._h, None, None, 0), "flow_init")
             self._n_flows = None
             return
         t = np.ascontiguousarray(flows, dtype=abi.FLOW_SPEC_DTYPE)
         if t.ndim != 1:
             raise ValueError("flow_init: flows must be a 1-d abi.FLOW_SPEC_DTYPE table")
         p = abi.Flow(seg_len, ack_len, window, rto_ticks, max_attempts, n_bins, bin_ns)
-        if cc is None:
-            self._check(fn(self._h, C.byref(p), t.ctypes.data, len(t)), "flow_init")
-        else:
-            c = abi.FlowCC(cc.get("init_cwnd", 1), cc.get("init_ssthresh", 0), cc.get("dupthresh", 3), 0)
-            self._check(fn(self._h, C.byref(p), C.byref(c), t.ctypes.data, len(t)), "flow_init_cc")
-            self.flow_cc_armed = True
-        self._n_flows = len(t)
-
-    def _flow_init_rto(self, flows, p, cc: Optional[dict], rto: dict) -> None:
-        fn = self._gossip_fn("flow_init_rto")
-        self.flow_cc_armed = self.flow_rto_armed = False
-        t = np.ascontiguousarray(flows, dtype=abi.FLOW_SPEC_DTYPE)
-        if t.ndim != 1:
-            raise ValueError("flow_init: flows must be a 1-d abi.FLOW_SPEC_DTYPE table")
-        c = None if cc is None else C.byref(abi.FlowCC(cc.get("init_cwnd", 1), cc.get("init_ssthresh", 0), cc.get("dupthresh", 3), 0))
-        r = abi.FlowRto(rto.get("min_rto_ticks", 1), rto.get("max_rto_ticks", abi.FLOW_MAX_RTO), rto.get("backoff", 1), 0)
-        self._check(fn(self._h, C.byref(p), c, C.byref(r), t.ctypes.data, len(t)), "flow_init_rto")
-        self.flow_cc_armed, self.flow_rto_armed = cc is not None, True
-        self._n_flows = len(t)
-
-    def _flow_init_fb(self, flows, p, cc: Optional[dict], rto: Optional[dict], fb: dict) -> None:
-        fn = self._gossip_fn("flow_init_fb")
-        self.flow_cc_armed = self.flow_rto_armed = False
-        t = np.ascontiguousarray(flows, dtype=abi.FLOW_SPEC_DTYPE)
-        if t.ndim != 1:
-            raise ValueError("flow_init: flows must be a 1-d abi.FLOW_SPEC_DTYPE table")
         c = None if cc is None else C.byref(abi.FlowCC(cc.get("init_cwnd", 1), cc.get("init_ssthresh", 0), cc.get("dupthresh", 3), 0))
         r = None if rto is None else C.byref(abi.FlowRto(rto.get("min_rto_ticks", 1), rto.get("max_rto_ticks", abi.FLOW_MAX_RTO),
                                                          rto.get("backoff", 1), 0))
-        b = abi.FlowFb(fb.get("fail_mask", 0))
-        self._check(fn(self._h, C.byref(p), c, r, C.byref(b), t.ctypes.data, len(t)), "flow_init_fb")
-        self.flow_cc_armed, self.flow_rto_armed, self.flow_fb_armed = cc is not None, rto is not None, True
+        b = None if fb is None else C.byref(abi.FlowFb(fb.get("fail_mask", 0)))
+        # the narrowest entry point that takes every part asked for (each exported call stays in use)
+        name, parts = (("flow_init_fb", [c, r, b]) if fb is not None else ("flow_init_rto", [c, r]) if rto is not None else
+                       ("flow_init_cc", [c]) if cc is not None else ("flow_init", []))
+        self._check(self._gossip_fn(name)(self._h, C.byref(p), *parts, t.ctypes.data, len(t)), name)
+        self.flow_cc_armed, self.flow_rto_armed, self.flow_fb_armed = cc is not None, rto is not None, fb is not None
         self._n_flows = len(t)
+
+    def _flow_rows(self, name: str, dtype, first: int, n: Optional[int]) -> np.ndarray:
+        total = getattr(self, "_n_flows", None) or 0  # (unarmed: the call says so)
+        n = max(total - first, 0) if n is None else n
+        out = np.zeros(n, dtype=dtype)
+        self._check(self._gossip_fn(name)(self._h, first, n, out.ctypes.data, len(out)), name)
+        return out
+
+    def _flow_part_report(self, name: str, summary, fields) -> dict:
+        s = summary()
+        self._check(self._gossip_fn(name)(self._h, C.byref(s)), name)
+        return {k: int(getattr(s, k)) for k in fields}
 
     def flow_fb_rows(self, first: int = 0, n: Optional[int] = None) -> np.ndarray:
         """abi.FLOW_FB_ROW_DTYPE rows of flows [first, first + n) (tgsim_flow_fb_rows)."""
-        fn = self._gossip_fn("flow_fb_rows")
-        total = getattr(self, "_n_flows", None) or 0  # (unarmed: the call says so)
-        n = max(total - first, 0) if n is None else n
-        out = np.zeros(n, dtype=abi.FLOW_FB_ROW_DTYPE)
-        self._check(fn(self._h, first, n, out.ctypes.data, len(out)), "flow_fb_rows")
-        return out
+        return self._flow_rows("flow_fb_rows", abi.FLOW_FB_ROW_DTYPE, first, n)
 
     def flow_fb_report(self) -> dict:
         """The verdict feedback's summary over every flow (abi.FLOW_FB_SUMMARY_FIELDS), reduced on the
         device (tgsim_flow_fb_report): the data offers by verdict, and the FAILED flows by cause."""
-        s = abi.FlowFbSummary()
-        self._check(self._gossip_fn("flow_fb_report")(self._h, C.byref(s)), "flow_fb_report")
-        return {k: int(getattr(s, k)) for k in abi.FLOW_FB_SUMMARY_FIELDS}
+        return self._flow_part_report("flow_fb_report", abi.FlowFbSummary, abi.FLOW_FB_SUMMARY_FIELDS)
 
     def flow_rto_rows(self, first: int = 0, n: Optional[int] = None) -> np.ndarray:
         """abi.FLOW_RTO_ROW_DTYPE rows of flows [first, first + n) (tgsim_flow_rto_rows)."""
-        fn = self._gossip_fn("flow_rto_rows")
-        total = getattr(self, "_n_flows", None) or 0  # (unarmed: the call says so)
-        n = max(total - first, 0) if n is None else n
-        out = np.zeros(n, dtype=abi.FLOW_RTO_ROW_DTYPE)
-        self._check(fn(self._h, first, n, out.ctypes.data, len(out)), "flow_rto_rows")
-        return out
+        return self._flow_rows("flow_rto_rows", abi.FLOW_RTO_ROW_DTYPE, first, n)
 
     def flow_rto_report(self) -> dict:
         """The estimator's summary (abi.FLOW_RTO_SUMMARY_FIELDS), reduced on the device
         (tgsim_flow_rto_report); every field but samples is over the flows with a sample."""
-        s = abi.FlowRtoSummary()
-        self._check(self._gossip_fn("flow_rto_report")(self._h, C.byref(s)), "flow_rto_report")
-        return {k: int(getattr(s, k)) for k in abi.FLOW_RTO_SUMMARY_FIELDS}
+        return self._flow_part_report("flow_rto_report", abi.FlowRtoSummary, abi.FLOW_RTO_SUMMARY_FIELDS)
 
     def flow_cc_rows(self, first: int = 0, n: Optional[int] = None) -> np.ndarray:
         """abi.FLOW_CC_ROW_DTYPE rows of flows [first, first + n) (tgsim_flow_cc_rows)."""
-        fn = self._gossip_fn("flow_cc_rows")
-        total = getattr(self, "_n_flows", None) or 0  # (unarmed: the call says so)
-        n = max(total - first, 0) if n is None else n
-        out = np.zeros(n, dtype=abi.FLOW_CC_ROW_DTYPE)
-        self._check(fn(self._h, first, n, out.ctypes.data, len(out)), "flow_cc_rows")
-        return out
+        return self._flow_rows("flow_cc_rows", abi.FLOW_CC_ROW_DTYPE, first, n)
 
     def flow_cc_report(self) -> dict:
         """The congestion summary over every flow (abi.FLOW_CC_SUMMARY_FIELDS), reduced on the device
         (tgsim_flow_cc_report); the cwnd fields are over the ACTIVE flows."""
-        s = abi.FlowCCSummary()
-        self._check(self._gossip_fn("flow_cc_report")(self._h, C.byref(s)), "flow_cc_report")
-        return {k: int(getattr(s, k)) for k in abi.FLOW_CC_SUMMARY_FIELDS}
+        return self._flow_part_report("flow_cc_report", abi.FlowCCSummary, abi.FLOW_CC_SUMMARY_FIELDS)
 
     def gen_flow(self, n_ticks: int) -> None:
         self._check(self._gossip_fn("gen_flow")(self._h, n_ticks), "gen_flow")
@@ -377,12 +339,7 @@ class CABIEngine:
 
     def flow_rows(self, first: int = 0, n: Optional[int] = None) -> np.ndarray:
         """abi.FLOW_ROW_DTYPE rows of flows [first, first + n) of the table (tgsim_flow_rows)."""
-        fn = self._gossip_fn("flow_rows")
-        total = getattr(self, "_n_flows", None) or 0  # (unarmed: the call says so)
-        n = max(total - first, 0) if n is None else n
-        out = np.zeros(n, dtype=abi.FLOW_ROW_DTYPE)
-        self._check(fn(self._h, first, n, out.ctypes.data, len(out)), "flow_rows")
-        return out
+        return self._flow_rows("flow_rows", abi.FLOW_ROW_DTYPE, first, n)
 
     # -- per-group traffic matrix (tgsim_groups_init / tgsim_group_matrix) ------------------------
     def groups_init(self, group_of=None, n_groups: Optional[int] = None) -> None:

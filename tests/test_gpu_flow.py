@@ -45,7 +45,7 @@ def test_rounds(make_oracle, rounds):
 
 
 def test_ping_disarm_leaves_flows(make_oracle):
-    """The flow driver's ACK calendar is the (disarmed) ping driver's: disarming ping while flows are
+    """The flow driver holds the reply calendar: disarming ping (not its owner) while flows are
     armed, mid-run with ACKs in the calendar, frees nothing, and the run goes on as the reference does."""
     kw = dict(lookahead_ns=fc.ROUNDS["lookahead_ns"])
     eng = Engine(2, **kw)

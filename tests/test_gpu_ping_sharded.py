@@ -145,7 +145,7 @@ def test_splitbrain(lib, bounds, case):
 @pytest.mark.parametrize("bounds", [[0, 50, 130], [0, 1, 60, 130]])
 def test_mesh_parity(lib, mesh_single, bounds):
     """[0, 1, 60, 130]: rank 0 owns only peer 0, whose rows exceed 64 entries (the long-row branch of
-    k_ping_order on a one-source shard)."""
+    k_cal_order on a one-source shard)."""
     n, kw = pc.MESH["n"], dict(lookahead_ns=pc.MESH["lookahead_ns"])
     per_rank, info = _sharded(lib, n, bounds, lambda e: pc.run_mesh(e, device=True), **kw)
     _assert_equals_single(per_rank, mesh_single)
