@@ -272,7 +272,9 @@ int tgsim_step_sim_release(void* engine);
 /* Fused form of the slotted step (n_win generated windows in one launch, tgsim_step_n): d_out holds
  * n_ranks x n_win chunks of (slot_cap + 1) records, rank-major (chunk r * n_win + w: window w's
  * records for rank r behind its count header), so one all-to-all moves the whole group; counts as
- * ONE launched step for _release.  -EINVAL when the next n_win windows are not fusable. */
+ * ONE launched step for _release.  -EINVAL when the next n_win windows are not fusable; on an engine
+ * with TGSIM_OPT_METRICS or an armed group matrix no windows are (n_win >= 2 is refused, naming that
+ * reason, before anything is simulated). */
 int tgsim_step_sim_launch_slotted_n(void* engine, uint32_t n_ticks, uint32_t n_win, uint32_t n_ranks,
                                     const uint32_t* rank_bounds, void* d_out, uint64_t slot_cap, void* routed_event);
 /* tgsim_deliver_slotted_async of a fused group's exchange output (n_ranks x n_win chunks, source-rank
@@ -338,7 +340,12 @@ int tgsim_comm_finish(void* engine);
  * records in fixed chunks of slot_cap records behind a count header (0: the largest per-rank count
  * of the earlier tgsim_comm_step windows, max over ranks, x 1.25 + 4096; without such windows the
  * bound of what one window can emit).  The host never waits for
- * the device.  A chunk that would overflow fails the run with -ENOSPC (nothing is lost silently). */
+ * the device.  A chunk that would overflow fails the run with -ENOSPC (nothing is lost silently).
+ * Engines created with TGSIM_OPT_METRICS, or with the group matrix armed, run every window unfused
+ * (their folds follow each window's kernel).  At one rank, and in tgsim_step_n, that happens by
+ * itself; at two or more ranks every rank must agree on the group size, so fuse >= 2 (with n_steps >= 2)
+ * is refused there with -EINVAL and that reason, on every rank, before a window is simulated (the clock does not
+ * move, the generated windows stay queued): call it with fuse = 1. */
 int tgsim_comm_run(void* engine, uint32_t n_ticks, uint32_t n_steps, uint32_t fuse, uint64_t slot_cap);
 /* SignalAndWait over the shards (sync-service Barrier, sidecar_handler.go:40-44): the counts of
  * `state` are summed over the ranks by an all-reduce of the device counter tables; returns 1 when

@@ -3598,6 +3598,9 @@ int tgsim_step_sim_launch_slotted_n(void* e, uint32_t n_ticks, uint32_t n_win, u
   if (E->route_n == Eng::kRouteSlots) return E->fail(-EBUSY, "two launched steps are not released yet");
   if (int brc = driver_busy(E, "step_sim_launch_slotted_n")) return brc;
   HIPCHK(hipSetDevice(E->dev));
+  if (E->metrics_on || E->groups_on)  // their folds follow every window's kernel: such windows never fuse
+    return E->fail(-EINVAL, "step_sim_launch_slotted_n: engine has %s: windows run unfused, call tgsim_comm_run with fuse = 1",
+                   E->metrics_on ? "TGSIM_OPT_METRICS" : "the group matrix armed (tgsim_groups_init)");
   if (!fusable(E, n_ticks, n_win, true))
     return E->fail(-EINVAL, "step_sim_launch_slotted_n: the next %u windows are not generated dense windows of %u ticks",
                    n_win, n_ticks);
