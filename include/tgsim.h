@@ -592,7 +592,8 @@ int64_t tgsim_comm_ping_report(void* engine, tgsim_ping_summary* out, uint64_t* 
  *   Verdicts the sender learns nothing from them: a filtered, lost or queue-full segment is recovered
  *            by its timer only (unless armed with tgsim_flow_init_fb, further down: the verdict
  *            feedback counts them per flow and can fail a flow on a refusal).
- * Single engine only (it must own every peer), as for ping. */
+ * tgsim_flow_init and its _cc / _rto / _fb forms arm a single engine that owns every peer;
+ * tgsim_flow_init_sharded (further down) arms one engine per shard of a run spread over tgsim_comm_*. */
 #define TGSIM_FLOW_SLOTS 16u
 enum tgsim_flow_state { TGSIM_FLOW_ACTIVE = 0, TGSIM_FLOW_DONE = 1, TGSIM_FLOW_FAILED = 2 };
 typedef struct {
@@ -848,6 +849,74 @@ int tgsim_flow_init_fb(void* engine, const tgsim_flow* p, const tgsim_flow_cc* c
  * synchronize, and fail, like tgsim_flow_rto_rows and tgsim_flow_rto_report. */
 int64_t tgsim_flow_fb_rows(void* engine, uint64_t first, uint64_t n, tgsim_flow_fb_row* out, size_t cap);
 int     tgsim_flow_fb_report(void* engine, tgsim_flow_fb_summary* out);
+
+/* ---- flow driver over shards ---------------------------------------------------------------- */
+/* tgsim_flow_init_fb on an engine that owns peers [shard_begin, shard_end), which may be every peer.
+ * `flows` is the WHOLE run's table, the same on every shard: it is replicated like the peer tables and
+ * the ping targets, because a receiver's shard validates a data record against the sender's flow
+ * (dst == r, seg < n_seg), which it does not own (16 B per flow, and first[] / cnt[] at 8 B per peer,
+ * per shard).  Every field rule, -EINVAL text and -EBUSY rule of tgsim_flow_init_fb holds, less the
+ * ownership test; cc, rto and fb are each NULL or not.  The table is sorted by src, so the flows an
+ * engine owns (those whose src it owns) are one contiguous range [first, first + n) of it, possibly
+ * empty (tgsim_flow_owned); the per-flow state -- the row, the bitmap, the due / attempt / sent rings,
+ * the cc, rto and fb rows -- exists for them only.  (engine, NULL, NULL, NULL, NULL, NULL, 0) disarms,
+ * frees the state and drops a generated window of its own that is still pending (the window of a step
+ * the ranks refused, see the late rule); tgsim_flow_init(engine, NULL, NULL, 0) disarms either form.
+ *
+ * Every rule of the sections above holds.  What differs is where things happen:
+ *   Offers   of flow f, its timers and its failing by tick: the shard that owns f.src (tgsim_gen_flow
+ *            generates the owned sources' rows and involves no collective).
+ *   Verdicts the feedback fold of flow f: f.src's shard, from the generated window's own rows and
+ *            verdict bytes.
+ *   ACK      a calendar entry is made from a delivered data record addressed to r at the shard that
+ *            owns r, where the exchange's delivery emits the record; it becomes r's ACK there.
+ *   Receipt  a delivered ACK addressed to q changes sender state at q's shard.
+ *   Counters dup_ignored and corrupt_ignored count at the shard that emits the record; pending_acks
+ *            is that shard's calendar.
+ *   Order    unchanged: a window's verdicts take effect before the records the same step emits are folded.
+ * While armed through this call the closed steps are accepted exactly as for the sharded ping driver:
+ * tgsim_comm_step, tgsim_comm_launch / tgsim_comm_finish and, underneath them, tgsim_step_sim,
+ * tgsim_step_sim_launch / _finish / _counts, tgsim_deliver / tgsim_deliver_async and
+ * tgsim_deliver_slotted_async with one window; tgsim_step on an engine that owns every peer gives the
+ * results of the unsharded form.  tgsim_comm_run, tgsim_step_sim_launch_slotted called directly and
+ * tgsim_step_sim_launch_slotted_n stay -EBUSY (pipelined or fused: they cannot be closed-loop); one
+ * generated window at a time, and none between tgsim_comm_launch and its tgsim_comm_finish (-EBUSY:
+ * the window's receipts come first).
+ *
+ * The calendar of a shard holds the ACKs of data other shards offered, which it never sees offered: it
+ * is grown, where needed, ahead of each delivery's receipts to what the last generation kept plus every
+ * record received since (an entry is made from exactly one received record).  -ENOSPC stays the net.
+ *
+ * tgsim_flow_report, tgsim_flow_cc_report, tgsim_flow_rto_report and tgsim_flow_fb_report give THIS
+ * shard's flows.  Reports merge over the shards field by field: every field by sum and hist by sum, bin
+ * by bin, except fct_min_ns, cwnd_min, srtt_min and rto_min by min, and fct_max_ns, cwnd_max, srtt_max
+ * and rto_max by max (a shard with nothing to report gives the neutral values it gives today:
+ * UINT64_MAX for a minimum, 0 for a maximum).  tgsim_comm_flow_report does that on the device.
+ * tgsim_flow_rows and its _cc / _rto / _fb forms take global flow indices inside the owned range
+ * (-EINVAL, naming both ranges, otherwise).
+ *
+ * The late rule and the calendar overflow across ranks are the sharded ping driver's, word for word: one
+ * rank's tgsim_gen_flow sees a late ACK or a late released segment (-EINVAL; nothing generated, no state
+ * changed, the error stays); every rank still calls tgsim_comm_step / tgsim_comm_launch for every window;
+ * with more than one rank the launch first agrees on the ranks' fault words (one 8-byte max all-reduce
+ * and one host wait per window); when any rank is late EVERY rank's call returns -EINVAL,
+ * tgsim_last_error names the rank and the tick, nothing is simulated, and the error stays on every rank
+ * until it re-arms.  The reports stay readable.  A full calendar (-ENOSPC) is agreed the same way. */
+int tgsim_flow_init_sharded(void* engine, const tgsim_flow* p, const tgsim_flow_cc* cc, const tgsim_flow_rto* rto,
+                            const tgsim_flow_fb* fb, const tgsim_flow_spec* flows, uint64_t n_flows);
+/* The owned flows: the contiguous range of the table whose src this engine owns (the whole table on an
+ * engine that owns every peer, armed through either form).  -EINVAL when the driver is not armed. */
+int tgsim_flow_owned(void* engine, uint64_t* first, uint64_t* n);
+/* The WHOLE run's reports on every rank (collective, after tgsim_comm_init): each rank's local
+ * reports are packed on the device into three runs (sums and histogram bins, minima, maxima), reduced
+ * by three u64 all-reduces (sum, min, max) on the exchange stream and unpacked; no per-flow table
+ * crosses between GPUs or to the host.  cc / rto / fb: NULL, or a buffer for a part that is armed (a
+ * buffer for an unarmed part is -EINVAL naming the part, before any collective).  Returns n_bins;
+ * -EINVAL without a communicator or when the driver is not armed through tgsim_flow_init_sharded,
+ * -EBUSY between tgsim_comm_launch and tgsim_comm_finish, -ETIMEDOUT as the other collectives.  With
+ * one rank it equals the local reports. */
+int64_t tgsim_comm_flow_report(void* engine, tgsim_flow_summary* out, uint64_t* hist, size_t hist_cap,
+                               tgsim_flow_cc_summary* cc, tgsim_flow_rto_summary* rto, tgsim_flow_fb_summary* fb);
 
 /* ---- per-group traffic matrix (who offered what to whom, and what became of it) -------------- */
 /* Every peer belongs to one group (a region, a composition group); the engine folds each window's

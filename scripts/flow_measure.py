@@ -9,6 +9,10 @@
          busy windows, see below), beside the HBM floor of a busy window
   steady the device loop alone: wall time per window and the median over the steady windows (the A/B
          figure: run it with TGSIM_LIB naming another build of the library)
+  sharded  what a sharded window costs on one GPU: the device loop of the single engine (flow_init +
+         step) against the sharded form at one rank on the routed path (TGSIM_COMM_ROUTE1=1:
+         flow_init(sharded=True) + comm_step, the N > 1 step's own kernels, delivered in place), and
+         the time of one comm_flow_report.  One process, no retries: run it under a time limit.
   curve  goodput per flow against link loss, with and without congestion control (the README's table)
   hetero 10,000 peers with latencies U[1,100] ms: a fixed timer of 60 ms, one above the largest round
          trip, and the RTT estimator from that same timer (the README's table)
@@ -35,6 +39,7 @@ sender per slot and no two of its ACKs share (tick, seq): without jitter such a 
 engine and the oracle differ, and a random table makes millions of them."""
 import csv
 import json
+import os
 import statistics
 import sys
 import time
@@ -44,7 +49,7 @@ import numpy as np
 
 sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
 from testground_amd import abi, network as nw, workloads as wl  # noqa: E402
-from testground_amd.engine import Engine  # noqa: E402
+from testground_amd.engine import Engine, comm_id  # noqa: E402
 
 N, PER_SOURCE, N_SEG, WIN, LAT = 100_000, 8, 64, 5_000, 5 * nw.Millisecond
 FLOW = dict(seg_len=1000, ack_len=64, window=8, rto_ticks=20_000, max_attempts=4, bin_ns=10 * nw.Millisecond, n_bins=32)
@@ -97,6 +102,27 @@ def device_loop(windows=WINDOWS, cc=None, loss=0.0, rto=None, fb=None):
     if fb is not None:
         rep["fb"] = eng.flow_fb_report()
     return rep, t
+
+
+def routed_loop(windows=WINDOWS, cc=None, loss=0.0, rto=None, fb=None):
+    """The sharded form at one rank, routed (the environment is read by comm_init)."""
+    os.environ["TGSIM_COMM_ROUTE1"] = "1"
+    eng, t, rep_t = engine(abi.OPT_DISCARD_DELIVERIES, loss), [], []
+    eng.comm_init(comm_id(), 0, 1)
+    eng.flow_init(flow_table(), cc=cc, rto=rto, fb=fb, sharded=True, **FLOW)
+    for w in range(windows):
+        eng.sync()
+        t0 = time.perf_counter()
+        eng.gen_flow(WIN)
+        eng.comm_step(WIN)
+        eng.sync()
+        t.append(time.perf_counter() - t0)
+    for _ in range(5):
+        eng.sync()
+        t0 = time.perf_counter()
+        rep = eng.comm_flow_report()
+        rep_t.append(time.perf_counter() - t0)
+    return rep, t, rep_t, eng.flow_report()
 
 
 def hist_quantile_ms(hist, q, bin_ns):
@@ -223,6 +249,20 @@ def main():
                           "device_steady_ms": round(1e3 * statistics.median(td[w] for w in steady), 3),
                           "device_steady_min_max_ms": [round(1e3 * min(td[w] for w in steady), 3),
                                                        round(1e3 * max(td[w] for w in steady), 3)]}))
+    elif mode == "sharded":
+        dev, td = device_loop(windows, cc, loss, rto, fb)
+        rep, tr, rep_t, local = routed_loop(windows, cc, loss, rto, fb)
+        same = all(dev[k] == rep[k] == local[k] for k in abi.FLOW_SUMMARY_FIELDS) and (dev["hist"] == rep["hist"]).all()
+        same = same and all(dev[k] == rep[k] for k in ("cc", "rto", "fb") if k in dev)
+        print(json.dumps({"peers": N, "flows": N * PER_SOURCE, "cc": cc, "rto": rto, "fb": fb, "loss_pct": loss, "windows": windows,
+                          "steady": [steady[0], steady[-1]], "reports_agree": bool(same), "done": int(rep["done"]),
+                          "segs_acked": int(rep["segs_acked"]),
+                          "single_ms_per_window": [round(1e3 * x, 3) for x in td],
+                          "routed_ms_per_window": [round(1e3 * x, 3) for x in tr],
+                          "single_steady_ms": round(1e3 * statistics.median(td[w] for w in steady), 3),
+                          "routed_steady_ms": round(1e3 * statistics.median(tr[w] for w in steady), 3),
+                          "comm_flow_report_ms": [round(1e3 * x, 3) for x in rep_t],
+                          "comm_flow_report_median_ms": round(1e3 * statistics.median(rep_t), 3)}))
     elif mode == "curve":
         for loss_pct in CURVE["losses"]:
             for c in (None, CC):

@@ -262,6 +262,7 @@ EXPORTS = [
     "tgsim_flow_init_cc", "tgsim_flow_cc_rows", "tgsim_flow_cc_report",
     "tgsim_flow_init_rto", "tgsim_flow_rto_rows", "tgsim_flow_rto_report",
     "tgsim_flow_init_fb", "tgsim_flow_fb_rows", "tgsim_flow_fb_report",
+    "tgsim_flow_init_sharded", "tgsim_flow_owned", "tgsim_comm_flow_report",
     "tgsim_groups_init", "tgsim_group_matrix",
     "tgsim_comm_id", "tgsim_comm_init", "tgsim_comm_step", "tgsim_comm_launch", "tgsim_comm_finish", "tgsim_comm_run", "tgsim_comm_barrier", "tgsim_comm_info",
     "tgsim_bridge_create", "tgsim_bridge_destroy", "tgsim_bridge_send", "tgsim_bridge_step",
@@ -354,6 +355,11 @@ def declare(lib: C.CDLL, prefix: str) -> None:
       C.c_uint64)
     f("flow_fb_rows", C.c_int64, vp, C.c_uint64, C.c_uint64, C.c_void_p, C.c_size_t)
     f("flow_fb_report", C.c_int, vp, C.POINTER(FlowFbSummary))
+    f("flow_init_sharded", C.c_int, vp, C.POINTER(Flow), C.POINTER(FlowCC), C.POINTER(FlowRto), C.POINTER(FlowFb),
+      C.c_void_p, C.c_uint64)
+    f("flow_owned", C.c_int, vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64))
+    f("comm_flow_report", C.c_int64, vp, C.POINTER(FlowSummary), C.c_void_p, C.c_size_t, C.POINTER(FlowCCSummary),
+      C.POINTER(FlowRtoSummary), C.POINTER(FlowFbSummary))
     f("groups_init", C.c_int, vp, C.c_void_p, C.c_uint32)
     f("group_matrix", C.c_int64, vp, C.c_void_p, C.c_size_t, C.c_int)
     f("offered", C.c_int64, vp, C.c_void_p, C.c_size_t)

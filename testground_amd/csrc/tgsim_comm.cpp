@@ -53,6 +53,11 @@ constexpr size_t kRec = sizeof(tgsim_delivery);
 constexpr uint32_t kRoutedGridPct = 90;
 // tgsim_comm_ping_report's pinned block: the summary (11 words), the histogram, the sequence word
 constexpr size_t kPingHostWords = sizeof(tgsim_ping_summary) / sizeof(uint64_t) + kCalMaxBins + 1;
+// The report buffers (the packed words on the device, the pinned block) are shared by the ping and the
+// flow report: sized for the larger, the flow's; the sequence word is the block's last (kReportSeqWord)
+// for both, so that neither report's words can read as the other's sequence.
+static_assert(kFlowHostWords >= kPingHostWords && kFlowPackWords >= kPingPackWords, "the report buffers are the flow's");
+static_assert(sizeof(tgsim_flow_summary) == kFlowHostBase * sizeof(uint64_t), "k_flow_unpack writes 15 summary words");
 static_assert(sizeof(tgsim_ping_summary) == 11 * sizeof(uint64_t), "k_ping_unpack writes 11 summary words");
 
 // librccl.so.1, loaded once per process (when torch has loaded it already, dlopen returns that
@@ -352,20 +357,32 @@ int allreduce_u64(Comm* C, const void* dev_src, uint64_t* result, ncclRedOp_t op
   return 0;
 }
 
-// The sharded ping driver's late rule across ranks (include/tgsim.h): a late receipt (or a full
-// calendar) is seen by one rank's tgsim_gen_ping; before a window is launched the ranks agree on their
+// The late rule across ranks of the reply calendar's holder, the sharded ping or flow driver
+// (include/tgsim.h): a late receipt (or a full calendar) is seen by one rank's tgsim_gen_ping /
+// tgsim_gen_flow; before a window is launched the ranks agree on their
 // fault words with one 8-byte max all-reduce, so that every rank fails the window (nothing is simulated
 // and none waits for a peer that stopped).  The agreed word stays on every rank until it re-arms, and
 // is not exchanged again: every rank learned it in the same collective.  One rank: nothing to exchange.
-int ping_agree(Comm* C) {
+int cal_agree(Comm* C) {
   bool agreed = false;
-  uint64_t word = engine_ping_fault(C->eng, C->rank, &agreed);
+  uint64_t word = engine_cal_fault(C->eng, C->rank, &agreed);
   if (!agreed && C->nranks > 1) {
     C->h_cnt[0] = word;
     CHIP(hipMemcpyAsync(C->d_cnt.p, C->h_cnt, sizeof(uint64_t), hipMemcpyHostToDevice, C->xs));
     CRC(allreduce_u64(C, C->d_cnt.p, &word, ncclMax));
   }
-  return word ? engine_ping_fail_agreed(C->eng, word) : 0;
+  return word ? engine_cal_fail_agreed(C->eng, word) : 0;
+}
+
+// The reports' buffers, made at the first tgsim_comm_ping_report or tgsim_comm_flow_report.
+int report_buffers(Comm* C) {
+  if (C->h_prep) return 0;
+  CHIP(hipHostMalloc(reinterpret_cast<void**>(&C->h_prep), kFlowHostWords * sizeof(uint64_t),
+                     hipHostMallocCoherent | hipHostMallocMapped));
+  memset(C->h_prep, 0, kFlowHostWords * sizeof(uint64_t));
+  CHIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&C->dm_prep), C->h_prep, 0));
+  CHIP(C->d_prep.ensure(kFlowPackWords * sizeof(uint64_t)));
+  return 0;
 }
 
 }  // namespace
@@ -492,9 +509,10 @@ int tgsim_comm_launch(void* e, uint32_t n_ticks) {
   if (C->launched) return engine_fail(e, -EBUSY, "comm_launch: the launched window is not finished (tgsim_comm_finish)");
   if (engine_ping_armed(e) && !engine_ping_sharded(e))
     return engine_fail(e, -EBUSY, "comm_launch: the ping driver is armed (single engine, tgsim_step)");
-  if (engine_flow_armed(e)) return engine_fail(e, -EBUSY, "comm_launch: the flow driver is armed (single engine, tgsim_step)");
+  if (engine_flow_armed(e) && !engine_flow_sharded(e))
+    return engine_fail(e, -EBUSY, "comm_launch: the flow driver is armed (single engine, tgsim_step)");
   CHIP(hipSetDevice(C->dev));
-  if (engine_ping_sharded(e)) CRC(ping_agree(C));
+  if (engine_ping_sharded(e) || engine_flow_sharded(e)) CRC(cal_agree(C));
   if (C->local) {  // one rank owns every destination: nothing to route or move, so the window
                          // is the single-shard step with its asynchronous local delivery (the count
                          // of routed records is never read back: no host round trip)
@@ -592,7 +610,10 @@ int tgsim_comm_run(void* e, uint32_t n_ticks, uint32_t n_steps, uint32_t fuse, u
     return engine_fail(e, -EBUSY, engine_ping_sharded(e)
                                       ? "comm_run: the ping driver is armed (a closed loop: tgsim_comm_step, window by window)"
                                       : "comm_run: the ping driver is armed (single engine, tgsim_step)");
-  if (engine_flow_armed(e)) return engine_fail(e, -EBUSY, "comm_run: the flow driver is armed (single engine, tgsim_step)");
+  if (engine_flow_armed(e))
+    return engine_fail(e, -EBUSY, engine_flow_sharded(e)
+                                      ? "comm_run: the flow driver is armed (a closed loop: tgsim_comm_step, window by window)"
+                                      : "comm_run: the flow driver is armed (single engine, tgsim_step)");
   if (!n_steps) return 0;
   CHIP(hipSetDevice(C->dev));
   const int nr = C->nranks;
@@ -698,13 +719,7 @@ int64_t tgsim_comm_ping_report(void* e, tgsim_ping_summary* out, uint64_t* hist,
   CRC(engine_ping_report_dev(e, &res, &ctr, &cal_word, &nb, C->ev_sig));  // k_ping_report's words, on the device
   if (nb && (!hist || hist_cap < nb))
     return fail(C, -EINVAL, "comm_ping_report: %zu histogram words for %u bins", hist ? hist_cap : size_t{0}, nb);
-  if (!C->h_prep) {
-    CHIP(hipHostMalloc(reinterpret_cast<void**>(&C->h_prep), kPingHostWords * sizeof(uint64_t),
-                       hipHostMallocCoherent | hipHostMallocMapped));
-    memset(C->h_prep, 0, kPingHostWords * sizeof(uint64_t));
-    CHIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&C->dm_prep), C->h_prep, 0));
-    CHIP(C->d_prep.ensure(kPingPackWords * sizeof(uint64_t)));
-  }
+  CRC(report_buffers(C));
   // packed as three runs -- sums and histogram bins, min_ns, max_ns -- and reduced in place, one
   // all-reduce per operator; the unpack publishes the summary and the histogram to pinned memory
   unsigned long long* pk = reinterpret_cast<unsigned long long*>(C->d_prep.p);
@@ -720,9 +735,64 @@ int64_t tgsim_comm_ping_report(void* e, tgsim_ping_summary* out, uint64_t* hist,
   launch_ping_unpack(pk, nb, C->dm_prep, ++C->prep_seq, C->xs);
   CHIP(hipGetLastError());
   CHIP(hipEventRecord(C->ev_red, C->xs));
-  CRC(wait_word(C, C->h_prep + kPingHostWords - 1, C->prep_seq, C->ev_red, "ping report all-reduce"));
+  CRC(wait_word(C, C->h_prep + kReportSeqWord, C->prep_seq, C->ev_red, "ping report all-reduce"));
   memcpy(out, C->h_prep, sizeof *out);
   for (uint32_t b = 0; b < nb; ++b) hist[b] = C->h_prep[11 + b];
+  return nb;
+}
+
+int64_t tgsim_comm_flow_report(void* e, tgsim_flow_summary* out, uint64_t* hist, size_t hist_cap, tgsim_flow_cc_summary* cc,
+                               tgsim_flow_rto_summary* rto, tgsim_flow_fb_summary* fb) {
+  Comm* C = comm_of(e);
+  if (!C) return e ? engine_fail(e, -EINVAL, "comm_flow_report: no communicator (tgsim_comm_init)") : -EINVAL;
+  if (C->timed_out) return -ETIMEDOUT;  // a collective never completed (tgsim_last_error says which)
+  if (!engine_flow_sharded(e))
+    return engine_fail(e, -EINVAL, "comm_flow_report: the sharded flow driver is not armed (tgsim_flow_init_sharded)");
+  if (!out) return engine_fail(e, -EINVAL, "comm_flow_report: no summary buffer");
+  if (C->launched) return engine_fail(e, -EBUSY, "comm_flow_report: the launched window is not finished (tgsim_comm_finish)");
+  bool cc_on = false, rto_on = false, fb_on = false;
+  engine_flow_parts(e, &cc_on, &rto_on, &fb_on);
+  if (cc && !cc_on) return engine_fail(e, -EINVAL, "comm_flow_report: congestion control is not armed (a cc buffer was given)");
+  if (rto && !rto_on) return engine_fail(e, -EINVAL, "comm_flow_report: the RTT estimator is not armed (an rto buffer was given)");
+  if (fb && !fb_on) return engine_fail(e, -EINVAL, "comm_flow_report: verdict feedback is not armed (an fb buffer was given)");
+  CHIP(hipSetDevice(C->dev));
+  const unsigned long long *res = nullptr, *ctr = nullptr;
+  FlowPack L{};
+  uint32_t seg_len = 0;
+  CRC(engine_flow_report_dev(e, &res, &ctr, &L, &seg_len, C->ev_sig));  // the report kernels' words, on the device
+  const uint32_t nb = L.n_bins;
+  if (nb && (!hist || hist_cap < nb))
+    return fail(C, -EINVAL, "comm_flow_report: %zu histogram words for %u bins", hist ? hist_cap : size_t{0}, nb);
+  CRC(report_buffers(C));
+  // packed as three runs -- sums and histogram bins, minima, maxima -- and reduced in place, one
+  // all-reduce per operator; the unpack publishes the summaries and the histogram to pinned memory
+  unsigned long long* pk = reinterpret_cast<unsigned long long*>(C->d_prep.p);
+  const unsigned long long* part = res + kFlowPartRes;
+  CHIP(hipStreamWaitEvent(C->xs, C->ev_sig, 0));
+  launch_flow_pack(res, cc_on ? part : nullptr, rto_on ? part + kFlowCcResWords : nullptr,
+                   fb_on ? part + kFlowCcResWords + kFlowRtoResWords : nullptr, ctr, L, seg_len, pk, C->xs);
+  CHIP(hipGetLastError());
+  if (C->nranks > 1) {
+    CNCCL(C->R->AllReduce(pk, pk, L.n_sum, ncclUint64, ncclSum, C->nc, C->xs));
+    CNCCL(C->R->AllReduce(pk + L.n_sum, pk + L.n_sum, L.n_min, ncclUint64, ncclMin, C->nc, C->xs));
+    CNCCL(C->R->AllReduce(pk + L.n_sum + L.n_min, pk + L.n_sum + L.n_min, L.n_min, ncclUint64, ncclMax, C->nc, C->xs));
+  }
+  launch_flow_unpack(pk, L, C->dm_prep, ++C->prep_seq, C->xs);
+  CHIP(hipGetLastError());
+  CHIP(hipEventRecord(C->ev_red, C->xs));
+  CRC(wait_word(C, C->h_prep + kReportSeqWord, C->prep_seq, C->ev_red, "flow report all-reduce"));
+  const uint64_t* h = C->h_prep;
+  memcpy(out, h, sizeof *out);
+  if (cc) {
+    *cc = tgsim_flow_cc_summary{};
+    memcpy(cc, h + kFlowHostBase, kFlowHostCc * sizeof(uint64_t));
+  }
+  if (rto) memcpy(rto, h + kFlowHostBase + kFlowHostCc, kFlowHostRto * sizeof(uint64_t));
+  if (fb) {
+    *fb = tgsim_flow_fb_summary{};
+    memcpy(fb, h + kFlowHostBase + kFlowHostCc + kFlowHostRto, kFlowHostFb * sizeof(uint64_t));
+  }
+  for (uint32_t b = 0; b < nb; ++b) hist[b] = h[kFlowHostHist + b];
   return nb;
 }
 

@@ -469,6 +469,7 @@ struct tgsim_engine_s {
     uint32_t cur = 0;                      // the buffer being appended to
     uint64_t kept = 0;                     // its entries behind the last generation (those not yet due then)
     uint64_t appended = 0;                 // entries made since the holder armed, as of the last generation
+    uint64_t recv_since = 0;               // records (or their bound) received since the last generation (sharded flow)
     // sticky faults, until the holder arms again
     bool late = false;                     // an entry preceded a generated window ...
     uint64_t late_tick = 0;                // ... due at this tick
@@ -497,6 +498,12 @@ struct tgsim_engine_s {
   tgsim_flow flow{};
   uint64_t n_flows = 0;
   uint64_t flow_offered = 0;     // data packets offered since tgsim_flow_init: each makes at most one calendar entry
+  // tgsim_flow_init_sharded (an engine that may own part of the peers): the closed steps of the exchange
+  // are accepted.  The owned flows [flow0, flow0 + n_own_flows) are those of the owned sources; the
+  // per-flow state is theirs alone.  Its ACK entries come from other shards' offers, which it does not
+  // see: the calendar grows ahead of each delivery's receipts instead (cal_recv), one entry per record.
+  bool flow_sharded = false;
+  uint64_t flow0 = 0, n_own_flows = 0;
   DevBuf<tgsim_flow_spec> d_fspec;
   DevBuf<tgsim_flow_row> d_frow;
   DevBuf<uint64_t> d_fbits;
@@ -1527,7 +1534,7 @@ void cal_release(Eng* E) {
   c.tmp.release();
   c.owner = Eng::ReplyCalendar::kNone;
   c.cur = 0;
-  c.kept = c.appended = 0;
+  c.kept = c.appended = c.recv_since = 0;
   c.late = false;
   c.nospc = c.agreed = 0;
 }
@@ -1546,7 +1553,8 @@ int cal_arm(Eng* E, size_t rows, uint64_t entries) {
   HIPCHK(c.cursor.ensure_exact(rows));
   HIPCHK(c.hist.ensure_exact(static_cast<size_t>(kCalReplicas) * kCalMaxBins));
   HIPCHK(c.ctr.ensure_exact(kCalCtrWords));
-  HIPCHK(c.res.ensure_exact(std::max(kPingResWords, kFlowResWords) + kCalMaxBins));
+  // (a report's words and histogram, then the flow parts' words for tgsim_comm_flow_report)
+  HIPCHK(c.res.ensure_exact(kFlowPartRes + kFlowCcResWords + kFlowRtoResWords + kFlowFbResWords));
   HIPCHK(c.buf[0].ensure_exact(std::max<uint64_t>(entries, 1024)));
   HIPCHK(c.buf[1].ensure_exact(std::max<uint64_t>(entries, 1024)));
   HIPCHK(hipEventRecord(c.ev_recv, E->dst_st));  // (the first generation waits for it)
@@ -1604,6 +1612,8 @@ void flow_release(Eng* E) {
   E->d_fspec.release(); E->d_frow.release(); E->d_fbits.release(); E->d_fdue.release(); E->d_ffirst.release();
   E->d_fcnt.release(); E->d_fatt.release(); E->d_fcc.release(); E->d_frt.release(); E->d_fsent.release();
   E->d_ffb.release();
+  E->flow_sharded = false;
+  E->flow0 = E->n_own_flows = 0;
   E->flow_fb_on = false;
   E->flow_cc_on = false;
   E->flow_rto_on = false;
@@ -1612,8 +1622,10 @@ void flow_release(Eng* E) {
 
 FlowArgs flow_args(Eng* E, uint64_t win0, uint32_t n_ticks) {
   FlowArgs f{};
-  // (the flow driver's engine owns every peer)
-  f.cal = cal_args(E, 0, E->N, E->flow.ack_len, E->flow.n_bins, E->flow.bin_ns, win0, n_ticks);
+  // (tgsim_flow_init*: the shard is every peer, and the owned flows are the table)
+  f.cal = cal_args(E, E->o.shard_begin, E->S, E->flow.ack_len, E->flow.n_bins, E->flow.bin_ns, win0, n_ticks);
+  f.flow0 = E->flow0;
+  f.n_own_flows = E->n_own_flows;
   f.spec = E->d_fspec.p;
   f.rows = E->d_frow.p;
   f.bitmap = E->d_fbits.p;
@@ -1642,10 +1654,21 @@ FlowArgs flow_args(Eng* E, uint64_t win0, uint32_t n_ticks) {
 
 // The holder's receipts of one window's delivery-ordered records (off[nd] of them; n bounds the count),
 // behind its per-destination sort on the delivery stream; the next generation waits for ev_recv.
+int cal_grow(Eng* E, uint64_t need, uint64_t live);
 int cal_recv(Eng* E, const tgsim_delivery* recs, const uint64_t* off, uint32_t nd, uint64_t n, hipStream_t sq) {
   if (E->ping_on()) {
     launch_ping_recv(ping_args(E, 0, 0), recs, off, nd, n, sq);
   } else if (E->flow_on()) {
+    if (E->flow_sharded) {
+      // the growth bound of a shard: an entry is made from exactly one received record, so the buffers
+      // hold what the last generation kept plus every record received since.  How many of the live
+      // buffer's entries are in use is known on the device only: the old buffer is copied whole.  No
+      // host wait unless it grows.
+      Eng::ReplyCalendar& c = E->cal;
+      c.recv_since += n;
+      int rc = cal_grow(E, c.kept + c.recv_since, std::min(c.buf[0].cap, c.buf[1].cap));
+      if (rc) return rc;
+    }
     // the window's verdict feedback writes the same rows on the simulate stream, and takes effect first
     if (E->flow_fb_on) HIPCHK(hipStreamWaitEvent(sq, E->ev_fb, 0));
     launch_flow_recv(flow_args(E, 0, 0), recs, off, nd, n, sq);
@@ -1684,6 +1707,8 @@ struct CalNouns {
   const char* entries;  // "replies"
   const char* entry;    // "reply"
 };
+constexpr CalNouns kPingNouns{"ping", "replies", "reply"}, kFlowNouns{"flow", "ACKs", "receipt"};
+CalNouns cal_nouns(const Eng* E) { return E->flow_on() ? kFlowNouns : kPingNouns; }
 
 // One generated window [now, now + n_ticks) of the driver that holds the calendar, behind the driver's
 // own preconditions: the count pass, the counters published to the host, the scan, the growth, the
@@ -1723,6 +1748,7 @@ int cal_generate(Eng* E, uint32_t n_ticks, const CalNouns& nn, Count count, Writ
   const uint64_t cal_n = c[cal.cur];
   cal.appended += cal_n - cal.kept;  // what the deliveries since the last generation added
   cal.kept = cal_n;
+  cal.recv_since = 0;
   if (c[kCalOverflow]) {
     (void)retire_gen(E, std::move(w));
     cal.nospc = c[kCalOverflow];
@@ -1782,7 +1808,8 @@ int driver_busy(Eng* E, const char* who, bool sharded_ok = false,
   if (E->cal.owner == self) return 0;
   if (E->ping_on() && !(sharded_ok && E->ping_sharded))
     return E->fail(-EBUSY, "%s: the ping driver is armed (tgsim_ping_init(engine, NULL, NULL) disarms it)", who);
-  if (E->flow_on()) return E->fail(-EBUSY, "%s: the flow driver is armed (tgsim_flow_init(engine, NULL, NULL, 0) disarms it)", who);
+  if (E->flow_on() && !(sharded_ok && E->flow_sharded))
+    return E->fail(-EBUSY, "%s: the flow driver is armed (tgsim_flow_init(engine, NULL, NULL, 0) disarms it)", who);
   return 0;
 }
 
@@ -2376,13 +2403,17 @@ int64_t flow_rows_read(void* e, const char* who, const FlowPart& part, DevBuf<Ro
   if (first > E->n_flows || n > E->n_flows - first)
     return E->fail(-EINVAL, "%s: flows [%llu, %llu) outside [0, %llu)", who, static_cast<unsigned long long>(first),
                    static_cast<unsigned long long>(first + n), static_cast<unsigned long long>(E->n_flows));
+  if (first < E->flow0 || first + n > E->flow0 + E->n_own_flows)  // (the tables hold the owned flows, from flow0 on)
+    return E->fail(-EINVAL, "%s: flows [%llu, %llu) outside this shard's [%llu, %llu)", who, static_cast<unsigned long long>(first),
+                   static_cast<unsigned long long>(first + n), static_cast<unsigned long long>(E->flow0),
+                   static_cast<unsigned long long>(E->flow0 + E->n_own_flows));
   if (cap < n) return E->fail(-ENOSPC, "%s: %zu rows for %llu", who, cap, static_cast<unsigned long long>(n));
   if (n && !out) return E->fail(-EINVAL, "%s: no output buffer", who);
   HIPCHK(hipSetDevice(E->dev));
   int rc = sync_stream(E);
   if (rc) return rc;
   if (!n) return 0;
-  HIPCHK(hipMemcpyAsync(out, (E->*tab).p + first, sizeof(Row) * n, hipMemcpyDeviceToHost, E->st));
+  HIPCHK(hipMemcpyAsync(out, (E->*tab).p + (first - E->flow0), sizeof(Row) * n, hipMemcpyDeviceToHost, E->st));
   HIPCHK(hipStreamSynchronize(E->st));
   return static_cast<int64_t>(n);
 }
@@ -2412,35 +2443,38 @@ int engine_fail(void* e, int code, const char* msg) { return as_eng(e)->fail(cod
 void engine_persist_routed(void* e, uint32_t pct) { as_eng(e)->routed_pct = pct; }
 bool engine_ping_armed(void* e) { return as_eng(e)->ping_on(); }
 bool engine_ping_sharded(void* e) { return as_eng(e)->ping_on() && as_eng(e)->ping_sharded; }
+bool engine_flow_sharded(void* e) { return as_eng(e)->flow_on() && as_eng(e)->flow_sharded; }
 
-uint64_t engine_ping_fault(void* e, int rank, bool* agreed) {
+uint64_t engine_cal_fault(void* e, int rank, bool* agreed) {
   Eng* E = as_eng(e);
-  const Eng::ReplyCalendar& c = E->cal;  // (the faults of the calendar the sharded ping driver holds)
+  const Eng::ReplyCalendar& c = E->cal;  // (the faults of the calendar the sharded driver holds)
   *agreed = c.agreed != 0;
   if (c.agreed) return c.agreed;
   const uint64_t r = static_cast<uint64_t>(rank) & 15u;
-  if (c.nospc) return kPingFaultNospc << 62 | std::min<uint64_t>(c.nospc, (1ull << 50) - 1) << 4 | r;
-  if (c.late) return kPingFaultLate << 62 | c.late_tick << 4 | r;  // (ticks stay below 2^31)
+  if (c.nospc) return kCalFaultNospc << 62 | std::min<uint64_t>(c.nospc, (1ull << 50) - 1) << 4 | r;
+  if (c.late) return kCalFaultLate << 62 | c.late_tick << 4 | r;  // (ticks stay below 2^31)
   return 0;
 }
 
-// The text and code of an agreed fault word (of this or another rank).
-static int ping_fail_word(Eng* E, uint64_t word) {
+// The text and code of an agreed fault word (of this or another rank), in the holder's nouns.
+static int cal_fail_word(Eng* E, uint64_t word) {
+  const CalNouns nn = cal_nouns(E);
   const unsigned long long v = word >> 4 & ((1ull << 50) - 1), r = word & 15u;
-  if (word >> 62 == kPingFaultNospc)
-    return E->fail(-ENOSPC, "ping: %llu replies found the calendar full on rank %llu (tgsim_ping_init_sharded starts again)", v, r);
-  return E->fail(-EINVAL, "ping: a reply due at tick %llu preceded a window on rank %llu (every rank starts again "
-                          "with tgsim_ping_init_sharded)", v, r);
+  if (word >> 62 == kCalFaultNospc)
+    return E->fail(-ENOSPC, "%s: %llu %s found the calendar full on rank %llu (tgsim_%s_init_sharded starts again)", nn.who, v,
+                   nn.entries, r, nn.who);
+  return E->fail(-EINVAL, "%s: a %s due at tick %llu preceded a window on rank %llu (every rank starts again "
+                          "with tgsim_%s_init_sharded)", nn.who, nn.entry, v, r, nn.who);
 }
 
-int engine_ping_fail_agreed(void* e, uint64_t word) {
+int engine_cal_fail_agreed(void* e, uint64_t word) {
   Eng* E = as_eng(e);
   E->cal.agreed = word;
-  if (word >> 62 == kPingFaultLate && !E->cal.late) {  // this rank's own generation fails from now on, too
+  if (word >> 62 == kCalFaultLate && !E->cal.late) {  // this rank's own generation fails from now on, too
     E->cal.late = true;
     E->cal.late_tick = word >> 4 & 0xFFFFFFFFull;
   }
-  return ping_fail_word(E, word);
+  return cal_fail_word(E, word);
 }
 
 int engine_ping_report_dev(void* e, const unsigned long long** res, const unsigned long long** ctr, uint32_t* cal_word,
@@ -2459,6 +2493,31 @@ int engine_ping_report_dev(void* e, const unsigned long long** res, const unsign
   return 0;
 }
 bool engine_flow_armed(void* e) { return as_eng(e)->flow_on(); }
+void engine_flow_parts(void* e, bool* cc, bool* rto, bool* fb) {
+  *cc = as_eng(e)->flow_cc_on;
+  *rto = as_eng(e)->flow_rto_on;
+  *fb = as_eng(e)->flow_fb_on;
+}
+int engine_flow_report_dev(void* e, const unsigned long long** res, const unsigned long long** ctr, FlowPack* layout,
+                           uint32_t* seg_len, hipEvent_t ev) {
+  Eng* E = as_eng(e);
+  HIPCHK(hipSetDevice(E->dev));
+  int rc = sync_stream(E);  // the receipts of the last delivery are folded on the delivery stream
+  if (rc) return rc;
+  const FlowArgs f = flow_args(E, 0, 0);
+  unsigned long long* part = E->cal.res.p + kFlowPartRes;
+  launch_flow_report(f, E->cal.res.p, E->st);
+  if (E->flow_cc_on) launch_flow_cc_report(f, part, E->st);
+  if (E->flow_rto_on) launch_flow_rto_report(f, part + kFlowCcResWords, E->st);
+  if (E->flow_fb_on) launch_flow_fb_report(f, part + kFlowCcResWords + kFlowRtoResWords, E->st);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(ev, E->st));
+  *res = E->cal.res.p;
+  *ctr = E->cal.ctr.p;
+  *layout = flow_pack_layout(E->flow_cc_on, E->flow_rto_on, E->flow_fb_on, E->flow.n_bins, E->cal.cur);
+  *seg_len = E->flow.seg_len;
+  return 0;
+}
 const uint64_t* engine_route_counts_dev(void* e) {
   Eng* E = as_eng(e);
   return E->route_n && E->d_rsend.p ? E->d_rsend.p + 16 * E->route_head : nullptr;
@@ -3165,10 +3224,10 @@ int tgsim_gen_ping(void* e, uint32_t n_ticks) {
   // (sharded: between tgsim_comm_launch and tgsim_comm_finish the window's delivery, and with it its
   // receipts, is not enqueued yet: the calendar's ev_recv would not cover it)
   if (E->route_n) return E->fail(-EBUSY, "ping: a launched step is not finished (its receipts come first)");
-  if (E->cal.agreed) return ping_fail_word(E, E->cal.agreed);
+  if (E->cal.agreed) return cal_fail_word(E, E->cal.agreed);
   const uint32_t j_lo = ping_probes_before(E->ping, E->now_tick), j_hi = ping_probes_before(E->ping, E->now_tick + n_ticks);
   return cal_generate(
-      E, n_ticks, CalNouns{"ping", "replies", "reply"},
+      E, n_ticks, kPingNouns,
       [&](uint64_t cal_bound) {
         launch_ping_count(ping_args(E, E->now_tick, n_ticks), E->d_pslots.p, E->d_cnt.p, E->cal.cursor.p, cal_bound, E->st);
       },
@@ -3246,8 +3305,9 @@ int tgsim_flow_init_rto(void* e, const tgsim_flow* p, const tgsim_flow_cc* cc, c
   return tgsim_flow_init_fb(e, p, cc, rto, nullptr, flows, n_flows);
 }
 
-int tgsim_flow_init_fb(void* e, const tgsim_flow* p, const tgsim_flow_cc* cc, const tgsim_flow_rto* rto,
-                       const tgsim_flow_fb* fb, const tgsim_flow_spec* flows, uint64_t n_flows) {
+// tgsim_flow_init_fb and tgsim_flow_init_sharded: the same rules, less the ownership test of the first.
+static int flow_arm(void* e, const tgsim_flow* p, const tgsim_flow_cc* cc, const tgsim_flow_rto* rto,
+                    const tgsim_flow_fb* fb, const tgsim_flow_spec* flows, uint64_t n_flows, bool sharded) {
   Eng* E = as_eng(e);
   if (!E) return -EINVAL;
   HIPCHK(hipSetDevice(E->dev));
@@ -3255,11 +3315,16 @@ int tgsim_flow_init_fb(void* e, const tgsim_flow* p, const tgsim_flow_cc* cc, co
     if (flows || n_flows) return E->fail(-EINVAL, "flow: a flow table without parameters");
     int rc = sync_stream(E);
     if (rc) return rc;
-    if (E->flow_on()) flow_release(E);
+    if (E->flow_on()) {
+      // a window of the sharded form still pending belongs to a step the ranks refused (a late receipt
+      // on another rank): it goes with the driver, or the rank could never generate again
+      if (E->flow_sharded) drop_gen(E);
+      flow_release(E);
+    }
     return 0;
   }
   if (!flows || !n_flows) return E->fail(-EINVAL, "flow: no flow table");
-  if (E->S != E->N)
+  if (!sharded && E->S != E->N)
     return E->fail(-EINVAL, "flow: this engine owns peers [%u, %u) of %u (the driver needs one engine for every peer)",
                    E->o.shard_begin, E->o.shard_end, E->N);
   if (p->seg_len == 0 || p->seg_len > 65535) return E->fail(-EINVAL, "flow: seg_len %u outside 1..65535", p->seg_len);
@@ -3295,7 +3360,10 @@ int tgsim_flow_init_fb(void* e, const tgsim_flow* p, const tgsim_flow_cc* cc, co
   if (!E->staged.empty()) return E->fail(-EBUSY, "flow: host packets are pending for the next step");
   if (!E->gen_q.empty() || E->route_n) return E->fail(-EBUSY, "flow: generated windows or launched steps are pending");
   std::vector<uint32_t> first(E->N, 0), cnt(E->N, 0);
-  uint64_t in_flight = 0;
+  // in_flight: the segments in flight to start with whose ACK entries are made here (the flows whose dst
+  // this engine owns: every flow of a whole-peer engine); [flow0, flow0 + n_own): the owned sources' flows
+  const uint32_t b0 = E->o.shard_begin, b1 = E->o.shard_end;
+  uint64_t in_flight = 0, flow0 = n_flows, n_own = 0;
   for (uint64_t i = 0; i < n_flows; ++i) {
     const tgsim_flow_spec& f = flows[i];
     const unsigned long long ii = i;
@@ -3314,8 +3382,14 @@ int tgsim_flow_init_fb(void* e, const tgsim_flow* p, const tgsim_flow_cc* cc, co
                      TGSIM_FLOW_SLOTS);
     if (!cnt[f.src]) first[f.src] = static_cast<uint32_t>(i);
     ++cnt[f.src];
-    in_flight += std::min(p->window, f.n_seg);
+    if (f.dst >= b0 && f.dst < b1) in_flight += std::min(p->window, f.n_seg);
+    if (f.src >= b0 && f.src < b1) {
+      if (!n_own) flow0 = i;
+      ++n_own;
+    }
   }
+  // (buffers that kernels index are never empty, though a shard without a flow launches none of them)
+  const uint64_t n_rows = std::max<uint64_t>(n_own, 1);
   int rc = sync_stream(E);  // a re-init: the last delivery's receipts may still run
   if (rc) return rc;
   if (fb && !E->ev_fb) HIPCHK(hipEventCreateWithFlags(&E->ev_fb, hipEventDisableTiming));
@@ -3323,30 +3397,33 @@ int tgsim_flow_init_fb(void* e, const tgsim_flow* p, const tgsim_flow_cc* cc, co
   E->flow = *p;
   E->n_flows = n_flows;
   E->flow_offered = 0;
+  E->flow_sharded = sharded;
+  E->flow0 = flow0;
+  E->n_own_flows = n_own;
   E->flow_cc_on = cc != nullptr;
   E->flow_cc = cc ? *cc : tgsim_flow_cc{};
-  if (cc) HIPCHK(E->d_fcc.ensure_exact(n_flows));
+  if (cc) HIPCHK(E->d_fcc.ensure_exact(n_rows));
   E->flow_rto_on = rto != nullptr;
   E->flow_rto = rto ? *rto : tgsim_flow_rto{};
   if (rto) {
-    HIPCHK(E->d_frt.ensure_exact(n_flows));
-    HIPCHK(E->d_fsent.ensure_exact(n_flows * p->window));
+    HIPCHK(E->d_frt.ensure_exact(n_rows));
+    HIPCHK(E->d_fsent.ensure_exact(n_rows * p->window));
   }
   E->flow_fb_on = fb != nullptr;
   E->flow_fb = fb ? *fb : tgsim_flow_fb{};
   if (fb) {
-    HIPCHK(E->d_ffb.ensure_exact(n_flows));
+    HIPCHK(E->d_ffb.ensure_exact(n_rows));
     HIPCHK(hipEventRecord(E->ev_fb, E->st));  // (flow_recv waits for it even behind a window that offered nothing)
   }
   HIPCHK(E->d_fspec.ensure_exact(n_flows));
-  HIPCHK(E->d_frow.ensure_exact(n_flows));
-  HIPCHK(E->d_fbits.ensure_exact(n_flows));
-  HIPCHK(E->d_fdue.ensure_exact(n_flows * p->window));
-  HIPCHK(E->d_fatt.ensure_exact(n_flows * p->window));
+  HIPCHK(E->d_frow.ensure_exact(n_rows));
+  HIPCHK(E->d_fbits.ensure_exact(n_rows));
+  HIPCHK(E->d_fdue.ensure_exact(n_rows * p->window));
+  HIPCHK(E->d_fatt.ensure_exact(n_rows * p->window));
   HIPCHK(E->d_ffirst.ensure_exact(E->N));
   HIPCHK(E->d_fcnt.ensure_exact(E->N));
   // an ACK per segment in flight to start with; tgsim_gen_flow grows it for retransmissions
-  rc = cal_arm(E, E->N, in_flight);
+  rc = cal_arm(E, E->S, in_flight);
   if (rc) return rc;
   HIPCHK(hipMemcpy(E->d_fspec.p, flows, sizeof(tgsim_flow_spec) * n_flows, hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(E->d_ffirst.p, first.data(), sizeof(uint32_t) * E->N, hipMemcpyHostToDevice));
@@ -3355,6 +3432,26 @@ int tgsim_flow_init_fb(void* e, const tgsim_flow* p, const tgsim_flow_cc* cc, co
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(E->st));
   E->cal.owner = Eng::ReplyCalendar::kFlow;
+  return 0;
+}
+
+int tgsim_flow_init_fb(void* e, const tgsim_flow* p, const tgsim_flow_cc* cc, const tgsim_flow_rto* rto,
+                       const tgsim_flow_fb* fb, const tgsim_flow_spec* flows, uint64_t n_flows) {
+  return flow_arm(e, p, cc, rto, fb, flows, n_flows, false);
+}
+
+int tgsim_flow_init_sharded(void* e, const tgsim_flow* p, const tgsim_flow_cc* cc, const tgsim_flow_rto* rto,
+                            const tgsim_flow_fb* fb, const tgsim_flow_spec* flows, uint64_t n_flows) {
+  return flow_arm(e, p, cc, rto, fb, flows, n_flows, true);
+}
+
+int tgsim_flow_owned(void* e, uint64_t* first, uint64_t* n) {
+  Eng* E = as_eng(e);
+  if (!E) return -EINVAL;
+  if (!E->flow_on()) return E->fail(-EINVAL, "flow_owned: the flow driver is not armed (tgsim_flow_init)");
+  if (!first || !n) return E->fail(-EINVAL, "flow_owned: no output");
+  *first = E->flow0;
+  *n = E->n_own_flows;
   return 0;
 }
 
@@ -3370,16 +3467,24 @@ int tgsim_gen_flow(void* e, uint32_t n_ticks) {
                    n_ticks, E->flow.rto_ticks);
   if (!E->staged.empty()) return E->fail(-EBUSY, "host packets already pending for the next step");
   if (!E->gen_q.empty()) return E->fail(-EBUSY, "flow: a generated window is pending (one window at a time)");
+  // (sharded: between tgsim_comm_launch and tgsim_comm_finish the window's delivery, and with it its
+  // receipts, is not enqueued yet: the calendar's ev_recv would not cover it)
+  if (E->route_n) return E->fail(-EBUSY, "flow: a launched step is not finished (its receipts come first)");
+  if (E->cal.agreed) return cal_fail_word(E, E->cal.agreed);
   return cal_generate(
-      E, n_ticks, CalNouns{"flow", "ACKs", "receipt"},
+      E, n_ticks, kFlowNouns,
       [&](uint64_t cal_bound) {
         launch_flow_count(flow_args(E, E->now_tick, n_ticks), E->d_cnt.p, E->cal.cursor.p, cal_bound, E->st);
       },
       [&](Eng::GenWindow& w, uint64_t cal_bound) {
         launch_flow_write(flow_args(E, E->now_tick, n_ticks), w.off.p, E->cal.cursor.p, E->cal.tmp.p, w.in.p, cal_bound, E->st);
       },
-      // an ACK for every data packet offered by the end of this window
-      [&](const uint64_t* c) { return E->flow_offered += c[kCalOffers]; },
+      // an ACK for every data packet offered by the end of this window; a shard sees only its own
+      // offers, so its calendar grows ahead of each delivery's receipts instead (cal_recv)
+      [&](const uint64_t* c) {
+        E->flow_offered += c[kCalOffers];
+        return E->flow_sharded ? uint64_t{0} : E->flow_offered;
+      },
       [&](const uint64_t* c) { return c[kCalOffers]; });
 }
 

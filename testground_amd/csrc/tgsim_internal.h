@@ -388,35 +388,78 @@ constexpr uint32_t kPingResWords = 8;   // pairs sent received sum min max pairs
 // fields in tgsim_ping_summary order, then the histogram), then min_ns, then max_ns.
 constexpr uint32_t kPingPackSums = 9;
 constexpr uint32_t kPingPackWords = kPingPackSums + kCalMaxBins + 2;
-// Flow driver (tgsim_flow_*) of an engine that owns every peer; its ACKs are `cal`'s entries.
+// Flow driver (tgsim_flow_*); its ACKs are `cal`'s entries.  An engine armed through
+// tgsim_flow_init* owns every peer; tgsim_flow_init_sharded arms one that owns the peers
+// [cal.first, cal.first + cal.n_own) and with them the flows [flow0, flow0 + n_own_flows) of the table (it
+// is sorted by src).  The spec table and first[] / cnt[] are the whole run's and take global indices; the
+// per-flow state (rows, bitmap, rings, cc / rto / fb rows) is the owned flows', indexed by flow - flow0;
+// counts, cursors and offsets are per owned source (src - cal.first).
 constexpr uint32_t kFlowResWords = 11;  // flows done failed active segs offered retransmits stale fct_sum fct_min fct_max
 struct FlowArgs {
   CalArgs cal;
   const tgsim_flow_spec* spec;  // [n_flows], sorted by src
-  tgsim_flow_row* rows;         // [n_flows]
-  uint64_t* bitmap;             // [n_flows] acknowledged segments of [base, base + 64)
-  uint32_t* due;                // [n_flows][window] ring indexed seg % window
-  uint8_t* att;                 // [n_flows][window]
+  tgsim_flow_row* rows;         // [n_own_flows]
+  uint64_t* bitmap;             // [n_own_flows] acknowledged segments of [base, base + 64)
+  uint32_t* due;                // [n_own_flows][window] ring indexed seg % window
+  uint8_t* att;                 // [n_own_flows][window]
   const uint32_t* first;        // [n_peers] first flow of the source
   const uint32_t* cnt;          // [n_peers] its flows (<= TGSIM_FLOW_SLOTS)
   uint64_t n_flows;
+  uint64_t flow0, n_own_flows;  // the owned flows; a whole-peer engine: 0, n_flows
   uint32_t seg_len, window, rto, max_attempts;
   // congestion control (tgsim_flow_init_cc); cc == nullptr: armed without it
-  tgsim_flow_cc_row* cc;        // [n_flows]
+  tgsim_flow_cc_row* cc;        // [n_own_flows]
   uint32_t init_cwnd, init_ssthresh, dupthresh;
   // RTT estimator and timer backoff (tgsim_flow_init_rto); rt == nullptr: armed
   // without it, and `rto` above is every segment's timer.  With it `rto` is the initial timer.
   uint32_t backoff;
-  tgsim_flow_rto_row* rt;       // [n_flows]
-  uint32_t* sent;               // [n_flows][window] ring beside due and att: the tick of attempt 0
+  tgsim_flow_rto_row* rt;       // [n_own_flows]
+  uint32_t* sent;               // [n_own_flows][window] ring beside due and att: the tick of attempt 0
   uint32_t min_rto, max_rto;
   // verdict feedback (tgsim_flow_init_fb); fb == nullptr: armed without it
   uint32_t fail_mask;           // bit 1 << v: a data offer refused with verdict v fails its flow
-  tgsim_flow_fb_row* fb;        // [n_flows]
+  tgsim_flow_fb_row* fb;        // [n_own_flows]
 };
+// tgsim_comm_flow_report's packed words: three runs for the ranks' all-reduces.  Sums: the summary's
+// thirteen summed fields in tgsim_flow_summary order, then (each only where armed, the same on every rank)
+// cc's five, rto's four and fb's eleven, then the histogram bins; mins: fct_min_ns, then cwnd_min, then
+// srtt_min and rto_min; maxes likewise.  flow_pack_layout gives the runs' lengths and the parts' places.
+constexpr uint32_t kFlowPackBase = 13, kFlowPackCc = 5, kFlowPackRto = 4, kFlowPackFb = 11;
+constexpr uint32_t kFlowPackWords = kFlowPackBase + kFlowPackCc + kFlowPackRto + kFlowPackFb + kCalMaxBins + 4 + 4;
+struct FlowPack {
+  uint32_t cc, rto, fb;          // 1: the part is armed
+  uint32_t n_bins, cal_word;
+  uint32_t s_cc, s_rto, s_fb, s_hist, n_sum;  // places in the sum run, its length
+  uint32_t m_cc, m_rto, n_min;   // places in the min run (and the max run), its length
+};
+__host__ __device__ inline FlowPack flow_pack_layout(bool cc, bool rto, bool fb, uint32_t n_bins, uint32_t cal_word) {
+  FlowPack p{};
+  p.cc = cc; p.rto = rto; p.fb = fb;
+  p.n_bins = n_bins;
+  p.cal_word = cal_word;
+  p.s_cc = kFlowPackBase;
+  p.s_rto = p.s_cc + (cc ? kFlowPackCc : 0);
+  p.s_fb = p.s_rto + (rto ? kFlowPackRto : 0);
+  p.s_hist = p.s_fb + (fb ? kFlowPackFb : 0);
+  p.n_sum = p.s_hist + n_bins;
+  p.m_cc = 1;
+  p.m_rto = p.m_cc + (cc ? 1 : 0);
+  p.n_min = p.m_rto + (rto ? 2 : 0);
+  return p;
+}
+// The pinned block k_flow_unpack fills: the four summaries as u64 words in struct order, the histogram,
+// the sequence word.
+constexpr uint32_t kFlowHostBase = 15, kFlowHostCc = 7, kFlowHostRto = 8, kFlowHostFb = 11;
+constexpr uint32_t kFlowHostHist = kFlowHostBase + kFlowHostCc + kFlowHostRto + kFlowHostFb;
+constexpr uint32_t kFlowHostWords = kFlowHostHist + kCalMaxBins + 1;
+constexpr uint32_t kReportSeqWord = kFlowHostWords - 1;  // (the ping report's block is the same one)
 constexpr uint32_t kFlowCcResWords = 7;  // loss_events fast_retransmits timeouts active cwnd_sum cwnd_min cwnd_max
 constexpr uint32_t kFlowRtoResWords = 8;  // samples sampled_flows srtt_sum srtt_min srtt_max rto_sum rto_min rto_max
 constexpr uint32_t kFlowFbResWords = 11;  // scheduled lost queue_full refused cloned refused_flows failed_timer failed_by[4]
+// The calendar's result buffer: a report's words and histogram, then (tgsim_comm_flow_report, which
+// needs all four at once) the cc, rto and fb words from kFlowPartRes on.
+constexpr uint32_t kFlowPartRes = kFlowResWords + kCalMaxBins;
+static_assert(kPingResWords <= kFlowResWords, "the result buffer is sized by the flow report");
 
 // Per-group traffic matrix (tgsim_groups_init / tgsim_group_matrix).
 constexpr uint32_t kGroupWords = TGSIM_GROUP_WORDS, kGroupMax = TGSIM_GROUP_MAX;
@@ -448,15 +491,15 @@ void engine_persist_routed(void* engine, uint32_t pct);
 bool engine_ping_armed(void* engine);
 // ... unless it was armed through tgsim_ping_init_sharded (closed windows only: tgsim_comm_run refuses).
 bool engine_ping_sharded(void* engine);
-// The sharded ping driver's sticky fault as one word for the ranks' max all-reduce (0: none):
-// kind << 62 (kPingFaultLate / kPingFaultNospc) | value << 4 (the late tick, or the entries that found
-// the calendar full, clamped to 2^50) | rank.  *agreed: the word is one the ranks agreed on already
-// (engine_ping_fail_agreed), so every rank holds it and none exchanges it again.
-constexpr uint64_t kPingFaultLate = 1, kPingFaultNospc = 2;
-uint64_t engine_ping_fault(void* engine, int rank, bool* agreed);
+// The sticky fault of the reply calendar's holder (the sharded ping or flow driver) as one word for the
+// ranks' max all-reduce (0: none): kind << 62 (kCalFaultLate / kCalFaultNospc) | value << 4 (the late
+// tick, or the entries that found the calendar full, clamped to 2^50) | rank.  *agreed: the word is one
+// the ranks agreed on already (engine_cal_fail_agreed), so every rank holds it and none exchanges it again.
+constexpr uint64_t kCalFaultLate = 1, kCalFaultNospc = 2;
+uint64_t engine_cal_fault(void* engine, int rank, bool* agreed);
 // Makes the ranks' agreed fault word this engine's own sticky error (until it re-arms) and fails with
-// it: -EINVAL for a late receipt, -ENOSPC for a full calendar; the text names the rank.
-int engine_ping_fail_agreed(void* engine, uint64_t word);
+// it, in the holder's nouns: -EINVAL for a late receipt, -ENOSPC for a full calendar; the text names the rank.
+int engine_cal_fail_agreed(void* engine, uint64_t word);
 // The local report's words on the device for tgsim_comm_ping_report, after k_ping_report on the
 // simulate stream: res = [kPingResWords + n_bins], ctr = the driver's counters (kCal*); cal_word is the
 // counter of the live calendar.  `ev` is recorded behind them.
@@ -466,8 +509,17 @@ int engine_ping_report_dev(void* engine, const unsigned long long** res, const u
 // with one chunk, which the sharded ping driver accepts (the public call refuses while it is armed).
 int engine_step_sim_launch_route1(void* engine, uint32_t n_ticks, const uint32_t* bounds, void* d_out,
                                   uint64_t slot_cap, void* routed_event);
-// The same for the flow driver (tgsim_flow_init).
+// The same for the flow driver (tgsim_flow_init*), and for its sharded form (tgsim_flow_init_sharded).
 bool engine_flow_armed(void* engine);
+bool engine_flow_sharded(void* engine);
+// Which of its optional parts are armed.
+void engine_flow_parts(void* engine, bool* cc, bool* rto, bool* fb);
+// The local reports' words on the device for tgsim_comm_flow_report, after the report kernels on the
+// simulate stream: res = k_flow_report's words and histogram, then from kFlowPartRes the armed parts' words
+// (cc, rto, fb, at fixed places); ctr = the calendar's counters; layout: the pack layout of this arming.
+// `ev` is recorded behind them.
+int engine_flow_report_dev(void* engine, const unsigned long long** res, const unsigned long long** ctr, FlowPack* layout,
+                           uint32_t* seg_len, hipEvent_t ev);
 // Records `ev` on the routing stream after every routing enqueued so far (the exchange of a launched
 // window waits for it on the device, not only for the host's view of the published edges).
 int engine_record_routed(void* engine, hipEvent_t ev);

@@ -3567,7 +3567,8 @@ __global__ __launch_bounds__(256) void k_ping_pack(const unsigned long long* __r
 }
 
 // ... and the reduced runs as the tgsim_ping_summary (11 u64 words) followed by the histogram, in the
-// pinned block the host reads, then the sequence word behind a system-scope release (as k_publish_words).
+// pinned block the host reads (shared with the flow report: kFlowHostWords), then the block's sequence
+// word behind a system-scope release (as k_publish_words).
 __global__ __launch_bounds__(256) void k_ping_unpack(const unsigned long long* __restrict__ in, uint32_t n_bins,
                                                      uint64_t* __restrict__ host, uint64_t seq) {
   const uint32_t i = threadIdx.x;
@@ -3579,7 +3580,7 @@ __global__ __launch_bounds__(256) void k_ping_unpack(const unsigned long long* _
     __hip_atomic_store(&host[11 + i], (uint64_t)in[kPingPackSums + i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
   __threadfence_system();
   __syncthreads();
-  if (i == 0) __hip_atomic_store(&host[11 + kCalMaxBins], seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+  if (i == 0) __hip_atomic_store(&host[kReportSeqWord], seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -3687,11 +3688,11 @@ __global__ __launch_bounds__(256) void k_flow_recv_ack(FlowArgs f, const tgsim_d
   const CalArgs& a = f.cal;
   for (uint32_t i = threadIdx.x; i < a.n_bins; i += 256) hist[i] = 0u;
   __syncthreads();
-  const uint64_t fl = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-  if (fl < f.n_flows) {
-    const tgsim_flow_spec sp = f.spec[fl];
-    const uint32_t slot = (uint32_t)(fl - f.first[sp.src]);
-    uint64_t b = off[sp.src], e = off[sp.src + 1];
+  const uint64_t fl = (uint64_t)blockIdx.x * 256 + threadIdx.x;  // (owned flow flow0 + fl: its state is at fl)
+  if (fl < f.n_own_flows) {
+    const tgsim_flow_spec sp = f.spec[f.flow0 + fl];
+    const uint32_t slot = (uint32_t)(f.flow0 + fl - f.first[sp.src]), ls = sp.src - a.first;  // (ls < n_own: an owned flow)
+    uint64_t b = off[ls], e = off[ls + 1];
     e = e < n_bound ? e : n_bound;  // (never past the buffer the bound sized)
     tgsim_flow_row row = f.rows[fl];
     [[maybe_unused]] tgsim_flow_cc_row c{};
@@ -3845,11 +3846,11 @@ template <bool CC>
 __global__ __launch_bounds__(256) void k_flow_count(FlowArgs f, uint64_t* counts) {
   const uint64_t fl = (uint64_t)blockIdx.x * 256 + threadIdx.x;
   FlowDue d{0u, ~0u, ~0u};
-  if (fl < f.n_flows) {
-    const tgsim_flow_spec sp = f.spec[fl];
+  if (fl < f.n_own_flows) {  // (owned flow flow0 + fl; counts are per owned source)
+    const tgsim_flow_spec sp = f.spec[f.flow0 + fl];
     const tgsim_flow_row row = f.rows[fl];
     d = flow_due<CC>(f, fl, row, f.bitmap[fl], flow_n_fly<CC>(f, fl, sp, row));
-    if (d.n) atomicAdd(reinterpret_cast<unsigned long long*>(&counts[sp.src]), (unsigned long long)d.n);
+    if (d.n) atomicAdd(reinterpret_cast<unsigned long long*>(&counts[sp.src - f.cal.first]), (unsigned long long)d.n);
   }
   const uint64_t tot = wave_sum(d.n), late = wave_min_max_u64(d.late == ~0u ? ~0ull : d.late, false);
   if ((threadIdx.x & 63u) == 0) {
@@ -3867,8 +3868,8 @@ __global__ __launch_bounds__(256) void k_flow_count(FlowArgs f, uint64_t* counts
 template <bool CC, bool RTO>
 __global__ __launch_bounds__(256) void k_flow_write(FlowArgs f, const uint64_t* __restrict__ off, uint32_t* cursor, InRec* out) {
   const uint64_t fl = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-  if (fl >= f.n_flows) return;
-  const tgsim_flow_spec sp = f.spec[fl];
+  if (fl >= f.n_own_flows) return;  // (owned flow flow0 + fl)
+  const tgsim_flow_spec sp = f.spec[f.flow0 + fl];
   tgsim_flow_row row = f.rows[fl];
   const uint64_t bm = f.bitmap[fl];
   [[maybe_unused]] tgsim_flow_cc_row c{};
@@ -3882,8 +3883,8 @@ __global__ __launch_bounds__(256) void k_flow_write(FlowArgs f, const uint64_t* 
   const FlowDue d = flow_due<CC>(f, fl, row, bm, n_fly);
   if (!d.n && d.fail == ~0u) return;
   const uint32_t win0 = (uint32_t)f.cal.win0, win1 = win0 + f.cal.n_ticks;
-  const uint32_t slot = (uint32_t)(fl - f.first[sp.src]);
-  uint64_t pos = d.n ? off[sp.src] + atomicAdd(&cursor[sp.src], d.n) : 0;
+  const uint32_t slot = (uint32_t)(f.flow0 + fl - f.first[sp.src]), ls = sp.src - f.cal.first;
+  uint64_t pos = d.n ? off[ls] + atomicAdd(&cursor[ls], d.n) : 0;
   [[maybe_unused]] bool loss = false;
   uint32_t rto = f.rto;
   if constexpr (RTO) rto = f.rt[fl].rto;
@@ -3940,8 +3941,8 @@ __global__ __launch_bounds__(256) void k_flow_write(FlowArgs f, const uint64_t* 
 template <bool CC, bool RTO>
 __global__ __launch_bounds__(256) void k_flow_init(FlowArgs f) {
   const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i < f.n_flows) {
-    const tgsim_flow_spec sp = f.spec[i];
+  if (i < f.n_own_flows) {
+    const tgsim_flow_spec sp = f.spec[f.flow0 + i];
     f.rows[i] = tgsim_flow_row{};
     f.bitmap[i] = 0ull;
     for (uint32_t k = 0; k < f.window; ++k) {
@@ -3973,7 +3974,7 @@ __global__ __launch_bounds__(256) void k_flow_init(FlowArgs f) {
 __global__ __launch_bounds__(256) void k_flow_cc_report(FlowArgs f, unsigned long long* res) {
   uint64_t v[kFlowCcResWords] = {};
   v[5] = ~0ull;
-  for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < f.n_flows; i += (uint64_t)gridDim.x * 256) {
+  for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < f.n_own_flows; i += (uint64_t)gridDim.x * 256) {
     const tgsim_flow_cc_row c = f.cc[i];
     v[0] += c.loss_events;
     v[1] += c.fast_retransmits;
@@ -3993,7 +3994,7 @@ __global__ __launch_bounds__(256) void k_flow_cc_report(FlowArgs f, unsigned lon
 // complemented (words 3 and 6 hold the maximum of ~x), so res starts as zeros.
 __global__ __launch_bounds__(256) void k_flow_rto_report(FlowArgs f, unsigned long long* res) {
   uint64_t v[kFlowRtoResWords] = {};
-  for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < f.n_flows; i += (uint64_t)gridDim.x * 256) {
+  for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < f.n_own_flows; i += (uint64_t)gridDim.x * 256) {
     const tgsim_flow_rto_row q = f.rt[i];
     if (!q.samples) continue;
     const uint64_t srtt = q.srtt8 >> 3, nsrtt = ~srtt, nrto = ~(uint64_t)q.rto;
@@ -4019,12 +4020,13 @@ __global__ __launch_bounds__(256) void k_flow_rto_report(FlowArgs f, unsigned lo
 __global__ __launch_bounds__(256) void k_flow_fb(FlowArgs f, const uint64_t* __restrict__ off, const InRec* __restrict__ in,
                                                  const uint8_t* __restrict__ verdict, uint64_t n_in) {
   const uint64_t fl = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-  if (fl >= f.n_flows) return;
-  const tgsim_flow_spec sp = f.spec[fl];
-  uint64_t b = off[sp.src], e = off[sp.src + 1];
+  if (fl >= f.n_own_flows) return;  // (owned flow flow0 + fl; off[] is per owned source)
+  const tgsim_flow_spec sp = f.spec[f.flow0 + fl];
+  const uint32_t ls = sp.src - f.cal.first;
+  uint64_t b = off[ls], e = off[ls + 1];
   e = e < n_in ? e : n_in;  // (never past the buffers the window sized)
   if (b >= e) return;
-  const uint32_t slot = (uint32_t)(fl - f.first[sp.src]);
+  const uint32_t slot = (uint32_t)(f.flow0 + fl - f.first[sp.src]);
   uint32_t seen = 0, sched = 0, lost = 0, full = 0, refused = 0, cloned = 0, fv = 0;
   uint64_t key = ~0ull;  // tick << 32 | seq of the earliest refusal that fails the flow
   for (; b < e; ++b) {
@@ -4072,7 +4074,7 @@ __global__ __launch_bounds__(256) void k_flow_fb(FlowArgs f, const uint64_t* __r
 // every flow, and the FAILED flows by cause (word 6: the timer; words 7..10: verdict 1..4).
 __global__ __launch_bounds__(256) void k_flow_fb_report(FlowArgs f, unsigned long long* res) {
   uint64_t v[kFlowFbResWords] = {};
-  for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < f.n_flows; i += (uint64_t)gridDim.x * 256) {
+  for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < f.n_own_flows; i += (uint64_t)gridDim.x * 256) {
     const tgsim_flow_fb_row q = f.fb[i];
     v[0] += q.scheduled;
     v[1] += q.lost;
@@ -4094,7 +4096,7 @@ __global__ __launch_bounds__(256) void k_flow_fb_report(FlowArgs f, unsigned lon
 __global__ __launch_bounds__(256) void k_flow_report(FlowArgs f, unsigned long long* res) {
   uint64_t v[kFlowResWords] = {};
   v[9] = ~0ull;
-  for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < f.n_flows; i += (uint64_t)gridDim.x * 256) {
+  for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < f.n_own_flows; i += (uint64_t)gridDim.x * 256) {
     const tgsim_flow_row r = f.rows[i];
     ++v[0];
     v[1] += r.state == TGSIM_FLOW_DONE;
@@ -4105,13 +4107,95 @@ __global__ __launch_bounds__(256) void k_flow_report(FlowArgs f, unsigned long l
     v[6] += r.retransmits;
     v[7] += r.stale_acks;
     if (r.state == TGSIM_FLOW_DONE) {
-      const uint64_t fct = r.done_ns - (uint64_t)f.spec[i].start_tick * f.cal.tick_ns;
+      const uint64_t fct = r.done_ns - (uint64_t)f.spec[f.flow0 + i].start_tick * f.cal.tick_ns;
       v[8] += fct;
       v[9] = fct < v[9] ? fct : v[9];
       v[10] = fct > v[10] ? fct : v[10];
     }
   }
   report_commit<kFlowResWords, 1u << 9, 1u << 10>(v, res);
+}
+
+// tgsim_comm_flow_report: the local reports (res: k_flow_report's words and histogram; cc / rt / fb: the
+// armed parts' result words, null where L says unarmed; ctr: the calendar's counters) as the three runs
+// of FlowPack for the ranks' all-reduces.  A shard with nothing to report holds the neutral values
+// already (UINT64_MAX for a minimum, 0 otherwise; the rto minima travel complemented in their result
+// words and are restored here).  A few hundred words: one workgroup, a word per lane.
+__global__ __launch_bounds__(256) void k_flow_pack(const unsigned long long* __restrict__ res,
+                                                   const unsigned long long* __restrict__ cc,
+                                                   const unsigned long long* __restrict__ rt,
+                                                   const unsigned long long* __restrict__ fb,
+                                                   const unsigned long long* __restrict__ ctr, FlowPack L,
+                                                   uint32_t seg_len, unsigned long long* __restrict__ out) {
+  const uint32_t i = threadIdx.x;
+  unsigned long long* mn = out + L.n_sum;
+  unsigned long long* mx = mn + L.n_min;
+  if (i == 0) {
+    out[0] = res[0];  // flows done failed active
+    out[1] = res[1];
+    out[2] = res[2];
+    out[3] = res[3];
+    out[4] = res[4];             // segs_acked
+    out[5] = res[4] * seg_len;   // bytes_acked
+    out[6] = res[5];  // data_offered retransmits stale_acks
+    out[7] = res[6];
+    out[8] = res[7];
+    out[9] = ctr[kCalDup];
+    out[10] = ctr[kCalCorrupt];
+    out[11] = ctr[L.cal_word];  // pending_acks
+    out[12] = res[8];           // fct_sum_ns
+    mn[0] = res[9];             // fct_min_ns
+    mx[0] = res[10];            // fct_max_ns
+  }
+  if (L.cc && i == 1) {  // loss_events fast_retransmits timeouts active cwnd_sum | cwnd_min | cwnd_max
+    for (uint32_t k = 0; k < kFlowPackCc; ++k) out[L.s_cc + k] = cc[k];
+    mn[L.m_cc] = cc[5];
+    mx[L.m_cc] = cc[6];
+  }
+  if (L.rto && i == 2) {  // samples sampled_flows srtt_sum rto_sum | srtt_min rto_min | srtt_max rto_max
+    out[L.s_rto] = rt[0];
+    out[L.s_rto + 1] = rt[1];
+    out[L.s_rto + 2] = rt[2];
+    out[L.s_rto + 3] = rt[5];
+    mn[L.m_rto] = ~rt[3];
+    mn[L.m_rto + 1] = ~rt[6];
+    mx[L.m_rto] = rt[4];
+    mx[L.m_rto + 1] = rt[7];
+  }
+  if (L.fb && i >= 64 && i < 64 + kFlowPackFb) out[L.s_fb + (i - 64)] = fb[i - 64];
+  if (i < L.n_bins) out[L.s_hist + i] = res[kFlowResWords + i];  // (n_bins <= kCalMaxBins = the workgroup)
+}
+
+// ... and the reduced runs as the four summaries' u64 words in struct order (kFlowHost*: an unarmed
+// part's words are zero) followed by the histogram, in the pinned block the host reads, then the
+// sequence word behind a system-scope release (as k_ping_unpack).
+__global__ __launch_bounds__(256) void k_flow_unpack(const unsigned long long* __restrict__ in, FlowPack L,
+                                                     uint64_t* __restrict__ host, uint64_t seq) {
+  const uint32_t i = threadIdx.x;
+  const unsigned long long* mn = in + L.n_sum;
+  const unsigned long long* mx = mn + L.n_min;
+  if (i < kFlowHostHist) {
+    unsigned long long v = 0;
+    if (i < kFlowHostBase) {
+      v = i < kFlowPackBase ? in[i] : i == kFlowPackBase ? mn[0] : mx[0];
+    } else if (i < kFlowHostBase + kFlowHostCc) {
+      const uint32_t k = i - kFlowHostBase;
+      if (L.cc) v = k < kFlowPackCc ? in[L.s_cc + k] : k == kFlowPackCc ? mn[L.m_cc] : mx[L.m_cc];
+    } else if (i < kFlowHostBase + kFlowHostCc + kFlowHostRto) {
+      const uint32_t k = i - kFlowHostBase - kFlowHostCc;  // samples sampled_flows srtt_sum srtt_min srtt_max rto_sum rto_min rto_max
+      if (L.rto)
+        v = k < 3 ? in[L.s_rto + k] : k == 3 ? mn[L.m_rto] : k == 4 ? mx[L.m_rto] : k == 5 ? in[L.s_rto + 3]
+            : k == 6 ? mn[L.m_rto + 1] : mx[L.m_rto + 1];
+    } else if (L.fb) {
+      v = in[L.s_fb + (i - kFlowHostBase - kFlowHostCc - kFlowHostRto)];
+    }
+    __hip_atomic_store(&host[i], (uint64_t)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  }
+  if (i < L.n_bins)
+    __hip_atomic_store(&host[kFlowHostHist + i], (uint64_t)in[L.s_hist + i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  __threadfence_system();
+  __syncthreads();
+  if (i == 0) __hip_atomic_store(&host[kReportSeqWord], seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -5460,7 +5544,7 @@ void launch_ping_report(const PingArgs& a, unsigned long long* res, hipStream_t 
 
 // Flow driver (tgsim_flow_*).
 void launch_flow_init(const FlowArgs& f, hipStream_t st) {
-  const uint64_t n = std::max<uint64_t>(f.n_flows, (uint64_t)kCalReplicas * kCalMaxBins);
+  const uint64_t n = std::max<uint64_t>(f.n_own_flows, (uint64_t)kCalReplicas * kCalMaxBins);
   flow_dispatch(f, [&](auto cc, auto rto) {
     hipLaunchKernelGGL((k_flow_init<cc.value, rto.value>), dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, f);
   });
@@ -5469,55 +5553,58 @@ void launch_flow_init(const FlowArgs& f, hipStream_t st) {
 void launch_flow_recv(const FlowArgs& f, const tgsim_delivery* recs, const uint64_t* off, uint32_t n_dst,
                       uint64_t n_bound, hipStream_t st) {
   hipLaunchKernelGGL(k_flow_recv_data, dim3(cal_grid(n_bound)), dim3(256), 0, st, f, recs, off, n_dst, n_bound);
+  if (!f.n_own_flows) return;  // (a shard that owns no flow: it only answers)
   flow_dispatch(f, [&](auto cc, auto rto) {
-    hipLaunchKernelGGL((k_flow_recv_ack<cc.value, rto.value>), dim3((uint32_t)((f.n_flows + 255) / 256)), dim3(256), 0, st,
+    hipLaunchKernelGGL((k_flow_recv_ack<cc.value, rto.value>), dim3((uint32_t)((f.n_own_flows + 255) / 256)), dim3(256), 0, st,
                        f, recs, off, n_bound);
   });
 }
 
 void launch_flow_count(const FlowArgs& f, uint64_t* counts, uint32_t* cursor, uint64_t cal_bound, hipStream_t st) {
-  (void)hipMemsetAsync(counts, 0, sizeof(uint64_t) * f.cal.n_peers, st);
-  (void)hipMemsetAsync(cursor, 0, sizeof(uint32_t) * f.cal.n_peers, st);
+  (void)hipMemsetAsync(counts, 0, sizeof(uint64_t) * f.cal.n_own, st);
+  (void)hipMemsetAsync(cursor, 0, sizeof(uint32_t) * f.cal.n_own, st);
   (void)hipMemsetAsync(f.cal.ctr + kCalOffers, 0, sizeof(unsigned long long), st);
-  const dim3 grid((uint32_t)((f.n_flows + 255) / 256));
-  if (f.cc) hipLaunchKernelGGL(k_flow_count<true>, grid, dim3(256), 0, st, f, counts);
+  const dim3 grid((uint32_t)((f.n_own_flows + 255) / 256));
+  if (!f.n_own_flows) {}  // (no owned flow: the calendar's entries only)
+  else if (f.cc) hipLaunchKernelGGL(k_flow_count<true>, grid, dim3(256), 0, st, f, counts);
   else hipLaunchKernelGGL(k_flow_count<false>, grid, dim3(256), 0, st, f, counts);
   launch_cal_count(f.cal, counts, cal_bound, st);
 }
 
 void launch_flow_write(const FlowArgs& f, const uint64_t* off, uint32_t* cursor, InRec* tmp, InRec* out,
                        uint64_t cal_bound, hipStream_t st) {
-  flow_dispatch(f, [&](auto cc, auto rto) {
-    hipLaunchKernelGGL((k_flow_write<cc.value, rto.value>), dim3((uint32_t)((f.n_flows + 255) / 256)), dim3(256), 0, st, f,
-                       off, cursor, tmp);
-  });
+  if (f.n_own_flows)
+    flow_dispatch(f, [&](auto cc, auto rto) {
+      hipLaunchKernelGGL((k_flow_write<cc.value, rto.value>), dim3((uint32_t)((f.n_own_flows + 255) / 256)), dim3(256), 0, st, f,
+                         off, cursor, tmp);
+    });
   launch_cal_write(f.cal, off, cursor, tmp, out, cal_bound, st);
 }
 
 void launch_flow_report(const FlowArgs& f, unsigned long long* res, hipStream_t st) {
   hipLaunchKernelGGL(k_cal_report_init, dim3(1), dim3(256), 0, st, f.cal, res, kFlowResWords, 9u, f.cal.n_bins);
-  hipLaunchKernelGGL(k_flow_report, report_grid(f.n_flows), dim3(256), 0, st, f, res);
+  hipLaunchKernelGGL(k_flow_report, report_grid(f.n_own_flows), dim3(256), 0, st, f, res);
 }
 
 void launch_flow_cc_report(const FlowArgs& f, unsigned long long* res, hipStream_t st) {
   hipLaunchKernelGGL(k_cal_report_init, dim3(1), dim3(256), 0, st, f.cal, res, kFlowCcResWords, 5u, 0u);  // (no histogram)
-  hipLaunchKernelGGL(k_flow_cc_report, report_grid(f.n_flows), dim3(256), 0, st, f, res);
+  hipLaunchKernelGGL(k_flow_cc_report, report_grid(f.n_own_flows), dim3(256), 0, st, f, res);
 }
 
 void launch_flow_rto_report(const FlowArgs& f, unsigned long long* res, hipStream_t st) {
   (void)hipMemsetAsync(res, 0, sizeof(unsigned long long) * kFlowRtoResWords, st);
-  hipLaunchKernelGGL(k_flow_rto_report, report_grid(f.n_flows), dim3(256), 0, st, f, res);
+  hipLaunchKernelGGL(k_flow_rto_report, report_grid(f.n_own_flows), dim3(256), 0, st, f, res);
 }
 
 void launch_flow_fb(const FlowArgs& f, const uint64_t* off, const InRec* in, const uint8_t* verdict, uint64_t n_in,
                     hipStream_t st) {
-  if (!f.n_flows || !n_in) return;
-  hipLaunchKernelGGL(k_flow_fb, dim3((uint32_t)((f.n_flows + 255) / 256)), dim3(256), 0, st, f, off, in, verdict, n_in);
+  if (!f.n_own_flows || !n_in) return;
+  hipLaunchKernelGGL(k_flow_fb, dim3((uint32_t)((f.n_own_flows + 255) / 256)), dim3(256), 0, st, f, off, in, verdict, n_in);
 }
 
 void launch_flow_fb_report(const FlowArgs& f, unsigned long long* res, hipStream_t st) {
   (void)hipMemsetAsync(res, 0, sizeof(unsigned long long) * kFlowFbResWords, st);
-  hipLaunchKernelGGL(k_flow_fb_report, report_grid(f.n_flows), dim3(256), 0, st, f, res);
+  hipLaunchKernelGGL(k_flow_fb_report, report_grid(f.n_own_flows), dim3(256), 0, st, f, res);
 }
 
 void launch_ping_pairs(const PingArgs& a, uint64_t i0, uint64_t n, tgsim_ping_pair* out, hipStream_t st) {
@@ -5531,6 +5618,16 @@ void launch_ping_pack(const unsigned long long* res, const unsigned long long* c
 
 void launch_ping_unpack(const unsigned long long* in, uint32_t n_bins, uint64_t* host, uint64_t seq, hipStream_t st) {
   hipLaunchKernelGGL(k_ping_unpack, dim3(1), dim3(256), 0, st, in, n_bins, host, seq);
+}
+
+void launch_flow_pack(const unsigned long long* res, const unsigned long long* cc, const unsigned long long* rt,
+                      const unsigned long long* fb, const unsigned long long* ctr, const FlowPack& L, uint32_t seg_len,
+                      unsigned long long* out, hipStream_t st) {
+  hipLaunchKernelGGL(k_flow_pack, dim3(1), dim3(256), 0, st, res, cc, rt, fb, ctr, L, seg_len, out);
+}
+
+void launch_flow_unpack(const unsigned long long* in, const FlowPack& L, uint64_t* host, uint64_t seq, hipStream_t st) {
+  hipLaunchKernelGGL(k_flow_unpack, dim3(1), dim3(256), 0, st, in, L, host, seq);
 }
 
 void launch_gossip(const GossipArgs& g, const tgsim_delivery* recs, uint64_t n, uint64_t* counts,

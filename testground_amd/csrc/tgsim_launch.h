@@ -115,6 +115,13 @@ void launch_flow_rto_report(const FlowArgs& f, unsigned long long* res, hipStrea
 void launch_flow_fb(const FlowArgs& f, const uint64_t* off, const InRec* in, const uint8_t* verdict, uint64_t n_in,
                     hipStream_t st);
 void launch_flow_fb_report(const FlowArgs& f, unsigned long long* res, hipStream_t st);
+// tgsim_comm_flow_report: the local reports' words (cc / rt / fb: null for an unarmed part) packed into
+// the sum / min / max runs of layout L (out: kFlowPackWords), and the reduced runs published to the host
+// (kFlowHostWords: the four summaries' words, the histogram, the sequence word).
+void launch_flow_pack(const unsigned long long* res, const unsigned long long* cc, const unsigned long long* rt,
+                      const unsigned long long* fb, const unsigned long long* ctr, const FlowPack& L, uint32_t seg_len,
+                      unsigned long long* out, hipStream_t st);
+void launch_flow_unpack(const unsigned long long* in, const FlowPack& L, uint64_t* host, uint64_t seq, hipStream_t st);
 // Per-group traffic matrix (tgsim_group_matrix).  _src: words 0..9 from a window's input (off[n_src + 1],
 // in, verdict) behind its simulate kernel; n_in: the window's offered packets (picks the lanes per
 // source).  _dst: words 10..13 from delivery-ordered records, segment sg = off[sg] ..

@@ -250,7 +250,7 @@ class CABIEngine:
     # -- flow driver (tgsim_flow_*) ----------------------------------------------------------------
     def flow_init(self, flows=None, seg_len: int = 1460, ack_len: int = 64, window: int = 16, rto_ticks: int = 1,
                   max_attempts: int = 8, bin_ns: int = 0, n_bins: int = 0, cc: Optional[dict] = None,
-                  rto: Optional[dict] = None, fb: Optional[dict] = None) -> None:
+                  rto: Optional[dict] = None, fb: Optional[dict] = None, sharded: bool = False) -> None:
         """Arms the device flow driver: `flows` is an abi.FLOW_SPEC_DTYPE table sorted by src
         (workloads.flow_table_mesh); a fixed window of `window` segments, one ACK per delivered
         segment, a retransmission timer of rto_ticks per segment, at most max_attempts offers of a
@@ -263,10 +263,16 @@ class CABIEngine:
         of fail_mask, default 0: count only) arms it through tgsim_flow_init_fb with the verdict
         feedback: per-flow verdict counters (flow_fb_rows, flow_fb_report), and a flow whose data
         offer is refused with a verdict in fail_mask (bits 1 << abi.V_*, within abi.FLOW_FB_REFUSALS)
-        fails at that offer's tick."""
+        fails at that offer's tick.  sharded: through tgsim_flow_init_sharded, on an engine that may own
+        part of the peers (`flows` is still the whole run's table); the windows then run through
+        comm_step, the reports and row readers are this shard's (flow_owned), and comm_flow_report gives
+        the whole run's."""
         self.flow_cc_armed = self.flow_rto_armed = self.flow_fb_armed = False
         if flows is None:
-            self._check(self._gossip_fn("flow_init")(self._h, None, None, 0), "flow_init")
+            if sharded:
+                self._check(self._gossip_fn("flow_init_sharded")(self._h, None, None, None, None, None, 0), "flow_init_sharded")
+            else:
+                self._check(self._gossip_fn("flow_init")(self._h, None, None, 0), "flow_init")
             self._n_flows = None
             return
         t = np.ascontiguousarray(flows, dtype=abi.FLOW_SPEC_DTYPE)
@@ -280,11 +286,25 @@ class CABIEngine:
         # the narrowest entry point that takes every part asked for (each exported call stays in use)
         name, parts = (("flow_init_fb", [c, r, b]) if fb is not None else ("flow_init_rto", [c, r]) if rto is not None else
                        ("flow_init_cc", [c]) if cc is not None else ("flow_init", []))
+        if sharded:
+            name, parts = "flow_init_sharded", [c, r, b]
         self._check(self._gossip_fn(name)(self._h, C.byref(p), *parts, t.ctypes.data, len(t)), name)
         self.flow_cc_armed, self.flow_rto_armed, self.flow_fb_armed = cc is not None, rto is not None, fb is not None
         self._n_flows = len(t)
 
+    def flow_owned(self) -> tuple:
+        """(first, n): the flows of the table this engine owns, those whose src is in its shard
+        (tgsim_flow_owned); the whole table on an engine that owns every peer."""
+        first, n = C.c_uint64(0), C.c_uint64(0)
+        self._check(self._gossip_fn("flow_owned")(self._h, C.byref(first), C.byref(n)), "flow_owned")
+        return int(first.value), int(n.value)
+
     def _flow_rows(self, name: str, dtype, first: int, n: Optional[int]) -> np.ndarray:
+        # the defaults (first=0, n=None) are the owned range; an explicit range is taken as given
+        if getattr(self, "_n_flows", None) is not None and n is None and hasattr(self._lib, self._p + "flow_owned"):
+            lo, cnt = self.flow_owned()
+            first = lo if first == 0 else first
+            n = max(lo + cnt - first, 0)
         total = getattr(self, "_n_flows", None) or 0  # (unarmed: the call says so)
         n = max(total - first, 0) if n is None else n
         out = np.zeros(n, dtype=dtype)
@@ -335,6 +355,25 @@ class CABIEngine:
         n = self._check(fn(self._h, C.byref(s), hist.ctypes.data, len(hist)), "flow_report")
         out = {k: int(getattr(s, k)) for k in abi.FLOW_SUMMARY_FIELDS}
         out["hist"] = hist[:n].copy()
+        return out
+
+    def comm_flow_report(self) -> dict:
+        """flow_report of the whole run on every rank, reduced over the ranks on the device
+        (tgsim_comm_flow_report; collective, sharded flow only), with the sub-dicts `cc`, `rto` and
+        `fb` (flow_cc_report, flow_rto_report, flow_fb_report of the whole run) where armed."""
+        s = abi.FlowSummary()
+        hist = np.zeros(abi.PING_MAX_BINS, dtype=np.uint64)
+        parts = {"cc": (getattr(self, "flow_cc_armed", False), abi.FlowCCSummary(), abi.FLOW_CC_SUMMARY_FIELDS),
+                 "rto": (getattr(self, "flow_rto_armed", False), abi.FlowRtoSummary(), abi.FLOW_RTO_SUMMARY_FIELDS),
+                 "fb": (getattr(self, "flow_fb_armed", False), abi.FlowFbSummary(), abi.FLOW_FB_SUMMARY_FIELDS)}
+        args = [C.byref(st) if on else None for on, st, _ in parts.values()]
+        n = self._check(self._gossip_fn("comm_flow_report")(self._h, C.byref(s), hist.ctypes.data, len(hist), *args),
+                        "comm_flow_report")
+        out = {k: int(getattr(s, k)) for k in abi.FLOW_SUMMARY_FIELDS}
+        out["hist"] = hist[:n].copy()
+        for key, (on, st, fields) in parts.items():
+            if on:
+                out[key] = {k: int(getattr(st, k)) for k in fields}
         return out
 
     def flow_rows(self, first: int = 0, n: Optional[int] = None) -> np.ndarray:

@@ -1046,12 +1046,15 @@ def flow_reference(eng, flow: Dict, flows: np.ndarray, n_windows: int, window: i
     return out
 
 
-def flow_run(eng, n_windows: int, window: int, collect: bool = False, probe_at=(), before=None) -> Dict:
+def flow_run(eng, n_windows: int, window: int, collect: bool = False, probe_at=(), before=None, step=None) -> Dict:
     """The device loop on an armed engine (Engine.flow_init): n_windows of gen_flow + step.  Nothing
     reaches the host unless asked for: collect keeps each window's (verdicts, deliveries), probe_at
     the (rows, report) after those windows, and the (cc rows, cc report) beside them when the engine
     is armed with congestion control, the (rto rows, rto report) when it is armed with the RTT
-    estimator, and the (fb rows, fb report) last when it is armed with the verdict feedback."""
+    estimator, and the (fb rows, fb report) last when it is armed with the verdict feedback.
+    step(window) replaces eng.step (a shard of a run armed with sharded=True: eng.comm_step; the rows
+    and reports are then the shard's)."""
+    step = eng.step if step is None else step
     out = {"windows": [], "probes": {}}
     cc, rto = getattr(eng, "flow_cc_armed", False), getattr(eng, "flow_rto_armed", False)
     fb = getattr(eng, "flow_fb_armed", False)
@@ -1059,7 +1062,7 @@ def flow_run(eng, n_windows: int, window: int, collect: bool = False, probe_at=(
         if before is not None:
             before(w)
         eng.gen_flow(window)
-        eng.step(window)
+        step(window)
         if collect:
             out["windows"].append((eng.verdicts(), eng.drain()))
         if w in probe_at:
@@ -1067,6 +1070,52 @@ def flow_run(eng, n_windows: int, window: int, collect: bool = False, probe_at=(
                                 + ((eng.flow_rto_rows(), eng.flow_rto_report()) if rto else ())
                                 + ((eng.flow_fb_rows(), eng.flow_fb_report()) if fb else ()))
     return out
+
+
+# The merge rules of include/tgsim.h for the shards' flow reports: every field by sum, except these.
+_FLOW_MERGE_MIN = {"fct_min_ns", "cwnd_min", "srtt_min", "rto_min"}
+_FLOW_MERGE_MAX = {"fct_max_ns", "cwnd_max", "srtt_max", "rto_max"}
+
+
+def _merge_flow_fields(who: str, reports, fields) -> Dict:
+    reports = list(reports)
+    if not reports:
+        raise ValueError(f"{who}: no report")
+    out = {}
+    for key in fields:
+        vals = [int(r[key]) for r in reports]
+        out[key] = min(vals) if key in _FLOW_MERGE_MIN else max(vals) if key in _FLOW_MERGE_MAX else sum(vals)
+    return out
+
+
+def merge_flow_reports(reports) -> Dict:
+    """The shards' flow reports (Engine.flow_report of every rank) as the whole run's, by the merge
+    rule of include/tgsim.h: every field by sum, except fct_min_ns by min and fct_max_ns by max; hist
+    by sum (a shard without a DONE flow reports the neutral UINT64_MAX and 0).  For hosts with their own
+    exchange; Engine.comm_flow_report does the same on the device."""
+    reports = list(reports)
+    out = _merge_flow_fields("merge_flow_reports", reports, abi.FLOW_SUMMARY_FIELDS)
+    hists = [np.asarray(r["hist"], dtype=np.uint64) for r in reports]
+    if len({len(h) for h in hists}) != 1:
+        raise ValueError("merge_flow_reports: the reports' histograms differ in length")
+    out["hist"] = np.sum(hists, axis=0, dtype=np.uint64)
+    return out
+
+
+def merge_flow_cc_reports(reports) -> Dict:
+    """The shards' Engine.flow_cc_report as the whole run's: sums, cwnd_min by min, cwnd_max by max."""
+    return _merge_flow_fields("merge_flow_cc_reports", reports, abi.FLOW_CC_SUMMARY_FIELDS)
+
+
+def merge_flow_rto_reports(reports) -> Dict:
+    """The shards' Engine.flow_rto_report as the whole run's: sums, srtt_min and rto_min by min, srtt_max
+    and rto_max by max."""
+    return _merge_flow_fields("merge_flow_rto_reports", reports, abi.FLOW_RTO_SUMMARY_FIELDS)
+
+
+def merge_flow_fb_reports(reports) -> Dict:
+    """The shards' Engine.flow_fb_report as the whole run's: every field by sum."""
+    return _merge_flow_fields("merge_flow_fb_reports", reports, abi.FLOW_FB_SUMMARY_FIELDS)
 
 
 # ---------------------------------------------------------------------------------------------
