@@ -953,6 +953,63 @@ int tgsim_groups_init(void* engine, const uint16_t* group_of, uint32_t n_groups)
  * armed") on an engine without the report.  Synchronizes like tgsim_stats. */
 int64_t tgsim_group_matrix(void* engine, uint64_t* out, size_t cap, int reset);
 
+/* ---- packet capture of watched instances (tcpdump on a handful of peers) --------------------- */
+/* For up to TGSIM_CAPTURE_MAX_PEERS watched peers the engine keeps two record lists on the device,
+ * whoever made the traffic (tgsim_submit, tgsim_gen_storm, the gossip, ping and flow drivers, bridge
+ * datagrams) and whether or not deliveries are kept (TGSIM_OPT_DISCARD_DELIVERIES): every packet a
+ * watched peer offered with its verdict byte (TX), and every record delivered to it (RX).
+ * DESIGN.md §5.12.  The order is fixed by construction:
+ *   TX  after each window's simulation, for each watched peer this engine owns as a source, in
+ *       ascending peer order, one record per offered packet of its row, in the row's order.  A netem
+ *       clone makes no TX record of its own: it is the high nibble of the verdict byte.
+ *   RX  after each window's delivery, for each watched peer this engine owns as a destination, in
+ *       ascending peer order, the records delivered to it in drain order (t_ns, src, seq, clone
+ *       first).  A record flushed or lost in flight is never delivered and has no RX record.
+ * Windows append in window order.  With deliveries kept, a window's RX capture is that window's drain
+ * filtered to the watched destinations, record for record, and its TX capture the window's packets
+ * and verdict bytes filtered to the watched sources.  Shards own ascending contiguous ranges, so the
+ * per-window reads of a run's ranks concatenated in rank order are the single engine's.
+ * Room: each direction is one linear buffer of `cap` records.  A window's records are placed in
+ * capture order while room remains, so what is kept is always a prefix of the capture stream; the
+ * rest only counts in `dropped`.  Nothing is overwritten and no error is raised; a read empties the
+ * direction.  seen == records read so far + pending + dropped, per direction, at every read.
+ * While armed, tgsim_step_n runs its windows one by one and tgsim_step_sim_launch_slotted_n returns
+ * -EINVAL (as with TGSIM_OPT_METRICS and the group matrix: nothing is captured inside a fused
+ * launch); the sparse windows' direct destination buckets stay on.  An engine that never arms the
+ * capture launches nothing for it. */
+#define TGSIM_CAPTURE_MAX_PEERS 1024u
+enum tgsim_capture_dir { TGSIM_CAPTURE_TX = 0, TGSIM_CAPTURE_RX = 1 };
+typedef struct {            /* 32 B */
+    uint64_t t_ns;          /* TX: (window start tick + the packet's tick) * tick_ns; RX: the record's delivery time */
+    uint32_t src, dst, seq;
+    uint16_t len;
+    uint16_t flags;         /* RX: TGSIM_FLAG_*; TX: 0 */
+    uint8_t  verdict;       /* TX: the packet's verdict byte (both nibbles); RX: 0 */
+    uint8_t  dir;           /* enum tgsim_capture_dir */
+    uint16_t _pad; uint32_t _pad2;
+} tgsim_capture_rec;
+typedef struct {            /* 56 B */
+    uint64_t pending[2];    /* kept and not yet read, TX / RX */
+    uint64_t seen[2];       /* records of watched, owned peers since arming, kept or not */
+    uint64_t dropped[2];    /* of them, not kept for want of room */
+    uint32_t n_watched, n_owned;
+} tgsim_capture_info_t;
+/* Arms the capture: peers[n], strictly ascending, 1 <= n <= TGSIM_CAPTURE_MAX_PEERS, every entry below
+ * n_peers, the same list on every shard (an entry this engine does not own is accepted and ignored
+ * there); tx_cap / rx_cap records of room, at most 2^31 each, 0 turns that direction off.  Re-arming
+ * replaces the list, empties both buffers and zeroes the counters.  (engine, NULL, 0, 0, 0) disarms and
+ * frees (a no-op on an unarmed engine).  -EINVAL, with a tgsim_last_error text that names the entry,
+ * for an unsorted or repeated entry, an entry out of range, n of 0 or above the maximum, or both caps
+ * 0; -EBUSY while launched steps, generated windows or host packets are pending. */
+int tgsim_capture_init(void* engine, const uint32_t* peers, uint32_t n, uint64_t tx_cap, uint64_t rx_cap);
+/* The counters, after every window issued so far.  -EINVAL ("capture is not armed") when unarmed. */
+int tgsim_capture_info(void* engine, tgsim_capture_info_t* out);
+/* Copies everything pending of direction dir, empties that direction and returns the count.  With
+ * out == NULL and cap == 0: the pending count, nothing removed.  -ENOSPC when cap is below the pending
+ * count (nothing removed); -EINVAL when unarmed or for dir > 1.  Synchronizes like tgsim_group_matrix
+ * and returns a sticky simulation error as it does. */
+int64_t tgsim_capture_read(void* engine, uint32_t dir, tgsim_capture_rec* out, size_t cap);
+
 /* ---- sync counters (sync-service SignalEntry / Barrier) ------------------------------------ */
 /* K7: TGSIM_SYNC_STATES u64 counters in device memory, incremented by a kernel on the engine's sync
  * stream (never behind a queued simulation) that also writes the new value into a pinned host

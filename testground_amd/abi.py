@@ -214,6 +214,21 @@ GROUP_NAMES = (["offered", "offered_bytes"] + VERDICT_NAMES
 assert len(GROUP_NAMES) == GROUP_WORDS
 
 
+# Packet capture of watched peers (tgsim_capture_*): tgsim_capture_rec and tgsim_capture_info_t.
+CAPTURE_MAX_PEERS = 1024
+CAPTURE_TX, CAPTURE_RX = 0, 1
+CAPTURE_DTYPE = np.dtype([("t_ns", "<u8"), ("src", "<u4"), ("dst", "<u4"), ("seq", "<u4"), ("len", "<u2"), ("flags", "<u2"),
+                          ("verdict", "u1"), ("dir", "u1"), ("_pad", "<u2"), ("_pad2", "<u4")])
+
+
+class CaptureInfo(C.Structure):
+    _fields_ = [("pending", C.c_uint64 * 2), ("seen", C.c_uint64 * 2), ("dropped", C.c_uint64 * 2),
+                ("n_watched", C.c_uint32), ("n_owned", C.c_uint32)]
+
+
+assert CAPTURE_DTYPE.itemsize == 32 and C.sizeof(CaptureInfo) == 56
+
+
 class CommInfo(C.Structure):
     _fields_ = [("rank", C.c_int32), ("nranks", C.c_int32), ("exchanged_records", C.c_uint64),
                 ("max_rank_count", C.c_uint64), ("slot_cap", C.c_uint64), ("bounds", C.c_uint32 * 9),
@@ -264,6 +279,7 @@ EXPORTS = [
     "tgsim_flow_init_fb", "tgsim_flow_fb_rows", "tgsim_flow_fb_report",
     "tgsim_flow_init_sharded", "tgsim_flow_owned", "tgsim_comm_flow_report",
     "tgsim_groups_init", "tgsim_group_matrix",
+    "tgsim_capture_init", "tgsim_capture_info", "tgsim_capture_read",
     "tgsim_comm_id", "tgsim_comm_init", "tgsim_comm_step", "tgsim_comm_launch", "tgsim_comm_finish", "tgsim_comm_run", "tgsim_comm_barrier", "tgsim_comm_info",
     "tgsim_bridge_create", "tgsim_bridge_destroy", "tgsim_bridge_send", "tgsim_bridge_step",
     "tgsim_bridge_recv", "tgsim_bridge_pending", "tgsim_bridge_in_flight", "tgsim_bridge_now_tick",
@@ -362,6 +378,9 @@ def declare(lib: C.CDLL, prefix: str) -> None:
       C.POINTER(FlowRtoSummary), C.POINTER(FlowFbSummary))
     f("groups_init", C.c_int, vp, C.c_void_p, C.c_uint32)
     f("group_matrix", C.c_int64, vp, C.c_void_p, C.c_size_t, C.c_int)
+    f("capture_init", C.c_int, vp, C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64)
+    f("capture_info", C.c_int, vp, C.POINTER(CaptureInfo))
+    f("capture_read", C.c_int64, vp, C.c_uint32, C.c_void_p, C.c_size_t)
     f("offered", C.c_int64, vp, C.c_void_p, C.c_size_t)
     f("metrics", C.c_int64, vp, C.c_uint32, C.c_void_p, C.c_size_t)
     f("comm_id", C.c_int, vp)

@@ -527,6 +527,16 @@ struct tgsim_engine_s {
   DevBuf<uint16_t> d_gof;                   // group_of[N]
   DevBuf<unsigned long long> d_gmat, d_gout;  // the matrix [G][G + 1][14] and the copy the host reads
 
+  // packet capture of watched peers (tgsim_capture_*); index 0: TX (simulate stream),
+  // 1: RX (delivery stream) -- the two directions share no word but the read-only watch list
+  bool capture_on = false;
+  uint32_t cap_n = 0, cap_owned = 0;
+  uint64_t cap_room[2] = {0, 0};
+  DevBuf<uint32_t> d_cpeers;
+  DevBuf<uint64_t> d_cstart[2];
+  DevBuf<unsigned long long> d_cctr[2];
+  DevBuf<tgsim_capture_rec> d_cbuf[2];
+
   int fail(int code, const char* fmt, ...) {
     char buf[512];
     va_list ap;
@@ -1208,6 +1218,31 @@ void groups_release(Eng* E) {
   E->n_groups = 0;
 }
 
+CaptureArgs capture_args(Eng* E, uint32_t dir) {
+  CaptureArgs c{};
+  c.peers = E->d_cpeers.p;
+  c.start = E->d_cstart[dir].p;
+  c.ctr = E->d_cctr[dir].p;
+  c.buf = E->d_cbuf[dir].p;
+  c.cap = E->cap_room[dir];
+  c.n = E->cap_n;
+  c.first = E->o.shard_begin;
+  c.n_own = E->S;
+  return c;
+}
+
+void capture_release(Eng* E) {
+  E->d_cpeers.release();
+  for (uint32_t d = 0; d < 2; ++d) {
+    E->d_cstart[d].release();
+    E->d_cctr[d].release();
+    E->d_cbuf[d].release();
+    E->cap_room[d] = 0;
+  }
+  E->capture_on = false;
+  E->cap_n = E->cap_owned = 0;
+}
+
 FlowArgs flow_args(Eng* E, uint64_t win0, uint32_t n_ticks);  // (with the flow driver, further down)
 
 int run_sim(Eng* E, uint32_t n_ticks, bool local_hist = false) {
@@ -1361,6 +1396,14 @@ int run_sim(Eng* E, uint32_t n_ticks, bool local_hist = false) {
       E->ev_sim_t = E->ev_sim;
     }
     launch_group_src(group_args(E), E->d_off.p, E->d_in.p, E->d_verdict.p, E->S, E->n_in, E->st);
+    HIPCHK(hipGetLastError());
+  }
+  if (E->capture_on && E->cap_room[0]) {  // the watched sources' rows and verdict bytes, like the fold above
+    if (!E->ev_sim_t) {  // the delivery waits for k_sim, not for the capture
+      HIPCHK(hipEventRecord(E->ev_sim, E->st));
+      E->ev_sim_t = E->ev_sim;
+    }
+    launch_capture_tx(capture_args(E, 0), E->d_off.p, E->d_in.p, E->d_verdict.p, E->now_tick, E->o.tick_ns, E->st);
     HIPCHK(hipGetLastError());
   }
   if (E->flow_fb_on) {  // the flows' verdict feedback, from the step's input and verdict bytes like the fold above
@@ -1933,6 +1976,10 @@ int deliver(Eng* E, const tgsim_delivery* in, uint64_t n, hipEvent_t wait, bool 
     launch_group_dst(group_args(E), dst, E->d_doff.p, nseg, nd, n, std::max<uint64_t>(E->n_in, 1), sq);
     HIPCHK(hipGetLastError());
   }
+  if (E->capture_on && E->cap_room[1] && n_win == 1) {  // (an armed engine never fuses: n_win is 1)
+    launch_capture_rx(capture_args(E, 1), dst, E->d_doff.p, n, sq);
+    HIPCHK(hipGetLastError());
+  }
   if (timed) {
     HIPCHK(hipEventRecord(dv1, sq));
     E->dv_pending.push_back({dv0, dv1, n_win});
@@ -2028,6 +2075,10 @@ int deliver_local_from(Eng* E, const EmitRead& emit, uint32_t* emit_n, uint64_t*
     launch_group_dst(group_args(E), dst, doff.p, nd, nd, n, need_n ? n : n_in, sq);
     HIPCHK(hipGetLastError());
   }
+  if (E->capture_on && E->cap_room[1]) {
+    launch_capture_rx(capture_args(E, 1), dst, doff.p, n, sq);
+    HIPCHK(hipGetLastError());
+  }
   if (timed) {
     HIPCHK(hipEventRecord(dv1, sq));
     E->dv_pending.push_back({dv0, dv1, 1u});
@@ -2057,7 +2108,8 @@ int deliver_local(Eng* E) {
 // dense windows on an engine that owns every peer, no host packets, no per-window diagnostics.
 bool fusable(Eng* E, uint32_t n_ticks, uint32_t g, bool routed = false) {
   if (g < 2 || (E->S != E->N && !routed) || !E->staged.empty() || E->gen_q.size() < g || E->metrics_on ||
-      E->gossip_on || E->ping_on() || E->flow_on() || E->groups_on || E->sparse_mode == 1 || kSpw != 1)
+      E->gossip_on || E->ping_on() || E->flow_on() || E->groups_on || E->capture_on || E->sparse_mode == 1 ||
+      kSpw != 1)
     return false;
   for (uint32_t i = 0; i < g; ++i)
     if (E->gen_q[i].ticks != n_ticks || E->gen_q[i].n < 64ull * E->S) return false;  // sparse windows
@@ -2798,6 +2850,7 @@ void tgsim_destroy(void* e) {
   ping_release(E);
   flow_release(E);
   groups_release(E);
+  capture_release(E);
   if (E->cal.h_pub) (void)hipHostFree(E->cal.h_pub);
   if (E->cal.ev_recv) (void)hipEventDestroy(E->cal.ev_recv);
   if (E->ev_fb) (void)hipEventDestroy(E->ev_fb);
@@ -3628,6 +3681,106 @@ int64_t tgsim_group_matrix(void* e, uint64_t* out, size_t cap, int reset) {
   return static_cast<int64_t>(words);
 }
 
+// Packet capture of watched peers (include/tgsim.h).
+int tgsim_capture_init(void* e, const uint32_t* peers, uint32_t n, uint64_t tx_cap, uint64_t rx_cap) {
+  Eng* E = as_eng(e);
+  if (!E) return -EINVAL;
+  const bool disarm = !peers && !n && !tx_cap && !rx_cap;
+  constexpr uint64_t kRoomMax = 1ull << 31;
+  if (!disarm) {
+    if (n == 0 || n > kCaptureMax) return E->fail(-EINVAL, "capture: n %u outside 1..%u", n, kCaptureMax);
+    if (!peers) return E->fail(-EINVAL, "capture: no watch list for n %u", n);
+    if (!tx_cap && !rx_cap) return E->fail(-EINVAL, "capture: tx_cap and rx_cap are both 0 (nothing to capture)");
+    if (tx_cap > kRoomMax || rx_cap > kRoomMax)
+      return E->fail(-EINVAL, "capture: %s %llu above 2^31 records", tx_cap > kRoomMax ? "tx_cap" : "rx_cap",
+                     static_cast<unsigned long long>(tx_cap > kRoomMax ? tx_cap : rx_cap));
+    for (uint32_t i = 0; i < n; ++i) {
+      if (peers[i] >= E->N) return E->fail(-EINVAL, "capture: peers[%u] = %u is not below n_peers %u", i, peers[i], E->N);
+      if (i && peers[i] <= peers[i - 1])
+        return E->fail(-EINVAL, "capture: peers[%u] = %u is not above peers[%u] = %u (the list is strictly ascending)", i,
+                       peers[i], i - 1, peers[i - 1]);
+    }
+  }
+  if (disarm && !E->capture_on) return 0;
+  if (E->route_n) return E->fail(-EBUSY, "capture: launched steps are pending (finish or release them first)");
+  if (!E->gen_q.empty()) return E->fail(-EBUSY, "capture: generated windows are pending");
+  if (!E->staged.empty()) return E->fail(-EBUSY, "capture: host packets are pending for the next step");
+  HIPCHK(hipSetDevice(E->dev));
+  int rc = sync_stream(E);  // the capture kernels of the windows so far read the list and write the buffers
+  if (rc) return rc;
+  capture_release(E);
+  if (disarm) return 0;
+  const uint64_t room[2] = {tx_cap, rx_cap};
+  HIPCHK(E->d_cpeers.ensure_exact(n));
+  HIPCHK(hipMemcpyAsync(E->d_cpeers.p, peers, sizeof(uint32_t) * n, hipMemcpyHostToDevice, E->st));
+  for (uint32_t d = 0; d < 2; ++d) {
+    HIPCHK(E->d_cstart[d].ensure_exact(kCaptureMax));
+    HIPCHK(E->d_cctr[d].ensure_exact(kCapCtrWords));
+    HIPCHK(hipMemsetAsync(E->d_cctr[d].p, 0, sizeof(unsigned long long) * kCapCtrWords, E->st));
+    if (room[d]) HIPCHK(E->d_cbuf[d].ensure_exact(room[d]));
+  }
+  HIPCHK(hipStreamSynchronize(E->st));  // (the delivery stream reads the list and its counters too)
+  for (uint32_t d = 0; d < 2; ++d) E->cap_room[d] = room[d];
+  E->cap_n = n;
+  for (uint32_t i = 0; i < n; ++i)
+    if (peers[i] >= E->o.shard_begin && peers[i] - E->o.shard_begin < E->S) E->cap_owned++;
+  E->capture_on = true;
+  return 0;
+}
+
+// The counters of both directions, behind every window issued so far.
+static int capture_counters(Eng* E, unsigned long long (*ctr)[kCapCtrWords]) {
+  HIPCHK(hipSetDevice(E->dev));
+  int rc = sync_stream(E);  // TX is written on the simulate stream, RX on the delivery stream
+  if (rc) return rc;
+  if ((rc = check_sim_error(E))) return rc;
+  for (uint32_t d = 0; d < 2; ++d)
+    HIPCHK(hipMemcpy(ctr[d], E->d_cctr[d].p, sizeof(unsigned long long) * kCapCtrWords, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int tgsim_capture_info(void* e, tgsim_capture_info_t* out) {
+  Eng* E = as_eng(e);
+  if (!E) return -EINVAL;
+  if (!E->capture_on) return E->fail(-EINVAL, "capture_info: capture is not armed (tgsim_capture_init)");
+  if (!out) return E->fail(-EINVAL, "capture_info: no output");
+  unsigned long long ctr[2][kCapCtrWords];
+  int rc = capture_counters(E, ctr);
+  if (rc) return rc;
+  *out = tgsim_capture_info_t{};
+  for (uint32_t d = 0; d < 2; ++d) {
+    out->pending[d] = ctr[d][kCapCursor];
+    out->seen[d] = ctr[d][kCapSeen];
+    out->dropped[d] = ctr[d][kCapDropped];
+  }
+  out->n_watched = E->cap_n;
+  out->n_owned = E->cap_owned;
+  return 0;
+}
+
+int64_t tgsim_capture_read(void* e, uint32_t dir, tgsim_capture_rec* out, size_t cap) {
+  Eng* E = as_eng(e);
+  if (!E) return -EINVAL;
+  if (!E->capture_on) return E->fail(-EINVAL, "capture_read: capture is not armed (tgsim_capture_init)");
+  if (dir > 1) return E->fail(-EINVAL, "capture_read: dir %u is neither TGSIM_CAPTURE_TX nor TGSIM_CAPTURE_RX", dir);
+  unsigned long long ctr[2][kCapCtrWords];
+  int rc = capture_counters(E, ctr);
+  if (rc) return rc;
+  const uint64_t pending = ctr[dir][kCapCursor];
+  if (!out && !cap) return static_cast<int64_t>(pending);
+  if (cap < pending)
+    return E->fail(-ENOSPC, "capture_read: room for %zu records, %llu pending", cap, static_cast<unsigned long long>(pending));
+  if (!out) return E->fail(-EINVAL, "capture_read: no output buffer");
+  if (pending) {
+    HIPCHK(hipMemcpy(out, E->d_cbuf[dir].p, sizeof(tgsim_capture_rec) * pending, hipMemcpyDeviceToHost));
+    // the cursor goes back to 0 on the stream whose plan kernel reads it next (both streams are idle)
+    hipStream_t sq = dir == TGSIM_CAPTURE_TX ? E->st : E->dst_st;
+    HIPCHK(hipMemsetAsync(E->d_cctr[dir].p + kCapCursor, 0, sizeof(unsigned long long), sq));
+    HIPCHK(hipStreamSynchronize(sq));
+  }
+  return static_cast<int64_t>(pending);
+}
+
 int64_t tgsim_sim_capacity(void* e) {
   Eng* E = as_eng(e);
   if (!E) return -EINVAL;
@@ -3703,9 +3856,11 @@ int tgsim_step_sim_launch_slotted_n(void* e, uint32_t n_ticks, uint32_t n_win, u
   if (E->route_n == Eng::kRouteSlots) return E->fail(-EBUSY, "two launched steps are not released yet");
   if (int brc = driver_busy(E, "step_sim_launch_slotted_n")) return brc;
   HIPCHK(hipSetDevice(E->dev));
-  if (E->metrics_on || E->groups_on)  // their folds follow every window's kernel: such windows never fuse
+  if (E->metrics_on || E->groups_on || E->capture_on)  // their folds follow every window's kernel: such windows never fuse
     return E->fail(-EINVAL, "step_sim_launch_slotted_n: engine has %s: windows run unfused, call tgsim_comm_run with fuse = 1",
-                   E->metrics_on ? "TGSIM_OPT_METRICS" : "the group matrix armed (tgsim_groups_init)");
+                   E->metrics_on  ? "TGSIM_OPT_METRICS"
+                   : E->groups_on ? "the group matrix armed (tgsim_groups_init)"
+                                  : "the packet capture armed (tgsim_capture_init)");
   if (!fusable(E, n_ticks, n_win, true))
     return E->fail(-EINVAL, "step_sim_launch_slotted_n: the next %u windows are not generated dense windows of %u ticks",
                    n_win, n_ticks);

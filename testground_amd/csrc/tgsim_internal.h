@@ -473,6 +473,20 @@ struct GroupArgs {
   uint32_t n_groups, n_peers, shard_begin;
 };
 
+// Packet capture of watched peers (tgsim_capture_*), one direction: the watch list, the
+// linear record buffer and its device-resident counters.  k_capture_plan_* gives every watched entry
+// its first position for the window (start[]), k_capture_copy_* writes the records there.
+constexpr uint32_t kCaptureMax = TGSIM_CAPTURE_MAX_PEERS;
+enum CaptureCtr { kCapCursor = 0, kCapSeen = 1, kCapDropped = 2, kCapCtrWords = 4 };
+struct CaptureArgs {
+  const uint32_t* peers;     // [n] watched peer ids, strictly ascending (the whole run's list)
+  uint64_t* start;           // [n] the window's first position of each entry (plan -> copy)
+  unsigned long long* ctr;   // [kCapCtrWords] this direction's cursor, seen, dropped
+  tgsim_capture_rec* buf;    // [cap]
+  uint64_t cap;
+  uint32_t n, first, n_own;  // the owned peers [first, first + n_own): the others count nothing
+};
+
 // Engine hooks of the RCCL exchange layer (tgsim_comm.cpp), which drives the engine through the
 // public ABI and keeps its own state in the engine's comm slot (freed by tgsim_destroy).
 struct CommSlot {

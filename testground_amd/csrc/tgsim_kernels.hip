@@ -5252,6 +5252,120 @@ __global__ __launch_bounds__(256) void k_group_read(unsigned long long* m, unsig
 }
 
 // ---------------------------------------------------------------------------------------------
+// Packet capture of watched peers (tgsim_capture_*).
+//
+// Per direction and window two kernels, in stream order.  The plan (one workgroup of kCaptureMax
+// threads, a thread per watched entry) scans the entries' record counts and gives each its first
+// position behind the cursor; the copy (a wavefront per entry) writes record k of entry e at
+// start[e] + k while that is below cap.  Positions follow from the scan alone, so the kept records
+// are a prefix of (window, watched peer, row order) whatever the wavefronts' timing: no atomics.
+// The cursor, seen and dropped words of a direction are written by its plan kernel only (and by the
+// host between windows, behind a synchronization).
+static_assert(kCaptureMax == 1024, "k_capture_plan_*: one thread per watched entry");
+
+// Exclusive scan of one count per thread over the workgroup (1024 threads); *total: the sum.
+__device__ __forceinline__ uint64_t capture_scan(uint64_t v, uint64_t (*tmp)[kCaptureMax], uint64_t* total) {
+  const uint32_t t = threadIdx.x;
+  uint32_t cur = 0;
+  tmp[0][t] = v;
+  __syncthreads();
+#pragma unroll
+  for (uint32_t d = 1; d < kCaptureMax; d <<= 1) {
+    tmp[cur ^ 1][t] = tmp[cur][t] + (t >= d ? tmp[cur][t - d] : 0ull);
+    cur ^= 1;
+    __syncthreads();
+  }
+  *total = tmp[cur][kCaptureMax - 1];
+  return tmp[cur][t] - v;
+}
+
+__device__ __forceinline__ void capture_place(const CaptureArgs& c, uint64_t excl, uint64_t total) {
+  const uint32_t t = threadIdx.x;
+  const uint64_t base = c.ctr[kCapCursor];  // (read by every thread before thread 0 stores it: the barrier below)
+  if (t < c.n) c.start[t] = base + excl;
+  __syncthreads();
+  if (t == 0) {
+    const uint64_t room = c.cap - base, kept = total < room ? total : room;  // (base <= cap always)
+    c.ctr[kCapCursor] = base + kept;
+    c.ctr[kCapSeen] += total;
+    c.ctr[kCapDropped] += total - kept;
+  }
+}
+
+__global__ __launch_bounds__(1024) void k_capture_plan_tx(CaptureArgs c, const uint64_t* __restrict__ off) {
+  __shared__ uint64_t tmp[2][kCaptureMax];
+  const uint32_t t = threadIdx.x;
+  uint64_t cnt = 0;
+  if (t < c.n) {
+    const uint32_t s = c.peers[t] - c.first;  // (unsigned: a peer below `first` wraps past n_own)
+    if (s < c.n_own) cnt = off[s + 1] - off[s];
+  }
+  uint64_t total;
+  const uint64_t excl = capture_scan(cnt, tmp, &total);
+  capture_place(c, excl, total);
+}
+
+// off[] holds the exact counts; no record at or past n_bound (what the buffer was sized for) exists.
+__global__ __launch_bounds__(1024) void k_capture_plan_rx(CaptureArgs c, const uint64_t* __restrict__ off,
+                                                          uint64_t n_bound) {
+  __shared__ uint64_t tmp[2][kCaptureMax];
+  const uint32_t t = threadIdx.x;
+  uint64_t cnt = 0;
+  if (t < c.n) {
+    const uint32_t d = c.peers[t] - c.first;
+    if (d < c.n_own) {
+      const uint64_t b0 = off[d] < n_bound ? off[d] : n_bound, b1 = off[d + 1] < n_bound ? off[d + 1] : n_bound;
+      cnt = b1 - b0;
+    }
+  }
+  uint64_t total;
+  const uint64_t excl = capture_scan(cnt, tmp, &total);
+  capture_place(c, excl, total);
+}
+
+__device__ __forceinline__ void capture_store(tgsim_capture_rec* p, uint64_t t_ns, uint32_t src, uint32_t dst,
+                                              uint32_t seq, uint32_t len, uint32_t flags, uint32_t verdict, uint32_t dir) {
+  uint4* q = reinterpret_cast<uint4*>(p);  // (32-B records in a hipMalloc'ed buffer: 16-B aligned)
+  q[0] = make_uint4((uint32_t)t_ns, (uint32_t)(t_ns >> 32), src, dst);
+  q[1] = make_uint4(seq, (len & 0xFFFFu) | flags << 16, (verdict & 0xFFu) | dir << 8, 0u);
+}
+
+// A wavefront per watched entry, its lanes striding the source's row of the step's input.
+__global__ __launch_bounds__(256) void k_capture_copy_tx(CaptureArgs c, const uint64_t* __restrict__ off,
+                                                         const InRec* __restrict__ in,
+                                                         const uint8_t* __restrict__ verdict, uint64_t win0,
+                                                         uint64_t tick_ns) {
+  const uint32_t lane = threadIdx.x & 63u, e = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (e >= c.n) return;
+  const uint32_t p = c.peers[e], s = p - c.first;
+  if (s >= c.n_own) return;
+  const uint64_t b0 = off[s], b1 = off[s + 1], pos0 = c.start[e];
+  for (uint64_t i = b0 + lane; i < b1; i += kWave) {
+    const uint64_t pos = pos0 + (i - b0);
+    if (pos >= c.cap) break;  // (positions ascend with i: nothing further of this lane fits either)
+    const uint4 r = *reinterpret_cast<const uint4*>(in + i);  // dst seq tick len
+    capture_store(c.buf + pos, (win0 + r.z) * tick_ns, p, r.x, r.y, r.w, 0u, verdict[i], TGSIM_CAPTURE_TX);
+  }
+}
+
+// The same over the destination's segment of the delivery-ordered records.
+__global__ __launch_bounds__(256) void k_capture_copy_rx(CaptureArgs c, const tgsim_delivery* __restrict__ recs,
+                                                         const uint64_t* __restrict__ off, uint64_t n_bound) {
+  const uint32_t lane = threadIdx.x & 63u, e = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (e >= c.n) return;
+  const uint32_t d = c.peers[e] - c.first;
+  if (d >= c.n_own) return;
+  const uint64_t b0 = off[d] < n_bound ? off[d] : n_bound, b1 = off[d + 1] < n_bound ? off[d + 1] : n_bound;
+  const uint64_t pos0 = c.start[e];
+  for (uint64_t i = b0 + lane; i < b1; i += kWave) {
+    const uint64_t pos = pos0 + (i - b0);
+    if (pos >= c.cap) break;
+    const tgsim_delivery r = recs[i];
+    capture_store(c.buf + pos, r.t_ns, r.src, r.dst, r.seq, r.len, r.flags, 0u, TGSIM_CAPTURE_RX);
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
 // Host-side launchers.
 
 void launch_sim(const SimArgs& a, uint32_t n_wg, hipStream_t st) {
@@ -5429,6 +5543,20 @@ void launch_group_src(const GroupArgs& g, const uint64_t* off, const InRec* in, 
   if (!n_src || !n_in) return;
   const GroupGrid r = group_grid(n_src, n_in);
   hipLaunchKernelGGL(k_group_src, dim3(r.grid), dim3(256), 0, st, g, off, in, verdict, n_src, r.per_wave, r.lg);
+}
+
+void launch_capture_tx(const CaptureArgs& c, const uint64_t* off, const InRec* in, const uint8_t* verdict, uint64_t win0,
+                       uint64_t tick_ns, hipStream_t st) {
+  if (!c.n || !c.cap) return;
+  hipLaunchKernelGGL(k_capture_plan_tx, dim3(1), dim3(kCaptureMax), 0, st, c, off);
+  hipLaunchKernelGGL(k_capture_copy_tx, dim3((c.n + 3) / 4), dim3(256), 0, st, c, off, in, verdict, win0, tick_ns);
+}
+
+void launch_capture_rx(const CaptureArgs& c, const tgsim_delivery* recs, const uint64_t* off, uint64_t n_bound,
+                       hipStream_t st) {
+  if (!c.n || !c.cap) return;
+  hipLaunchKernelGGL(k_capture_plan_rx, dim3(1), dim3(kCaptureMax), 0, st, c, off, n_bound);
+  hipLaunchKernelGGL(k_capture_copy_rx, dim3((c.n + 3) / 4), dim3(256), 0, st, c, recs, off, n_bound);
 }
 
 void launch_group_dst(const GroupArgs& g, const tgsim_delivery* recs, const uint64_t* off, uint64_t n_seg,

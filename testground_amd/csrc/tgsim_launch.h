@@ -132,6 +132,15 @@ void launch_group_src(const GroupArgs& g, const uint64_t* off, const InRec* in, 
 void launch_group_dst(const GroupArgs& g, const tgsim_delivery* recs, const uint64_t* off, uint64_t n_seg,
                       uint32_t n_dst, uint64_t n_bound, uint64_t n_hint, hipStream_t st);
 void launch_group_read(const GroupArgs& g, unsigned long long* out, bool reset, hipStream_t st);
+// Packet capture (tgsim_capture_*), one direction of one window: the plan kernel (positions from a scan
+// of the watched entries' counts, the cursor, seen and dropped) and the copy kernel behind it.  _tx: from
+// the window's input (off[n_own + 1], in, verdict) behind its simulate kernel; win0: its first tick.
+// _rx: from delivery-ordered records, segment d = off[d] .. off[d + 1] holding owned destination d; no
+// record at or past n_bound is read.  Nothing is launched for a direction without room (c.cap == 0).
+void launch_capture_tx(const CaptureArgs& c, const uint64_t* off, const InRec* in, const uint8_t* verdict, uint64_t win0,
+                       uint64_t tick_ns, hipStream_t st);
+void launch_capture_rx(const CaptureArgs& c, const tgsim_delivery* recs, const uint64_t* off, uint64_t n_bound,
+                       hipStream_t st);
 // Exclusive scan of in[0..n) into out[0..n] (out[n] = total, also stored at *total when non-null);
 // pos (optional) receives a copy of out[0..n), the scatter cursors.
 // clear: the input counts, zeroed as they are read (the histogram free for its next window), or null

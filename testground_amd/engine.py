@@ -411,6 +411,45 @@ class CABIEngine:
         self._check(fn(self._h, out.ctypes.data, len(out), 1 if reset else 0), "group_matrix")
         return out.reshape(g, g + 1, abi.GROUP_WORDS)
 
+    # -- packet capture of watched peers (tgsim_capture_*) ----------------------------------------
+    def capture_init(self, peers=None, tx_cap: int = 1 << 20, rx_cap: int = 1 << 20) -> None:
+        """Arms the capture for the strictly ascending peer ids `peers` (the same list on every shard)
+        with room for tx_cap / rx_cap records (0: that direction off); re-arming empties both buffers
+        and zeroes the counters.  capture_init(None) disarms and frees."""
+        fn = self._gossip_fn("capture_init")
+        if peers is None:
+            self._check(fn(self._h, None, 0, 0, 0), "capture_init")
+            return
+        p = np.asarray(peers)
+        if p.ndim != 1:
+            raise ValueError("capture_init: peers must be a list of peer ids")
+        if len(p) and (p.min() < 0 or p.max() > 0xFFFFFFFF):
+            raise ValueError("capture_init: a peer id outside 0..2^32-1")
+        p = np.ascontiguousarray(p, dtype=np.uint32)
+        self._check(fn(self._h, p.ctypes.data if len(p) else None, len(p), tx_cap, rx_cap), "capture_init")
+
+    def capture_info(self) -> dict:
+        """tgsim_capture_info: `pending`, `seen`, `dropped` as {"tx": .., "rx": ..}, `n_watched`, `n_owned`."""
+        s = abi.CaptureInfo()
+        self._check(self._gossip_fn("capture_info")(self._h, C.byref(s)), "capture_info")
+        out = {k: {"tx": int(getattr(s, k)[0]), "rx": int(getattr(s, k)[1])} for k in ("pending", "seen", "dropped")}
+        out["n_watched"], out["n_owned"] = int(s.n_watched), int(s.n_owned)
+        return out
+
+    def capture_read(self) -> dict:
+        """Everything captured since the last read, {"tx": records, "rx": records} of abi.CAPTURE_DTYPE in
+        capture order (tgsim_capture_read); both directions are emptied."""
+        fn = self._gossip_fn("capture_read")
+        out = {}
+        for name, d in (("tx", abi.CAPTURE_TX), ("rx", abi.CAPTURE_RX)):
+            n = self._check(fn(self._h, d, None, 0), "capture_read")
+            rec = np.zeros(n, dtype=abi.CAPTURE_DTYPE)
+            if n:
+                got = self._check(fn(self._h, d, rec.ctypes.data, n), "capture_read")
+                rec = rec[:got]
+            out[name] = rec
+        return out
+
     def step(self, n_ticks: int) -> None:
         self._check(self._fn("step")(self._h, n_ticks), "step")
 

@@ -28,6 +28,7 @@ need the engine's lookahead to cover one window, which `Run` sets.
 from __future__ import annotations
 
 import dataclasses
+import errno
 import io
 import json
 import os
@@ -36,10 +37,14 @@ import tarfile
 import tempfile
 import threading
 import time
-from typing import Callable, Dict, List, Optional, Tuple
+from typing import Callable, Dict, List, Optional, Sequence, Tuple
 
+import numpy as np
+
+from . import abi
 from .bridge import NativeBridge, PacketBridge
 from .engine import LIB_PATH, EngineError
+from .pcap import write_pcap
 from .sidecar import Context, NetClient, SimReactor, SyncClient, handler
 from .sync_service import SyncService
 
@@ -145,6 +150,10 @@ class LocalSimRunnerCfg:
     # engine_factory(n_peers, **engine kwargs) -> engine; default: the HIP engine (engine.Engine)
     engine_factory: Optional[Callable] = None
     sync_service: bool = True  # serve the run's sync counters on a loopback port (sync_service.py)
+    # instances (run-wide sequence numbers) whose packets are captured on the device (Engine.capture_init)
+    # and written to <run>/<group>/<i>/capture.pcap after the run; capture_cap: records of room per direction
+    capture: Sequence[int] = ()
+    capture_cap: int = 1 << 20
 
 
 def _make_bridge(engine, n: int, cfg):
@@ -416,6 +425,18 @@ class LocalSimRunner:
             engine = Engine(n, **kw)
         else:
             engine = cfg.engine_factory(n, **kw)
+        watched = sorted(set(int(p) for p in cfg.capture))
+        if watched:
+            if not hasattr(engine, "capture_init"):
+                raise ValueError("capture: this engine has no packet capture (capture_init)")
+            if watched[0] < 0 or watched[-1] >= n:
+                raise ValueError(f"capture: instance {watched[0] if watched[0] < 0 else watched[-1]} outside 0..{n - 1}")
+            try:
+                engine.capture_init(watched, tx_cap=cfg.capture_cap, rx_cap=cfg.capture_cap)
+            except EngineError as e:
+                if e.code != -errno.ENOSYS:
+                    raise
+                raise ValueError(f"capture: this engine has no packet capture ({e})") from e
 
         run_ctx = Context(timeout=cfg.run_timeout_s)
         with self._lk:
@@ -489,10 +510,26 @@ class LocalSimRunner:
         result.Outcome = OUTCOME_SUCCESS if ok and not reactor.errors else (
             OUTCOME_CANCELED if canceled else OUTCOME_FAILURE)
         os.makedirs(run_dir, exist_ok=True)
+        doc = {}
+        if watched:  # one read at the end: each watched instance's TX and RX into its own output directory
+            doc["capture"] = engine.capture_info()
+            got = engine.capture_read()
+            recs = np.concatenate([got["tx"], got["rx"]])
+            where, peer = {}, 0
+            for g in job.Groups:
+                for i in range(g.Instances):
+                    where[peer] = os.path.join(run_dir, g.ID, str(i))
+                    peer += 1
+            for p in watched:
+                mine = recs[((recs["dir"] == abi.CAPTURE_TX) & (recs["src"] == p))
+                            | ((recs["dir"] == abi.CAPTURE_RX) & (recs["dst"] == p))]
+                os.makedirs(where[p], exist_ok=True)
+                with open(os.path.join(where[p], "capture.pcap"), "wb") as f:
+                    write_pcap(f, mine, subnet_base=getattr(engine, "subnet_base", 16 << 24))
         with open(os.path.join(run_dir, "run.json"), "w") as f:
             json.dump({"outcome": result.Outcome, "outcomes": {g: str(o) for g, o in result.Outcomes.items()},
                        "errors": result.Errors, "simulated_ns": result.SimulatedNs,
-                       "engine_stats": engine.stats()}, f, indent=1,
+                       "engine_stats": engine.stats(), **doc}, f, indent=1,
                       default=lambda o: o.tolist() if hasattr(o, "tolist") else int(o))
         if cfg.engine_factory is None:
             engine.close()

@@ -1181,6 +1181,57 @@ def group_reachability(m, round_trip: bool = False) -> np.ndarray:
 
 
 # ---------------------------------------------------------------------------------------------
+# Packet capture of watched peers (tgsim_capture_*): the host model of one window.
+def capture_reference(watched, pkts, verdicts, drained, start_tick: int, tick_ns: int, owned=None,
+                      generated: bool = False) -> Tuple[np.ndarray, np.ndarray]:
+    """What an engine owning the peers owned = (lo, hi) (default: every watched peer) captures in one
+    window, from what a host sees of it: the packets offered (abi.PKT_DTYPE), their verdict bytes (one
+    per packet, in the packets' order) and the records drained after the step.  Returns (tx, rx) of
+    abi.CAPTURE_DTYPE in the capture's order (include/tgsim.h):
+      tx  the packets of watched, owned sources in (src, tick, seq, dst) order -- a row of the
+          engine's input is in (tick, seq) order, and host packets arrive in submit order; with
+          generated=True the packets are a generated window's, already in row order (the oracle's
+          `offered`), and are only stable-sorted by src;
+      rx  the drained records of watched, owned destinations, by destination, each in drain order.
+    start_tick: the window's first tick (stats()["now_tick"] before the step)."""
+    w = np.asarray(watched, dtype=np.int64)
+    lo, hi = (0, 1 << 32) if owned is None else owned
+    w = w[(w >= lo) & (w < hi)]
+    tx = np.zeros(0, dtype=abi.CAPTURE_DTYPE)
+    if pkts is not None and len(pkts):
+        v = np.asarray(verdicts, dtype=np.uint8)
+        if len(v) != len(pkts):
+            raise ValueError("capture_reference: one verdict byte per offered packet")
+        keep = np.nonzero(np.isin(pkts["src"], w))[0]
+        p, v = pkts[keep], v[keep]
+        order = np.argsort(p["src"], kind="stable") if generated else np.lexsort((p["dst"], p["seq"], p["tick"], p["src"]))
+        p, v = p[order], v[order]
+        tx = np.zeros(len(p), dtype=abi.CAPTURE_DTYPE)
+        tx["t_ns"] = (np.uint64(start_tick) + p["tick"].astype(np.uint64)) * np.uint64(tick_ns)
+        tx["src"], tx["dst"], tx["seq"], tx["len"] = p["src"], p["dst"], p["seq"], p["len"]
+        tx["verdict"], tx["dir"] = v, abi.CAPTURE_TX
+    rx = np.zeros(0, dtype=abi.CAPTURE_DTYPE)
+    if drained is not None and len(drained):
+        d = drained[np.isin(drained["dst"], w)]
+        d = d[np.argsort(d["dst"], kind="stable")]
+        rx = np.zeros(len(d), dtype=abi.CAPTURE_DTYPE)
+        for k in ("t_ns", "src", "dst", "seq", "len", "flags"):
+            rx[k] = d[k]
+        rx["dir"] = abi.CAPTURE_RX
+    return tx, rx
+
+
+def merge_captures(per_rank_reads) -> Dict[str, np.ndarray]:
+    """One window's Engine.capture_read() results of a run's shards, in rank order, as the single engine's:
+    shards own ascending contiguous ranges and every direction is in ascending peer order, so the merge
+    is concatenation.  (Reads that span several windows do not merge this way.)"""
+    reads = list(per_rank_reads)
+    if not reads:
+        raise ValueError("merge_captures: no reads")
+    return {k: np.concatenate([np.asarray(r[k], dtype=abi.CAPTURE_DTYPE) for r in reads]) for k in ("tx", "rx")}
+
+
+# ---------------------------------------------------------------------------------------------
 # C4: gossip flood.  The engine generates and consumes the traffic on the device
 # (tgsim_gossip_init / tgsim_gen_gossip); this module only shapes the peers and runs windows.
 GOSSIP_MIN_LAT = 5 * Millisecond
